@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """bench.py -- the embedding + feature-interaction hot path, forward+backward, on synthetic Criteo-shaped batches.
 
-    python bench.py [--config fm|youtubednn|deepfm|sasrec] --gpus N --steps K --warmup W
+    python bench.py [--config fm|youtubednn|deepfm|sasrec] --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line, nothing else.  --full adds what takes runs
+of its own: the dominant kernel's roofline figures (HIP events around eager steps after the timed region), the CPU
+baseline and, for fm on one GPU, the other configurations' sub-runs under "configs".  --dump-outputs DIR writes what
+the last timed step computed (prediction, loss, a fixed sample of every parameter's gradient) as DIR/<name>.npy.
 
 --config fm (the default: BASELINE.json configs[1], the configuration the headline metric is quoted on) is described
 below; youtubednn / deepfm / sasrec are configs[2..4] (see `MODEL_CONFIGS`): with --gpus N > 1 the first two run in
@@ -134,6 +139,43 @@ def cpu_baseline(dim, B, dist, budget_s):
     return {"value": B * n / el, "unit": "samples/s", "cores": best, "kind": "port",
             "sample": "%d full steps of the same workload (B=%d, dim=%d, %s ids) on torch CPU ops, %d of %d "
                       "hardware threads (fastest of a 1/8-batch calibration)" % (n, B, dim, dist, best, ncpu)}
+
+
+DUMP_LIMIT = 64 << 20          # bytes: what --dump-outputs may write in all
+DUMP_FULL_NUMEL = 1 << 18      # gradients up to this size are written whole, larger ones as a fixed sample of rows
+DUMP_ROWS = 1024
+
+
+def dump_outputs(path, arrays, params, touched):
+    """--dump-outputs: `arrays` (name -> tensor, written whole) and the gradient of every parameter as PATH/<name>.npy,
+    float32 (float64 stays float64).  A gradient of more than DUMP_FULL_NUMEL elements is written as a fixed sample of its
+    rows: DUMP_ROWS rows drawn by a seeded generator, plus the rows of the first DUMP_ROWS ids of the last step's batch
+    for the feature named in the parameter's name (`touched`: feature -> ids), sorted.  The same arguments give the same
+    rows in every run and every build."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    g = torch.Generator().manual_seed(20240601)
+    out = OrderedDict((k, v) for k, v in arrays.items() if v is not None)
+    for name, p in params:
+        if p.grad is None:
+            continue
+        grad = p.grad.detach()
+        if grad.numel() > DUMP_FULL_NUMEL and grad.dim() >= 1:
+            V = grad.shape[0]
+            rows = [torch.randint(0, V, (DUMP_ROWS,), generator=g)]
+            for tok in name.split("."):
+                if tok in touched:
+                    ids = touched[tok].reshape(-1)[:DUMP_ROWS].long().cpu()
+                    rows.append(ids[(ids >= 0) & (ids < V)])
+            grad = grad[torch.cat(rows).unique().to(grad.device)]
+        out["grad." + name] = grad
+    out = OrderedDict((k, (v.detach().double() if v.dtype == torch.float64 else v.detach().float()).cpu().numpy())
+                      for k, v in out.items())
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("bench.py: --dump-outputs would write %.1f MB, more than %d MB" % (total / 2.0 ** 20, DUMP_LIMIT >> 20))
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def measured_traffic(path, kernel):
@@ -415,9 +457,15 @@ def run_model_config(args, rank, world, dev):
     if sharded and not hasattr(model, "sync_grads") and world > 1:
         dp_flat = [p for p in params if p.requires_grad]
 
-    def step_over(xb):
+    # --dump-outputs: the loss of the step over resident batch k (key -1: the static buffers `x`) as its last call left it
+    outs = {} if args.dump_outputs else None
+
+    def step_over(xb, key=-1):
         def one_step():
-            return _model_step(xb)
+            loss = _model_step(xb)
+            if outs is not None:
+                outs[key] = loss
+            return loss
         return one_step
 
     # --optimizer: the step continues into an optimiser step (not part of BASELINE's fwd+bwd metric: reported beside it).
@@ -469,7 +517,7 @@ def run_model_config(args, rank, world, dev):
                 # a refill is one copy_ launch per input tensor, 40 of them for DeepFM's feature dict
                 rotating_graphs = []
                 for k in range(K):
-                    rotating_graphs.append(GraphedStep(step_over(batches[k]), warmup=3 if k == 0 else 2, reuse_grads=reuse,
+                    rotating_graphs.append(GraphedStep(step_over(batches[k], k), warmup=3 if k == 0 else 2, reuse_grads=reuse,
                                                        params=params,
                                                        pool=rotating_graphs[0].pool() if rotating_graphs else None))
                 step = rotating_graphs[0]
@@ -492,7 +540,7 @@ def run_model_config(args, rank, world, dev):
         try:
             rotating_graphs = []
             for k in range(K):
-                rotating_graphs.append(GraphedStep(step_over(batches[k]), warmup=3 if k == 0 else 2, reuse_grads=False,
+                rotating_graphs.append(GraphedStep(step_over(batches[k], k), warmup=3 if k == 0 else 2, reuse_grads=False,
                                                    params=params, capture_error_mode="thread_local",
                                                    pool=rotating_graphs[0].pool() if rotating_graphs else None))
             step = rotating_graphs[0]
@@ -548,7 +596,7 @@ def run_model_config(args, rank, world, dev):
         work = 5.0 * B * 200 * 200 * 64                                                   # 5 causal-halved L x L x d GEMMs
         roof = {"bound": "mfma", "peak": FP32_MFMA_PEAK * 1e3, "unit": "GFLOP/s"}
     timer = ops.KernelTimer(want)
-    if step is eager_step:
+    if step is eager_step and args.full:
         ops.kernel_timer = timer
     if world > 1:
         torch.distributed.barrier()
@@ -560,7 +608,13 @@ def run_model_config(args, rank, world, dev):
     if world > 1:
         torch.distributed.barrier()
     el = time.perf_counter() - t0
-    if step is not eager_step:
+    if args.dump_outputs and rank == 0:
+        # (before anything else runs a step: the eager steps of --full below overwrite the gradients)
+        last = args.warmup + args.steps - 1
+        loss = outs.get(last % K if rotating_graphs is not None else -1)
+        touched = OrderedDict((k, v) for k, v in batches[last % K].items() if not v.is_floating_point())
+        dump_outputs(args.dump_outputs, OrderedDict([("loss", loss)]), model.named_parameters(), touched)
+    if step is not eager_step and args.full:
         # the replay cannot be bracketed: time the dominant kernel with HIP events over eager steps queued behind fills
         # (on the stream the captured steps' autograd nodes live on: a backward on another stream than a parameter's
         #  AccumulateGrad node makes the engine sync the two and warn)
@@ -655,7 +709,7 @@ def run_model_config(args, rank, world, dev):
         out["metric"] = "samples/sec fwd+bwd+update (beside the fwd+bwd metric of BASELINE.json)"
     if store is not None:
         out["config"]["exchange"] = "padded capacity_factor=%g, overflow=%s" % (factor, overflow)
-    if world == 1 and not args.no_cpu_baseline and not sharded:
+    if args.full and world == 1 and not args.no_cpu_baseline and not sharded:
         out["cpu_baseline"] = model_cpu_baseline(cfg, args, args.cpu_seconds)
     print(json.dumps(out))
     return held
@@ -671,8 +725,14 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (default 65536; sasrec 4096)")
     ap.add_argument("--dim", type=int, default=16)
     ap.add_argument("--dist", choices=["uniform", "zipf"], default="uniform")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the dominant kernel's roofline figures, the CPU baseline "
+                         "and (fm, one GPU) the other configurations' sub-runs under \"configs\"")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (prediction, loss, a fixed sample of every "
+                         "parameter's gradient) as DIR/<name>.npy")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: time budget of the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline and the sub-runs")
     ap.add_argument("--eager", action="store_true", help="launch every step from Python instead of replaying a hipGraph")
     ap.add_argument("--fresh-grads", action="store_true",
                     help="allocate and zero-fill new dense gradients every step (autograd's default) instead of re-zeroing "
@@ -723,7 +783,7 @@ def main():
                     help="model configs, one GPU: append an optimiser step to every step (sparse_adam: only the touched rows of "
                          "the tables, recbox_amd.optim; dense_adam: torch.optim.Adam over every parameter, as the reference does)")
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="fm, one GPU: do not append the time-boxed youtubednn / deepfm / sasrec sub-runs under \"configs\"")
+                    help="--full, fm, one GPU: do not append the time-boxed youtubednn / deepfm / sasrec sub-runs under \"configs\"")
     ap.add_argument("--scaling", choices=["weak", "strong"], default=None,
                     help="N > 1: weak = --batch samples PER GPU (per-GPU work fixed: the default of fm, deepfm, sasrec); strong "
                          "= --global-batch samples split B/N per GPU (the default of youtubednn: SURVEY.md 8d states cfg 3 as "
@@ -852,8 +912,11 @@ def main():
     loss_fn = get_loss("binary_crossentropy")
 
     params = list(model.parameters())
+    # --dump-outputs: (prediction, loss) of the step over resident batch k (key -1: the static buffer), as the last call of
+    # that step left them -- for a captured step, the graph's own output tensors, which every replay rewrites
+    outs = {} if args.dump_outputs else None
 
-    def step_over(Xk, yk):
+    def step_over(Xk, yk, key=-1):
         def one_step():
             for p in params:                  # == model.zero_grad(set_to_none=True) without walking the module tree
                 p.grad = None
@@ -864,12 +927,14 @@ def main():
                 model.sync_grads()            # replicated small tables / numeric weights / bias: one all-reduce
             else:
                 ops.backward(loss)            # == loss.backward() with the constant 1 as its gradient (no ones_like fill)
+            if outs is not None:
+                outs[key] = (prob, loss)
             return loss
         return one_step
 
     eager_step = step_over(X, y)              # reads the static buffer `batch` (refill(i) puts batch i % K there)
 
-    def prefetching_step(Xk, yk, mine, X_next, nxt):
+    def prefetching_step(Xk, yk, mine, X_next, nxt, key):
         """The same step with its id sort made one step AHEAD: `mine` holds the sorted ids of this batch (made while the
         previous step ran), and while this step runs the ids of the NEXT batch are sorted into `nxt` on the side stream --
         what a training loop whose loader is one batch ahead does.  One sort per step, as before; it has left the chain
@@ -888,6 +953,8 @@ def main():
             loss = loss_fn(prob, yk, reduction="mean")
             ops.backward(loss)
             cur.wait_stream(side)
+            if outs is not None:
+                outs[key] = (prob, loss)
             return loss
         return one_step
 
@@ -931,7 +998,7 @@ def main():
                 steps_per_launch = S
                 for k in range(0, K, S):
                     if S > 1:
-                        fns = [step_over(*inputs_of[k + j]) for j in range(S)]
+                        fns = [step_over(*inputs_of[k + j], key=k + j) for j in range(S)]
 
                         def fn(fns=fns):
                             out = None
@@ -940,8 +1007,8 @@ def main():
                             return out
                     else:
                         Xk, yk = inputs_of[k]
-                        fn = (prefetching_step(Xk, yk, sorted_ids[k], inputs_of[(k + 1) % K][0], sorted_ids[(k + 1) % K])
-                              if prefetch else step_over(Xk, yk))
+                        fn = (prefetching_step(Xk, yk, sorted_ids[k], inputs_of[(k + 1) % K][0], sorted_ids[(k + 1) % K], k)
+                              if prefetch else step_over(Xk, yk, key=k))
                     rotating_graphs.append(GraphedStep(fn, warmup=3 if k == 0 else 2,
                                                        reuse_grads=ops.config.reuse_grad_buffers, params=params,
                                                        pool=rotating_graphs[0].pool() if rotating_graphs else None))
@@ -1013,7 +1080,7 @@ def main():
     warm_timer = ops.KernelTimer(timer.want)
     alone_timer = ops.KernelTimer(timer.want)
     plain_eager = step is eager_step or (sharded and graph_note == "eager launches")
-    if plain_eager:
+    if plain_eager and args.full:
         ops.kernel_timer = timer
     if world > 1:
         torch.distributed.barrier()
@@ -1026,7 +1093,17 @@ def main():
     if world > 1:
         torch.distributed.barrier()
     el = time.perf_counter() - t0
-    if not plain_eager:
+    if args.dump_outputs and rank == 0:
+        # (before anything else runs a step: the eager steps of --full below overwrite the gradients)
+        last = warmup_done + args.steps - 1
+        if rotating_graphs is not None:
+            key, X_last = last % K, inputs_of[last % K][0]
+        else:
+            key, X_last = -1, X
+        prob, loss = outs.get(key, (None, getattr(step, "loss", None)))
+        touched = OrderedDict((name, X_last[name]) for name, spec in fmw.fm.features.items() if spec["type"] == "categorical")
+        dump_outputs(args.dump_outputs, OrderedDict([("y_pred", prob), ("loss", loss)]), model.named_parameters(), touched)
+    if not plain_eager and args.full:
         # a graph replay cannot be bracketed from Python: time the dominant kernel with HIP events
         # on the launch stream over the same steps launched eagerly right after the timed region
         # Launched eagerly the step is host-bound (the GPU idles between kernels and the kernel would be timed on a
@@ -1163,9 +1240,9 @@ def main():
                                          if cap_factor else "exact all-to-all-v")
             if overflow:
                 out["config"]["warning"] = "exchange capacity overflowed: rerun with a larger --capacity-factor"
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.dim, B, args.dist, args.cpu_seconds)
-        if world == 1 and not sharded and not args.no_cpu_baseline and not args.no_extra_configs:
+        if args.full and world == 1 and not sharded and not args.no_cpu_baseline and not args.no_extra_configs:
             out["configs"] = extra_configs(args)
         print(json.dumps(out))
     if world > 1 or args.force_sharded:
@@ -1189,7 +1266,7 @@ def extra_configs(args):
             ("youtubednn", ["--config", "youtubednn"]), ("deepfm", ["--config", "deepfm"]), ("sasrec", ["--config", "sasrec"])]
     for cfg, extra in runs:
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(min(args.steps, 20)),
-               "--warmup", str(min(args.warmup, 5)), "--cpu-seconds", "6", "--dist", args.dist] + extra
+               "--warmup", str(min(args.warmup, 5)), "--cpu-seconds", "6", "--dist", args.dist, "--full"] + extra
         t0 = time.perf_counter()
         try:
             proc = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=budget)

@@ -1,6 +1,6 @@
 """Average duration of ONE kernel over a slice of its launches in a rocprofv3 --kernel-trace rocpd database.
     python profiles/kernel_slice.py <results.db> <name-substring> <first-launch> <count>
-bench.py launches the FM forward kernel in several phases (eager warm-up while the graphs are captured, the replayed warm-up
+bench.py --full launches the FM forward kernel in several phases (eager warm-up while the graphs are captured, the replayed warm-up
 and timed steps, then eager launches that measure it as it runs in the step / warm / alone); `rocprofv3 --stats` averages all
 of them.  This prints the average of the replayed launches only -- the number bench.py's `roofline.kernel_ms` (the kernel as
 it runs in the step) has to agree with -- next to the overall one."""
