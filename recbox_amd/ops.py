@@ -1394,6 +1394,11 @@ def fm_fused(emb_plan, lr_plan, inputs, emb_params, lr_params, bias=None, extra=
     wire slot extra_index[b, t] (``route``); slots >= rows are lookups that found no room: zero row, no grad.
     with_prob: return (logit, sigmoid(logit)) -- the second written by the same kernel, not differentiable by itself
     (``sigmoid_output(logit, prob)`` turns it into the model's y_pred)."""
+    if emb_plan is not None and lr_plan is not None and \
+            [s.param for s in emb_plan.specs] != [s.param for s in lr_plan.specs]:
+        # the backward keys a feature's LR gradient by its embedding table: features sharing one embedding table must
+        # share their LR table too, or their LR gradients would land in one of them
+        raise ValueError("fm_fused: the LR tables must be shared exactly where the embedding tables are")
     tail = ((bias,) if bias is not None else ())
     has_extra = 0
     if extra is not None:

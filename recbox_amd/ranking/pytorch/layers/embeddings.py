@@ -59,6 +59,15 @@ class FeatureEmbedding(nn.Module):
         return self.embedding_layer.dict2tensor(feature_emb_dict, dynamic_emb_dim=dynamic_emb_dim)
 
 
+def fm_fused_takes_dim(dim):
+    """Embedding dims of the fused FM body (rbx_fm_fwd / rbx_fm_bwd).  dispatch_fm_fwd has lane groups of up to 64
+    units -- D floats, or D / 4 float4s when D % 4 == 0 -- and refuses wider rows (D = 65, 260).  Rows of more than 32
+    float4s (D = 132 .. 256) would take the backward's sorted tier in its 64-lane vector form
+    (segment_*_kernel<FmPolicy, 64, 1, true>), which left rows of a few thousand lookups up to 2 % off; the library
+    refuses them (kFmMaxDim in rbx_fm_fused.hip) and those dims compose the layers instead."""
+    return dim <= 64 or (dim % 4 == 0 and dim <= 128)
+
+
 class FeatureEmbeddingDict(nn.Module):
     def __init__(self, feature_map, embedding_dim, embedding_initializer="partial(nn.init.normal_, std=1e-4)",
                  required_feature_columns=None, not_required_feature_columns=None, use_pretrain=True,
@@ -215,9 +224,9 @@ class FeatureEmbeddingDict(nn.Module):
         return names, values, cached[0], cached[1]
 
     def fusable(self, plan, posts):
-        """True when the FM / LR body can be fused: one id per sample, no encoders, one dim."""
-        return (plan is not None and plan.uniform_dim is not None and all(p is None for p in posts)
-                and all(s.seq_len == 1 and s.pool == POOL_NONE for s in plan.specs))
+        """True when the FM / LR body can be fused: one id per sample, no encoders, one dim the fused kernels take."""
+        return (plan is not None and plan.uniform_dim is not None and fm_fused_takes_dim(plan.uniform_dim)
+                and all(p is None for p in posts) and all(s.seq_len == 1 and s.pool == POOL_NONE for s in plan.specs))
 
     def forward(self, inputs, feature_source=[], feature_type=[]):
         names, values, plan, posts = self.plan_for(inputs, feature_source, feature_type)

@@ -33,6 +33,13 @@ def inputs_from_batch(feature_map, batch, feature_source=None):
     return X
 
 
+def _same_sharing(plan, lplan):
+    """The fused backward keys an LR gradient by its field's EMBEDDING table: fields that share an embedding table
+    (share_embedding) but not their LR tables -- the reference's LogisticRegression builds one per feature -- would have
+    their LR gradients summed into one of them.  Such a model composes the layers."""
+    return [s.param for s in plan.specs] == [s.param for s in lplan.specs]
+
+
 class FM(nn.Module):
     """y = sigmoid(LR(X) + 0.5 * sum_d[(sum_f e)^2 - sum_f e^2])."""
 
@@ -48,7 +55,8 @@ class FM(nn.Module):
         lr = self.fm.lr_layer.embedding_layer.embedding_layer
         names, values, plan, posts = emb.plan_for(X)
         lnames, _, lplan, lposts = lr.plan_for(X)
-        if self.fused and emb.fusable(plan, posts) and lr.fusable(lplan, lposts) and names == lnames:
+        if (self.fused and emb.fusable(plan, posts) and lr.fusable(lplan, lposts) and names == lnames
+                and _same_sharing(plan, lplan)):
             # gather + LR + interaction (+ the output sigmoid) in ONE kernel; [B, F, D] is never written (rbx_fm_fwd / rbx_fm_bwd)
             return ops.fm_fused(plan.plan, lplan.plan, values, [m.weight for m in plan.modules],
                                 [m.weight for m in lplan.modules], self.fm.lr_layer.bias, with_prob=with_prob,
@@ -72,7 +80,8 @@ class FM(nn.Module):
         lr = self.fm.lr_layer.embedding_layer.embedding_layer
         names, values, plan, posts = emb.plan_for(X)
         lnames, _, lplan, lposts = lr.plan_for(X)
-        if not (self.fused and emb.fusable(plan, posts) and lr.fusable(lplan, lposts) and names == lnames):
+        if not (self.fused and emb.fusable(plan, posts) and lr.fusable(lplan, lposts) and names == lnames
+                and _same_sharing(plan, lplan)):
             raise ValueError("FM.presort: only the fused path sorts ahead of its step")
         return ops.fm_presort(plan.plan, lplan.plan, values, [m.weight for m in plan.modules],
                               [m.weight for m in lplan.modules], into=into)
@@ -181,7 +190,7 @@ class ShardedFM(nn.Module):
         lr = self.fm.lr_layer.embedding_layer.embedding_layer
         names, values, plan, posts = emb.plan_for(X)
         lnames, _, lplan, lposts = lr.plan_for(X)
-        if not (emb.fusable(plan, posts) and lr.fusable(lplan, lposts) and names == lnames):
+        if not (emb.fusable(plan, posts) and lr.fusable(lplan, lposts) and names == lnames and _same_sharing(plan, lplan)):
             raise NotImplementedError("ShardedFM fuses one-id-per-sample categorical and numeric features only")
         return values, plan, lplan
 

@@ -42,6 +42,18 @@ def _make(rule, params):
 @pytest.mark.parametrize("fused", [True, False])
 @pytest.mark.parametrize("rule", ["sgd", "adagrad", "adam"])
 def test_sparse_row_step_equals_torch_rule_on_touched_rows(rule, fused):
+    _sparse_row_step(rule, fused, 16)
+
+
+@pytest.mark.parametrize("fused", [True, False])
+@pytest.mark.parametrize("rule", ["sgd", "adagrad", "adam"])
+def test_sparse_row_step_equals_torch_rule_on_touched_rows_at_dim_10(rule, fused):
+    """The same at the library's default embedding dim: rbx_fm_sparse_update walks the tier plans with the non-vector row
+    update."""
+    _sparse_row_step(rule, fused, 10)
+
+
+def _sparse_row_step(rule, fused, dim):
     """Four steps of an FM over tables of 5 .. 70 000 rows (the fused body: tier A tables by bitmap, tier B by sorted run
     heads; the layer-composed model: rbx_embed_sparse_update for FeatureEmbedding + the LR-only fused call): every table
     and its optimiser state equal the torch rule applied to the rows the batch looked up; rows it did not look up are
@@ -49,8 +61,8 @@ def test_sparse_row_step_equals_torch_rule_on_touched_rows(rule, fused):
     from recbox_amd import ops, optim
     from recbox_amd.ranking.pytorch.models import FM
     vocabs = [37, 5, 3001, 211, 70000]
-    fm, _, _ = _criteo_like(4, vocabs, 16, seed=3)
-    model = FM(fm, 16, fused=fused).cuda()
+    fm, _, _ = _criteo_like(4, vocabs, dim, seed=3)
+    model = FM(fm, dim, fused=fused).cuda()
     with torch.no_grad():
         for p in model.parameters():
             p.normal_(0, 0.1)
@@ -73,7 +85,7 @@ def test_sparse_row_step_equals_torch_rule_on_touched_rows(rule, fused):
         for flag in (False, True):                      # fresh gradients, then the persistent buffers
             ops.config.reuse_grad_buffers = flag
             for k, B in enumerate([300, 700, 64, 700]):
-                _, X, y = _criteo_like(B, vocabs, 16, seed=50 + k + 10 * int(flag), zipf=bool(k % 2))
+                _, X, y = _criteo_like(B, vocabs, dim, seed=50 + k + 10 * int(flag), zipf=bool(k % 2))
                 Xc, yc = _cuda(X), y.cuda()
                 opt.zero_grad()
                 for p in rest:

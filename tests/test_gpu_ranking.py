@@ -263,7 +263,7 @@ def test_fused_fm_matches_layer_path_and_oracle(B, zipf):
 @pytest.mark.parametrize("dim", [8, 32, 64, 128])
 def test_fused_fm_of_other_dims_matches_the_oracle(dim):
     """The fused FM body at embedding dims other than the benchmark's 16: the general forward kernel, the sorted backward for
-    every table (tier A is for rows of up to 16 floats) and the numeric features' reductions in whichever form fits the
+    every table (tier A takes rows of up to 64 floats; only its LDS form is limited to 16) and the numeric features' reductions in whichever form fits the
     workgroup's LDS (512-sample units up to dim ~40, fm_numeric_partial_kernel beyond) -- logits and every gradient against
     the float64-free oracle restatement of the model."""
     from oracle import torch_ref as R
