@@ -114,6 +114,11 @@ int make_plan(const rbx_field_t* fields, int n, int64_t B, const float* dout, in
   }
   if (lookups >= (1ull << 31) || rows >= (1ull << 31))
     return fail(RBX_ERR_UNSUPPORTED, "too many lookups/rows for one call (%llu / %llu)", lookups, rows);
+  // widths dispatch_reduce has no lane-group form for are refused here, before the workspace is sized or the ids sorted
+  // (vector D > 1024, scalar D > 256): the reduce would refuse them after the sort's launches
+  if (p->n_cat > 0 && pow2_ceil(p->vec ? p->max_dim / 4 : p->max_dim) > 256)
+    return fail(RBX_ERR_UNSUPPORTED, "embedding dim %d too large for one lane group (%s units)", p->max_dim,
+                p->vec ? "float4" : "scalar");
   p->n_lookups = static_cast<unsigned>(lookups);
   p->total_rows = static_cast<unsigned>(rows);
   // segments: maximal runs of consecutive fields closed under table sharing.  Tables are numbered in first-seen order,

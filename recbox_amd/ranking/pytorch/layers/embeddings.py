@@ -64,7 +64,9 @@ def fm_fused_takes_dim(dim):
     units -- D floats, or D / 4 float4s when D % 4 == 0 -- and refuses wider rows (D = 65, 260).  Rows of more than 32
     float4s (D = 132 .. 256) would take the backward's sorted tier in its 64-lane vector form
     (segment_*_kernel<FmPolicy, 64, 1, true>), which left rows of a few thousand lookups up to 2 % off; the library
-    refuses them (kFmMaxDim in rbx_fm_fused.hip) and those dims compose the layers instead."""
+    refuses them (kFmMaxDim in rbx_fm_fused.hip) and those dims compose the layers instead.  The composed path runs
+    the same three kernels with GenericPolicy, and tests/test_gpu_embed_dims.py holds it to the float64 bound at those
+    dims with hot rows: the defect is in FmPolicy's part (its flush at 64 lanes), not in the fallback."""
     return dim <= 64 or (dim % 4 == 0 and dim <= 128)
 
 
