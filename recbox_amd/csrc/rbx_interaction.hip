@@ -279,9 +279,12 @@ static int dispatch_fm(bool bwd, const float* emb, const float* dout, int64_t B,
 static int run_interaction(bool bwd, const float* emb, long long sb, const float* dout, int64_t B, int F, int D, int mode,
                            float* out, long long dsb, void* stream) {
   if (B == 0) return RBX_OK;   // empty batch: nothing to do, pointers may be NULL
-  if (emb == nullptr || out == nullptr || (bwd && dout == nullptr)) return fail(RBX_ERR_INVALID, "NULL tensor");
   if (B < 0 || F <= 0 || D <= 0) return fail(RBX_ERR_INVALID, "bad shape B=%lld F=%d D=%d", (long long)B, F, D);
   if (mode < 0 || mode > 3) return fail(RBX_ERR_INVALID, "InnerProductInteraction output mode %d is not supported", mode);
+  // one field in a pairwise mode: the output (and the upstream gradient) has no element, its pointer may be NULL
+  const bool no_pairs = mode >= 2 && F < 2;
+  if (emb == nullptr || (out == nullptr && (bwd || !no_pairs)) || (bwd && dout == nullptr && !no_pairs))
+    return fail(RBX_ERR_INVALID, "NULL tensor");
   if (B == 0) return RBX_OK;
   if (sb < static_cast<long long>(F) * D || (bwd && dsb < static_cast<long long>(F) * D))
     return fail(RBX_ERR_INVALID, "interaction: batch stride smaller than n_fields * dim");
@@ -294,7 +297,7 @@ static int run_interaction(bool bwd, const float* emb, long long sb, const float
   }
   const size_t lds = static_cast<size_t>(F) * D * sizeof(float);
   if (lds > 64 * 1024) return fail(RBX_ERR_UNSUPPORTED, "F*D=%d too large for the pairwise modes", F * D);
-  if (F < 2) return RBX_OK;
+  if (F < 2 && !bwd) return RBX_OK;   // no pair: the output is empty; the backward still writes its zeros (j == i is skipped)
   if (bwd)
     hipLaunchKernelGGL(pair_bwd_kernel, dim3(static_cast<unsigned>(B)), dim3(64), lds, s, emb, sb, dout, F, D, mode, out, dsb);
   else
@@ -409,8 +412,8 @@ extern "C" int rbx_pairmul_fwd(const float* d_left, const float* d_right, int64_
   using namespace rbx;
   if (batch == 0) return RBX_OK;
   if (batch < 0 || n_fields <= 0 || dim <= 0) return fail(RBX_ERR_INVALID, "pairmul: bad shape");
+  if (n_fields < 2) return RBX_OK;   // no pair: the output (and a per-pair left) has no element, NULL is fine
   if (!d_left || !d_right || !d_out) return fail(RBX_ERR_INVALID, "pairmul: NULL tensor");
-  if (n_fields < 2) return RBX_OK;
   const size_t lds = static_cast<size_t>(2) * n_fields * dim * sizeof(float);
   if (lds > 64 * 1024) return fail(RBX_ERR_UNSUPPORTED, "pairmul: F*D=%d too large", n_fields * dim);
   hipLaunchKernelGGL(pairmul_fwd_kernel, dim3(static_cast<unsigned>(batch)), dim3(64), lds, as_stream(stream), d_left, d_right,
@@ -423,6 +426,14 @@ extern "C" int rbx_pairmul_bwd(const float* d_left, const float* d_right, const 
   using namespace rbx;
   if (batch == 0) return RBX_OK;
   if (batch < 0 || n_fields <= 0 || dim <= 0) return fail(RBX_ERR_INVALID, "pairmul_bwd: bad shape");
+  if (n_fields < 2) {                // no pair: the gradients that have elements are zero, and this call writes them
+    const size_t bytes = static_cast<size_t>(batch) * n_fields * dim * sizeof(float);
+    if (!d_dright || (!per_pair && !d_dleft)) return fail(RBX_ERR_INVALID, "pairmul_bwd: NULL tensor");
+    if (hipMemsetAsync(d_dright, 0, bytes, as_stream(stream)) != hipSuccess ||
+        (!per_pair && hipMemsetAsync(d_dleft, 0, bytes, as_stream(stream)) != hipSuccess))
+      return fail(RBX_ERR_LAUNCH, "pairmul_bwd: memset failed");
+    return RBX_OK;
+  }
   if (!d_left || !d_right || !d_dout || !d_dleft || !d_dright) return fail(RBX_ERR_INVALID, "pairmul_bwd: NULL tensor");
   const size_t lds = static_cast<size_t>(2) * n_fields * dim * sizeof(float);
   if (lds > 64 * 1024) return fail(RBX_ERR_UNSUPPORTED, "pairmul_bwd: F*D=%d too large", n_fields * dim);

@@ -618,7 +618,7 @@ def embed_lookup(plan, inputs, params, pad_rows=False):
 
 class _Interaction(torch.autograd.Function):
     """InnerProductInteraction on [B, F, D]; the [F, D] block of a sample may be the leading columns of a wider row
-    (batch stride > F * D): it is read, and its gradient written, in place."""
+    (batch stride > F * D): it is read in place.  The gradient is a tight [B, F, D] tensor of its own."""
 
     @staticmethod
     def forward(ctx, emb, mode):
@@ -630,6 +630,12 @@ class _Interaction(torch.autograd.Function):
                 (B <= 1 or emb.stride(0) >= F * D)):
             emb = emb.contiguous().float()
         sb = emb.stride(0) if B > 1 else F * D
+        if mode <= 1 and D % 4 == 0 and D > 256 and (emb.data_ptr() % 16 != 0 or sb % 4 != 0):
+            # a float4 dim on a view that is not 16-byte aligned is a layout accident; its scalar form (D lanes' worth of
+            # units > 256) does not exist, so the block is copied to an aligned buffer instead of being refused; the copy
+            # is what the backward reads, so a second [B, F, D] buffer lives until then
+            emb = emb.clone(memory_format=torch.contiguous_format)
+            sb = F * D
         P = F * (F - 1) // 2
         shape = {0: (B, 1), 1: (B, D), 2: (B, P), 3: (B, P, D)}[mode]
         out = torch.empty(shape, dtype=torch.float32, device=emb.device)
@@ -644,8 +650,6 @@ class _Interaction(torch.autograd.Function):
         B, F, D = emb.shape
         dout = dout.contiguous().float()
         demb = torch.empty((B, F, D), dtype=torch.float32, device=emb.device)
-        if F < 2 and ctx.mode >= 2:
-            demb.zero_()
         check(lib.rbx_interaction_bwd(_ptr(emb), ctx.sb, _ptr(dout), B, F, D, ctx.mode, _ptr(demb), F * D, _stream()))
         return demb, None
 
@@ -2786,7 +2790,7 @@ class _PairMul(torch.autograd.Function):
         left, right = ctx.saved_tensors
         B, F, D = right.shape
         g = g.contiguous().float()
-        dleft, dright = torch.zeros_like(left), torch.zeros_like(right)
+        dleft, dright = torch.empty_like(left), torch.empty_like(right)      # every element is written, also with one field
         check(lib.rbx_pairmul_bwd(_ptr(left), _ptr(right), _ptr(g), B, F, D, ctx.per_pair, _ptr(dleft), _ptr(dright),
                                   _stream()))
         return dleft, dright, None
