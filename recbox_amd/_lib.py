@@ -19,6 +19,12 @@ RBX_I32, RBX_I64, RBX_F32, RBX_F64 = 0, 1, 2, 3
 FIELD_CATEGORICAL, FIELD_NUMERIC, FIELD_DENSE = 0, 1, 2
 POOL_NONE, POOL_SUM, POOL_MEAN_VALUE, POOL_MEAN_ID, POOL_SUM_ID, POOL_CONCAT = 0, 1, 2, 3, 4, 5
 INTERACTION_MODES = {"product_sum": 0, "bi_interaction": 1, "inner_product": 2, "elementwise_product": 3}
+# ``phases`` of rbx_fm_sort_phases: ids -> the workspace's compact int32 matrix (both tiers need it done); tier B: (row,
+# sample) pairs + radix sort; tier A: the per-block sorts
+FM_SORT_IDS, FM_SORT_TIER_B, FM_SORT_TIER_A = 1, 2, 4
+# ``phases`` of rbx_fm_bwd (the same bits mean other things there): the categorical tables (needs the sort); numeric weights +
+# bias (does not); STORE the numeric / bias gradients instead of adding; with FM_BWD_TABLES: leave tier A / tier B out
+FM_BWD_TABLES, FM_BWD_NUMERIC, FM_BWD_STORE, FM_BWD_SKIP_TIER_A, FM_BWD_SKIP_TIER_B = 1, 2, 4, 8, 16
 
 
 class rbx_field_t(ctypes.Structure):

@@ -206,27 +206,20 @@ class _SparseRows(object):
             n = plan.n if plan is not None else 1
             st_arrays.append([self._ptr_array(n, dict((i, self._state_of(p)["s"][k]) for i, p in sel.items())
                                               if k < self.n_state else {}) for k in range(2)])
-        lead = rec.plans[0] if rec.plans[0] is not None else rec.plans[-1]
-        _, keep = lead.bind_inputs(rec.inputs)
         st = ops._stream()
         if rec.kind == "embed":
             plan = rec.plans[0]
+            plan.bind_inputs(rec.inputs)
             plan.bind_params(rec.params[0], rec.grads[0])
             check(lib.rbx_embed_sparse_update(plan.arr, plan.n, rec.B, ops._ptr(rec.ws), rec.ws_bytes, ctypes.byref(opt),
                                               st_arrays[0][0], st_arrays[0][1], st))
         else:
-            emb_plan, lr_plan = rec.plans
-            if emb_plan is not None:
-                emb_plan.bind_params(rec.params[0], rec.grads[0])
-                if lr_plan is not None:
-                    lr_plan.bind_inputs(keep)
-            if lr_plan is not None:
-                lr_plan.bind_params(rec.params[1], rec.grads[1])
-            ea = emb_plan.arr if emb_plan is not None else None
-            la = lr_plan.arr if lr_plan is not None else None
-            e_arr = st_arrays[0] if emb_plan is not None else [None, None]
-            l_arr = st_arrays[1] if lr_plan is not None else [None, None]
-            check(lib.rbx_fm_sparse_update(ea, la, lead.n, rec.B, ops._ptr(rec.ws), rec.ws_bytes, ctypes.byref(opt),
+            tb = rec.tables
+            tb.bind_inputs(rec.inputs)
+            tb.bind(rec.grads[0] + rec.grads[1])
+            e_arr = st_arrays[0] if tb.emb_plan is not None else [None, None]
+            l_arr = st_arrays[1] if tb.lr_plan is not None else [None, None]
+            check(lib.rbx_fm_sparse_update(tb.ea, tb.la, tb.n, rec.B, ops._ptr(rec.ws), rec.ws_bytes, ctypes.byref(opt),
                                            e_arr[0], e_arr[1], l_arr[0], l_arr[1], st))
         return stepped
 
