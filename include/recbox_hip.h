@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define RBX_VERSION 124          /* 0.1.24: rbx_sort_chained (the id sort in 1 + passes launches); 0.1.23: rbx_fm_tier_c / rbx_fm_rezero_fusable, rbx_linear_fwd_bnstats / rbx_linear_dx_bnsums / rbx_batchnorm_*_from_partials removed (variants that lost their A/B); 0.1.22: rbx_cin_outer_*; 0.1.21: rbx_prelu_* / rbx_dropout / rbx_dice_* (csrc/rbx_act.hip); 0.1.20: rbx_fm_quad (rbx_fm_fwd's kernel for ids that are columns of one batch tensor); 0.1.19: rbx_seqblock_* (the row-local chains of a SASRec block as single passes); 0.1.18: rbx_fm_tier_c (the fused FM backward's sort-free tier C), rbx_opt_advance, rbx_opt_t.d_step_size, rbx_comm_bind_collectives takes ncclCommUserRank; 0.1.17: rbx_all_reduce / rbx_all_gather / rbx_comm_bind_collectives (every collective of the sharded step on the caller's stream); 0.1.16: rbx_linear_dx_scaled / rbx_linear_dwdb_scaled, rbx_rowscale_seq / rbx_seq_colsum; 0.1.15: rbx_linear_fwd_bnstats / rbx_linear_dx_bnsums / rbx_batchnorm_*_from_partials; 0.1.14: rbx_split_bf16 / _register / _unregister (f32 GEMM on the bf16 matrix cores); 0.1.13: rbx_fm_sort_phases, rbx_fm_bwd phases bits 3 / 4 (round 3: the fused FM backward in
+#define RBX_VERSION 124          /* 0.1.24: rbx_sort_chained (the id sort in 1 + passes launches), then rbx_bag_t / rbx_embed_csr_fwd / _bwd_workspace_size / _sort / _bwd (ragged bags; additions only, the number stays); 0.1.23: rbx_fm_tier_c / rbx_fm_rezero_fusable, rbx_linear_fwd_bnstats / rbx_linear_dx_bnsums / rbx_batchnorm_*_from_partials removed (variants that lost their A/B); 0.1.22: rbx_cin_outer_*; 0.1.21: rbx_prelu_* / rbx_dropout / rbx_dice_* (csrc/rbx_act.hip); 0.1.20: rbx_fm_quad (rbx_fm_fwd's kernel for ids that are columns of one batch tensor); 0.1.19: rbx_seqblock_* (the row-local chains of a SASRec block as single passes); 0.1.18: rbx_fm_tier_c (the fused FM backward's sort-free tier C), rbx_opt_advance, rbx_opt_t.d_step_size, rbx_comm_bind_collectives takes ncclCommUserRank; 0.1.17: rbx_all_reduce / rbx_all_gather / rbx_comm_bind_collectives (every collective of the sharded step on the caller's stream); 0.1.16: rbx_linear_dx_scaled / rbx_linear_dwdb_scaled, rbx_rowscale_seq / rbx_seq_colsum; 0.1.15: rbx_linear_fwd_bnstats / rbx_linear_dx_bnsums / rbx_batchnorm_*_from_partials; 0.1.14: rbx_split_bf16 / _register / _unregister (f32 GEMM on the bf16 matrix cores); 0.1.13: rbx_fm_sort_phases, rbx_fm_bwd phases bits 3 / 4 (round 3: the fused FM backward in
                                   * two tiers); 0.1.11: rbx_fm_fwd grew d_prob; 0.1.10: rbx_field_t grew table_stride (round 2) */
 #define RBX_MAX_FIELDS 64        /* fields per call */
 #define RBX_NO_ID INT64_MIN      /* "no such id" for padding_idx / mask_id */
@@ -134,6 +134,63 @@ int rbx_embed_bwd_indexed(const rbx_field_t* fields, int32_t n_fields, int64_t b
                           const float* d_dout, int64_t out_stride_b, const int32_t* d_dout_index,
                           const float* d_row_scale, int32_t accumulate, void* d_workspace, size_t workspace_bytes,
                           void* stream);
+
+/* ---- K1-K3 for RAGGED bags (CSR): indices / offsets gather-pool, forward and backward (csrc/rbx_embed_csr.hip) ----
+ * The same pooled lookups as a sequence feature of rbx_embed_fwd, for a caller that holds its multi-hot ids unpadded: the
+ * layout of torch.nn.EmbeddingBag and of every loader that does not pad to max_len.  Semantics kept: the pooling variants
+ * of core/pytorch/layers/sequence.py:4-20 (MaskedSumPooling / MaskedAveragePooling) and of
+ * third_party/rechub/basic/layers.py:176-230 (InputMask + SumPooling / AveragePooling), each exactly as rbx_pool_t
+ * defines it for padded ids -- a bag is the history without its padded tail.
+ *   indices  flat [nnz] ids of any rbx_dtype_t (the `.long()` cast happens in registers), element stride indices_stride;
+ *   offsets  [batch + 1], RBX_I32 or RBX_I64, contiguous: bag b = indices[offsets[b] : offsets[b + 1]).  offsets[0] may be
+ *            > 0 and offsets[batch] < nnz (ids outside every bag are never looked up); a bag may be empty: a zero output
+ *            row, and for the mean pools a scale of 1 / (0 + eps) times a zero sum = 0.
+ *   pool     RBX_POOL_SUM, RBX_POOL_SUM_ID, RBX_POOL_MEAN_ID or RBX_POOL_MEAN_VALUE; RBX_POOL_NONE / RBX_POOL_CONCAT return
+ *            RBX_ERR_UNSUPPORTED.
+ * Malformed offsets cannot make a kernel read outside indices[0, nnz): every bag is clamped to 0 <= begin <= end <= nnz
+ * before an index is read, and bit 1 (value 2) of *d_status is set when the clamp changed anything (a decreasing pair, a
+ * negative value, a value above nnz).  Ids outside [0, vocab) set bit 0 and read as zero rows, as in rbx_embed_fwd.
+ *   rbx_embed_csr_fwd   one launch per (float4 | scalar) class over all bags of the call; bag b of descriptor i goes to
+ *                       d_out + b * out_stride_b + bags[i].out_off -- the slots may sit inside the [batch, width] block
+ *                       an rbx_embed_fwd call fills.  d_row_scale [n_bags, batch]: written for the mean pools (may be
+ *                       NULL without one).  A bag is summed in list order by the lane-group form rbx_embed_fwd uses for
+ *                       that dim: bit-equal to the padded call over the same live ids.
+ *   rbx_embed_csr_sort  (global row, bag) pairs of the in-range, unmasked, non-padding ids that lie inside a bag, plus an
+ *                       int32 lookup -> bag map in the workspace; ONE segmented radix sort per call (the passes of
+ *                       rbx_embed_sort; key width derived the same way: the bits of the largest table group's row count).
+ *   rbx_embed_csr_bwd   the contract of rbx_embed_bwd: dense [vocab, dim] gradients into bags[i].grad (NULL = frozen),
+ *                       every touched row written once, the padding_idx row zero, masked ids contribute nothing, bags
+ *                       that share a `table` pointer are merged, accumulate as there, no float atomics: bit-identical
+ *                       from run to run.  The mean scale is read per bag (d_row_scale[i * batch + b]).
+ * Limits: n_bags <= RBX_MAX_BAGS; nnz of one descriptor and batch at most 2^26; the nnz of a call together below 2^31
+ * (positions outside every bag take part in the sort as dropped pairs); dims as rbx_embed_fwd (1..256 lane-group units). */
+#define RBX_MAX_BAGS 32
+typedef struct rbx_bag {
+  const void*  indices;          /* [nnz] ids */
+  const void*  offsets;          /* [batch + 1] bag boundaries */
+  const float* table;            /* [vocab, dim] */
+  float*       grad;             /* backward only: dense grad, same shape as table; NULL = frozen */
+  int64_t      nnz;
+  int64_t      indices_stride;   /* element stride of indices */
+  int64_t      vocab;
+  int64_t      padding_idx;      /* row that gets zero grad; RBX_NO_ID if unset */
+  int64_t      mask_id;          /* *_ID pools: ids equal to it get weight 0; RBX_NO_ID if unset */
+  int64_t      out_off;          /* float offset of the slot inside an output row */
+  int32_t      dim;
+  int32_t      indices_dtype;    /* rbx_dtype_t */
+  int32_t      offsets_dtype;    /* RBX_I32 or RBX_I64 */
+  int32_t      pool;             /* rbx_pool_t */
+  float        eps;              /* MEAN pools */
+  int32_t      reserved;         /* 0 */
+} rbx_bag_t;
+int rbx_embed_csr_fwd(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, float* d_out, int64_t out_stride_b,
+                      float* d_row_scale, int32_t* d_status, void* stream);
+size_t rbx_embed_csr_bwd_workspace_size(const rbx_bag_t* bags, int32_t n_bags, int64_t batch);
+int rbx_embed_csr_sort(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, void* d_workspace, size_t workspace_bytes,
+                       int32_t* d_status, void* stream);
+int rbx_embed_csr_bwd(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, const float* d_dout, int64_t out_stride_b,
+                      const float* d_row_scale, int32_t accumulate, void* d_workspace, size_t workspace_bytes,
+                      void* stream);
 
 /* ---- K4: InnerProductInteraction / rechub FM on a materialised [B,F,D] tensor ---
  * ranking/pytorch/layers/interactions/inner_product.py:40-56,

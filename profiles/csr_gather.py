@@ -1,0 +1,160 @@
+"""Ragged (CSR) gather-pool against the padded lookup at BASELINE cfg 3's shape: B = 65 536 samples, one 10 M x 128 table,
+MEAN_ID pooling.  Times the C-ABI calls themselves (forward, id sort, backward with accumulate = 1 into a persistent
+gradient, so that no zero fill is inside the bracket) with HIP events on torch's current stream: 3 warm-up rounds, then
+``--repeats`` rounds in which the variants of a case ALTERNATE in one process; median, min and max per call in microseconds.
+
+    python profiles/csr_gather.py [--repeats 20] [--rows 10000000] [--out FILE]
+
+Cases: (1) every bag 50 ids = the padded L = 50 call's lookups; (2) lengths uniform in 1 .. 50 against the same ids padded
+to 50; (3) skewed lengths (bags of 1 .. 9 ids, 0.1 % of them 1 000 .. 5 000) against the same nnz spread evenly."""
+import argparse
+import os
+import statistics
+import subprocess
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from recbox_amd import _embed_host as host  # noqa: E402
+from recbox_amd import _lib, ops  # noqa: E402
+from recbox_amd._lib import lib  # noqa: E402
+
+B, D, L = 65536, 128, 50
+
+
+def bracket(fns, repeats):
+    """[(median, min, max) in us] of every callable, the callables alternating inside each round."""
+    for _ in range(3):
+        for f in fns:
+            f()
+    torch.cuda.synchronize()
+    times = [[] for _ in fns]
+    for _ in range(repeats):
+        for t, f in zip(times, fns):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            f()
+            b.record()
+            b.synchronize()
+            t.append(a.elapsed_time(b) * 1e3)
+    return [(statistics.median(t), min(t), max(t)) for t in times]
+
+
+class Padded(object):
+    def __init__(self, emb, grad, ids):
+        self.plan = host.Plan([host.Lookup("h", _lib.FIELD_CATEGORICAL, emb, D, pool=_lib.POOL_MEAN_ID, seq_len=ids.shape[1],
+                                           mask_id=0, eps=1e-16)]).plan
+        self.ids, self.w, self.g = ids, emb.weight, grad
+        self.out = torch.empty(B, D, device="cuda")
+        self.scale = torch.empty(1, B, device="cuda")
+        self.plan.bind_inputs([ids])
+        self.plan.bind_params([self.w], [self.g])
+        self.nbytes = lib.rbx_embed_bwd_workspace_size(self.plan.arr, 1, B)
+        self.ws = torch.empty(self.nbytes, dtype=torch.uint8, device="cuda")
+        self.lookups = ids.numel()
+
+    def fwd(self):
+        _lib.check(lib.rbx_embed_fwd(self.plan.arr, 1, B, self.out.data_ptr(), D, self.scale.data_ptr(), None, ops._stream()))
+
+    def sort(self):
+        _lib.check(lib.rbx_embed_sort(self.plan.arr, 1, B, self.ws.data_ptr(), self.nbytes, None, ops._stream()))
+
+    def bwd(self):
+        _lib.check(lib.rbx_embed_bwd(self.plan.arr, 1, B, self.out.data_ptr(), D, self.scale.data_ptr(), 1, self.ws.data_ptr(),
+                                     self.nbytes, ops._stream()))
+
+
+class Ragged(object):
+    def __init__(self, emb, grad, bags):
+        self.plan = ops.BagPlan([ops.BagSpec("h", D, 0, 0, _lib.POOL_MEAN_ID, emb.num_embeddings, mask_id=0, eps=1e-16)])
+        self.bags, self.w, self.g = bags, emb.weight, grad
+        self.out = torch.empty(B, D, device="cuda")
+        self.scale = torch.empty(1, B, device="cuda")
+        self.plan.bind_inputs([bags])
+        self.plan.bind_params([self.w], [self.g])
+        self.nbytes = lib.rbx_embed_csr_bwd_workspace_size(self.plan.arr, 1, B)
+        self.ws = torch.empty(self.nbytes, dtype=torch.uint8, device="cuda")
+        self.lookups = bags.nnz
+
+    def fwd(self):
+        _lib.check(lib.rbx_embed_csr_fwd(self.plan.arr, 1, B, self.out.data_ptr(), D, self.scale.data_ptr(), None, ops._stream()))
+
+    def sort(self):
+        _lib.check(lib.rbx_embed_csr_sort(self.plan.arr, 1, B, self.ws.data_ptr(), self.nbytes, None, ops._stream()))
+
+    def bwd(self):
+        _lib.check(lib.rbx_embed_csr_bwd(self.plan.arr, 1, B, self.out.data_ptr(), D, self.scale.data_ptr(), 1,
+                                         self.ws.data_ptr(), self.nbytes, ops._stream()))
+
+
+def bags_of(lengths, rows, gen):
+    offsets = torch.zeros(B + 1, dtype=torch.int64)
+    torch.cumsum(lengths, 0, out=offsets[1:])
+    return ops.Bags(torch.randint(1, rows, (int(offsets[-1]),), generator=gen).cuda(), offsets.cuda())
+
+
+def padded_of(bags):
+    lengths = (bags.offsets[1:] - bags.offsets[:-1])
+    ids = torch.zeros(B, L, dtype=torch.int64, device="cuda")
+    ids[torch.arange(L, device="cuda")[None, :] < lengths[:, None]] = bags.indices
+    return ids
+
+
+def case(title, names, variants, repeats, lines):
+    lines.append("\n### %s\n" % title)
+    lines.append("| variant | lookups | forward us (min .. max) | sort us | backward us | sort + backward us |")
+    lines.append("|---|---|---|---|---|---|")
+    res = [bracket([getattr(v, what) for v in variants], repeats) for what in ("fwd", "sort", "bwd")]
+    for k, (n, v) in enumerate(zip(names, variants)):
+        f, s, b = res[0][k], res[1][k], res[2][k]
+        lines.append("| %s | %d | %.1f (%.1f .. %.1f) | %.1f (%.1f .. %.1f) | %.1f (%.1f .. %.1f) | %.1f |"
+                     % (n, v.lookups, f[0], f[1], f[2], s[0], s[1], s[2], b[0], b[1], b[2], s[0] + b[0]))
+    if len(variants) == 2:
+        lines.append("\nratio %s / %s: forward %.3f, sort %.3f, backward %.3f, sort + backward %.3f"
+                     % (names[1], names[0], res[0][1][0] / res[0][0][0], res[1][1][0] / res[1][0][0],
+                        res[2][1][0] / res[2][0][0], (res[1][1][0] + res[2][1][0]) / (res[1][0][0] + res[2][0][0])))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=20)
+    ap.add_argument("--rows", type=int, default=10000000)
+    ap.add_argument("--out", default="", help="also write the markdown report to this file")
+    a = ap.parse_args()
+    gen = torch.Generator().manual_seed(7)
+    emb = torch.nn.Embedding(a.rows, D).cuda()
+    grad = torch.zeros_like(emb.weight)
+    try:
+        commit = subprocess.run(["git", "rev-parse", "--short", "HEAD"], stdout=subprocess.PIPE, stderr=subprocess.DEVNULL,
+                                text=True).stdout.strip() or "working tree"
+    except OSError:
+        commit = "working tree"
+    lines = ["box: %s, torch %s; commit: %s; B = %d, table %d x %d, MEAN_ID, %d repeats, variants alternating"
+             % (torch.cuda.get_device_name(0), torch.__version__, commit, B, a.rows, D, a.repeats)]
+    full = bags_of(torch.full((B,), L, dtype=torch.int64), a.rows, gen)
+    pad = Padded(emb, grad, full.indices.view(B, L))
+    case("1. every bag %d ids (the padded call's lookups; `padded again` = its run-to-run spread)" % L,
+         ["padded", "CSR", "padded again"], [pad, Ragged(emb, grad, full), Padded(emb, grad, full.indices.view(B, L))],
+         a.repeats, lines)
+    uni = bags_of(torch.randint(1, L + 1, (B,), generator=gen), a.rows, gen)
+    case("2. lengths uniform in 1 .. %d against the same ids padded to %d" % (L, L), ["padded", "CSR"],
+         [Padded(emb, grad, padded_of(uni)), Ragged(emb, grad, uni)], a.repeats, lines)
+    skew = torch.randint(1, 10, (B,), generator=gen)
+    where = torch.randperm(B, generator=gen)[:B // 1000]
+    skew[where] = torch.randint(1000, 5001, (where.numel(),), generator=gen)
+    total = int(skew.sum())
+    even = torch.full((B,), total // B, dtype=torch.int64)
+    even[:total - int(even.sum())] += 1
+    case("3. skewed lengths (1 .. 9, 0.1 pct of the bags 1 000 .. 5 000) against the same nnz spread evenly", ["even", "skewed"],
+         [Ragged(emb, grad, bags_of(even, a.rows, gen)), Ragged(emb, grad, bags_of(skew, a.rows, gen))], a.repeats, lines)
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+        with open(a.out, "w") as fh:
+            fh.write(text)
+
+
+if __name__ == "__main__":
+    main()

@@ -46,6 +46,30 @@ class rbx_field_t(ctypes.Structure):
                 ("table_stride", ctypes.c_int64)]
 
 
+RBX_MAX_BAGS = 32
+STATUS_BAD_ID, STATUS_BAD_OFFSETS = 1, 2     # bits of the kernels' status word
+
+
+class rbx_bag_t(ctypes.Structure):
+    """One ragged multi-hot feature (indices / offsets) of rbx_embed_csr_*."""
+    _fields_ = [("indices", ctypes.c_void_p),
+                ("offsets", ctypes.c_void_p),
+                ("table", ctypes.c_void_p),
+                ("grad", ctypes.c_void_p),
+                ("nnz", ctypes.c_int64),
+                ("indices_stride", ctypes.c_int64),
+                ("vocab", ctypes.c_int64),
+                ("padding_idx", ctypes.c_int64),
+                ("mask_id", ctypes.c_int64),
+                ("out_off", ctypes.c_int64),
+                ("dim", ctypes.c_int32),
+                ("indices_dtype", ctypes.c_int32),
+                ("offsets_dtype", ctypes.c_int32),
+                ("pool", ctypes.c_int32),
+                ("eps", ctypes.c_float),
+                ("reserved", ctypes.c_int32)]
+
+
 class rbx_shard_geom_t(ctypes.Structure):
     _fields_ = [("world", ctypes.c_int32), ("dim", ctypes.c_int32), ("n_rows", ctypes.c_int32),
                 ("n_pool", ctypes.c_int32), ("batch", ctypes.c_int64), ("cap_rows", ctypes.c_int64),
@@ -66,6 +90,7 @@ class rbx_rowcopy_t(ctypes.Structure):
 
 _P = ctypes.c_void_p
 _FP = ctypes.POINTER(rbx_field_t)
+_BP = ctypes.POINTER(rbx_bag_t)
 _RP = ctypes.POINTER(rbx_rowcopy_t)
 _GP = ctypes.POINTER(rbx_shard_geom_t)
 _OP = ctypes.POINTER(rbx_opt_t)
@@ -82,6 +107,10 @@ SIGNATURES = {
     "rbx_embed_sort": (ctypes.c_int, [_FP, _i32, _i64, _P, _sz, _P, _P]),
     "rbx_embed_bwd": (ctypes.c_int, [_FP, _i32, _i64, _P, _i64, _P, _i32, _P, _sz, _P]),
     "rbx_embed_bwd_indexed": (ctypes.c_int, [_FP, _i32, _i64, _P, _i64, _P, _P, _i32, _P, _sz, _P]),
+    "rbx_embed_csr_fwd": (ctypes.c_int, [_BP, _i32, _i64, _P, _i64, _P, _P, _P]),
+    "rbx_embed_csr_bwd_workspace_size": (_sz, [_BP, _i32, _i64]),
+    "rbx_embed_csr_sort": (ctypes.c_int, [_BP, _i32, _i64, _P, _sz, _P, _P]),
+    "rbx_embed_csr_bwd": (ctypes.c_int, [_BP, _i32, _i64, _P, _i64, _P, _i32, _P, _sz, _P]),
     "rbx_shard_int_chunk": (_sz, [_GP]),
     "rbx_shard_float_rows": (_sz, [_GP]),
     "rbx_shard_route_workspace_size": (_sz, [_GP, _i32]),

@@ -89,6 +89,13 @@ __device__ __forceinline__ void seg_of_tile(const SegPack& S, unsigned tile, int
   *count = (end - f < static_cast<unsigned>(kSortTile)) ? end - f : static_cast<unsigned>(kSortTile);
 }
 
+// digit `shift / RB` of a key inside its segment; masked lookups (key == sentinel) are all ones: last in every pass
+template <int RB>
+__device__ __forceinline__ unsigned seg_digit(unsigned key, unsigned sentinel, unsigned row0, int shift) {
+  const unsigned local = (key == sentinel) ? 0xFFFFFFFFu : key - row0;
+  return (local >> shift) & ((1u << RB) - 1u);
+}
+
 struct NumField {            // numeric features: grad[d] += sum_b x_b * dY[b, off+d]
   const void* ids;
   float* grad;
@@ -131,10 +138,17 @@ struct BwdPlan {
 
 // Build the plan for `fields` (definition in rbx_embed_bwd.hip).  `extra_dim` floats are
 // reserved behind every chunk summary (the fused FM backward keeps sum(g) there).
+// `lookups_of` (optional, one entry per field): the number of lookups field i owns when that is not B * seq_len -- the
+// ragged bags of rbx_embed_csr.hip, whose descriptors arrive as seq_len = 1 fields over their flat index arrays.
 int make_plan(const rbx_field_t* fields, int n, int64_t B, const float* dout, int64_t stride_b, BwdPlan* p,
-              int extra_dim = 0);
+              int extra_dim = 0, const unsigned long long* lookups_of = nullptr);
 // build_keys + LSD radix passes; sorted pairs end up in key/val buffer (passes & 1).
 int run_sort(const BwdPlan& p, char* ws, int* d_status, hipStream_t s);
+// The radix passes alone, for a caller that has built the pairs (and the tile histograms build_keys_kernel leaves) itself.
+int run_sort_passes(const BwdPlan& p, char* ws, hipStream_t s);
+// GenericPolicy's segmented reduce over the sorted pairs of `p` (the body of rbx_embed_bwd_indexed's categorical part).
+int generic_reduce(const BwdPlan& p, const float* dout, int64_t stride_b, const int32_t* index, const float* row_scale,
+                   int64_t B, int accumulate, char* ws, hipStream_t s);
 
 // ---- segment reduce ------------------------------------------------------------------
 template <int G, int NV, bool VEC>

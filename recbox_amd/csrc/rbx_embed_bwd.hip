@@ -37,7 +37,7 @@ static bool sort_chained_on() {
 }
 
 int make_plan(const rbx_field_t* fields, int n, int64_t B, const float* dout, int64_t stride_b, BwdPlan* p,
-              int extra_dim) {
+              int extra_dim, const unsigned long long* lookups_of) {
   if (fields == nullptr || n <= 0 || n > RBX_MAX_FIELDS) return fail(RBX_ERR_INVALID, "bad field array");
   FieldPack tmp;
   int rc = pack_fields(fields, n, B, true, &tmp);
@@ -66,7 +66,8 @@ int make_plan(const rbx_field_t* fields, int n, int64_t B, const float* dout, in
       nf.dtype = static_cast<unsigned char>(f.ids_dtype);
       continue;
     }
-    const unsigned long long n_lk = static_cast<unsigned long long>(B) * f.seq_len;
+    // (ragged bags, rbx_embed_csr.hip: field i owns lookups_of[i] lookups, whatever the batch is)
+    const unsigned long long n_lk = lookups_of != nullptr ? lookups_of[i] : static_cast<unsigned long long>(B) * f.seq_len;
     if (n_lk > kLocalMask) return fail(RBX_ERR_UNSUPPORTED, "field %d: B*seq_len=%llu exceeds 2^26 per call", i, n_lk);
     int hit = -1;
     for (int s = 0; s < n_seen; ++s)
@@ -214,12 +215,7 @@ int make_plan(const rbx_field_t* fields, int n, int64_t B, const float* dout, in
 }
 
 // ---- build_keys ----------------------------------------------------------------
-// digit `shift / RB` of a key inside its segment; masked lookups (key == sentinel) are all ones: last in every pass
-template <int RB>
-__device__ __forceinline__ unsigned seg_digit(unsigned key, unsigned sentinel, unsigned row0, int shift) {
-  const unsigned local = (key == sentinel) ? 0xFFFFFFFFu : key - row0;
-  return (local >> shift) & ((1u << RB) - 1u);
-}
+// (seg_digit: rbx_bwd_common.h)
 
 template <int RB>
 __global__ __launch_bounds__(kSortThreads) void build_keys_kernel(const KeyPack P, const int n_cat, const SegPack S,
@@ -809,19 +805,16 @@ extern "C" size_t rbx_embed_bwd_workspace_size(const rbx_field_t* fields, int32_
 }
 
 namespace rbx {
+// the radix passes over the pairs a key-building kernel left (build_keys_kernel here, csr_keys_kernel in rbx_embed_csr.hip)
 template <int RB>
-static int run_sort_rb(const BwdPlan& p, char* ws, int* d_status, hipStream_t s) {
+static int run_passes_rb(const BwdPlan& p, char* ws, hipStream_t s) {
   constexpr int R = 1 << RB;
   unsigned* keys[2] = {reinterpret_cast<unsigned*>(ws + p.off_keys[0]), reinterpret_cast<unsigned*>(ws + p.off_keys[1])};
   unsigned* vals[2] = {reinterpret_cast<unsigned*>(ws + p.off_vals[0]), reinterpret_cast<unsigned*>(ws + p.off_vals[1])};
   unsigned* hist = reinterpret_cast<unsigned*>(ws + p.off_hist);
   unsigned* ssum = reinterpret_cast<unsigned*>(ws + p.off_ssum);
   const bool chained = p.chained && RB == 8;
-  hipLaunchKernelGGL(build_keys_kernel<RB>, dim3(p.n_tiles), dim3(kSortThreads), 0, s, p.keys, p.n_cat, p.segs, p.total_rows,
-                     keys[0], vals[0], keys[1], vals[1], d_status, reinterpret_cast<unsigned*>(ws + p.off_fin), hist,
-                     chained ? p.passes : 0, p.n_tiles);
-  int rc = check_launch("build_keys_kernel");
-  if (rc != RBX_OK) return rc;
+  int rc = RBX_OK;
   int cur = 0;
   for (int pass = 0; pass < p.passes; ++pass) {
     if (chained) {
@@ -851,6 +844,27 @@ static int run_sort_rb(const BwdPlan& p, char* ws, int* d_status, hipStream_t s)
   return RBX_OK;
 }
 
+int run_sort_passes(const BwdPlan& p, char* ws, hipStream_t s) {
+  switch (p.radix_bits) {
+    case 8: return run_passes_rb<8>(p, ws, s);
+    case 10: return run_passes_rb<10>(p, ws, s);
+    default: return run_passes_rb<11>(p, ws, s);
+  }
+}
+
+template <int RB>
+static int run_sort_rb(const BwdPlan& p, char* ws, int* d_status, hipStream_t s) {
+  unsigned* keys[2] = {reinterpret_cast<unsigned*>(ws + p.off_keys[0]), reinterpret_cast<unsigned*>(ws + p.off_keys[1])};
+  unsigned* vals[2] = {reinterpret_cast<unsigned*>(ws + p.off_vals[0]), reinterpret_cast<unsigned*>(ws + p.off_vals[1])};
+  const bool chained = p.chained && RB == 8;
+  hipLaunchKernelGGL(build_keys_kernel<RB>, dim3(p.n_tiles), dim3(kSortThreads), 0, s, p.keys, p.n_cat, p.segs, p.total_rows,
+                     keys[0], vals[0], keys[1], vals[1], d_status, reinterpret_cast<unsigned*>(ws + p.off_fin),
+                     reinterpret_cast<unsigned*>(ws + p.off_hist), chained ? p.passes : 0, p.n_tiles);
+  const int rc = check_launch("build_keys_kernel");
+  if (rc != RBX_OK) return rc;
+  return run_passes_rb<RB>(p, ws, s);
+}
+
 int run_sort(const BwdPlan& p, char* ws, int* d_status, hipStream_t s) {
   if (p.n_lookups == 0) return RBX_OK;
   switch (p.radix_bits) {
@@ -858,6 +872,22 @@ int run_sort(const BwdPlan& p, char* ws, int* d_status, hipStream_t s) {
     case 10: return run_sort_rb<10>(p, ws, d_status, s);
     default: return run_sort_rb<11>(p, ws, d_status, s);
   }
+}
+
+int generic_reduce(const BwdPlan& p, const float* dout, int64_t stride_b, const int32_t* index, const float* row_scale,
+                   int64_t B, int accumulate, char* ws, hipStream_t s) {
+  for (int i = 0; i < p.n_cat; ++i) {
+    const unsigned char pool = p.red.f[i].pool;
+    if ((pool == RBX_POOL_MEAN_VALUE || pool == RBX_POOL_MEAN_ID) && row_scale == nullptr)
+      return fail(RBX_ERR_INVALID, "mean pooling backward needs d_row_scale from the forward");
+  }
+  const int cur = p.passes & 1;
+  const unsigned* keys = reinterpret_cast<const unsigned*>(ws + p.off_keys[cur]);
+  const unsigned* vals = reinterpret_cast<const unsigned*>(ws + p.off_vals[cur]);
+  const GenericPolicy::Args args = {dout, static_cast<long long>(stride_b), row_scale, static_cast<long long>(B), accumulate,
+                                    index};
+  return p.vec ? dispatch_reduce<GenericPolicy, true>(p, args, keys, vals, ws, s)
+               : dispatch_reduce<GenericPolicy, false>(p, args, keys, vals, ws, s);
 }
 }  // namespace rbx
 
@@ -906,18 +936,7 @@ extern "C" int rbx_embed_bwd_indexed(const rbx_field_t* fields, int32_t n_fields
   char* ws = static_cast<char*>(d_workspace);
   hipStream_t s = as_stream(stream);
   if (p.n_lookups > 0) {
-    for (int i = 0; i < p.n_cat; ++i) {
-      const unsigned char pool = p.red.f[i].pool;
-      if ((pool == RBX_POOL_MEAN_VALUE || pool == RBX_POOL_MEAN_ID) && d_row_scale == nullptr)
-        return fail(RBX_ERR_INVALID, "mean pooling backward needs d_row_scale from the forward");
-    }
-    const int cur = p.passes & 1;
-    const unsigned* keys = reinterpret_cast<const unsigned*>(ws + p.off_keys[cur]);
-    const unsigned* vals = reinterpret_cast<const unsigned*>(ws + p.off_vals[cur]);
-    const GenericPolicy::Args args = {d_dout, static_cast<long long>(out_stride_b), d_row_scale,
-                                      static_cast<long long>(batch), accumulate, d_dout_index};
-    rc = p.vec ? dispatch_reduce<GenericPolicy, true>(p, args, keys, vals, ws, s)
-               : dispatch_reduce<GenericPolicy, false>(p, args, keys, vals, ws, s);
+    rc = generic_reduce(p, d_dout, out_stride_b, d_dout_index, d_row_scale, batch, accumulate, ws, s);
     if (rc != RBX_OK) return rc;
   }
   if (p.n_num > 0 && d_dout_index != nullptr) return fail(RBX_ERR_UNSUPPORTED, "embed_bwd_indexed: numeric features are not indexed");

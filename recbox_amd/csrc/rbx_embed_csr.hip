@@ -1,0 +1,526 @@
+// rbx_embed_csr.hip -- K1-K3 for ragged bags: the multi-hot gather-pool over `indices` / `offsets` (CSR) and its
+// deterministic backward (gfx950).
+//
+// Reference behaviour kept (paths relative to the reference's recbox/ package): the pooling variants of
+// core/pytorch/layers/sequence.py:4-20 and third_party/rechub/basic/layers.py:176-230 over the embedding of a history,
+// each exactly as rbx_pool_t defines it for padded ids (rbx_embed_fwd.hip, embed_seq_kernel) -- a bag is the history
+// without its padded tail, the layout of torch.nn.EmbeddingBag.
+//
+// Forward.  embed_seq_kernel's mapping with the id range taken from two offset loads per lane group instead of
+// (b * stride, seq_len): a lane group per bag, a wave task = (bag descriptor, block of 64 / SG bags) with the descriptor
+// in SGPRs, a coalesced sweep of the bag's ids in chunks of 4 * SG, classify + compact into the group's LDS list, U = 4
+// rows in flight, R sub-groups and a closing butterfly for narrow rows.  Chunk size, list order, U and R are the padded
+// kernel's, so a bag is summed in the order the padded call sums the same live ids: the outputs are bit-equal.  The
+// wave-uniform loop bound is the longest bag of the wave.
+// Backward.  The positions of a descriptor's index array are its lookups.  csr_bag_map_kernel (a lane group per bag,
+// coalesced stores) leaves an int32 lookup -> bag map; csr_keys_kernel builds, per sort tile, (global row, bag) pairs
+// for the in-range, unmasked, non-padding ids inside a bag -- every other position gets the sentinel key the sort puts
+// last and the reduce drops -- and the tile's digit counts; the radix passes, segment_reduce_kernel and the fix-ups are
+// rbx_embed_bwd.hip's, with GenericPolicy over seq_len = 1 fields: the pair's value names the BAG, so the upstream
+// gradient row and the mean scale (row_scale[slot * B + bag]) are read per bag and never expanded per lookup.
+// User-supplied offsets are clamped to 0 <= begin <= end <= nnz before any index is read (status bit 1 when that
+// changed anything): no input makes a kernel read outside indices[0, nnz).
+#include "rbx_bwd_common.h"
+#include "rbx_rowfrag.h"
+
+namespace rbx {
+
+constexpr int kStatusBadId = 1;        // an id outside [0, vocab): as rbx_embed_fwd
+constexpr int kStatusBadOffsets = 2;   // a bag's range had to be clamped
+
+struct BagK {               // 64 B; RBX_MAX_BAGS of them (2 KiB) travel in the kernarg segment
+  const void* indices;
+  const void* offsets;
+  const float* table;
+  long long idx_stride;
+  int nnz;
+  int vocab;
+  int mask_id;              // kNoId when unset
+  int pad_id;
+  int out_off;
+  short dim;
+  unsigned char idx_dtype, off_dtype, pool, slot;
+  short reserved;
+  float eps;
+};
+static_assert(sizeof(BagK) == 64, "BagK must stay 64 bytes");
+struct BagPack { BagK f[RBX_MAX_BAGS]; };
+struct BagLookups { unsigned lk_off[RBX_MAX_BAGS]; };   // first lookup of every bag descriptor in the call's sort
+
+// [begin, end) of bag b, clamped into [0, nnz]; *bad: the clamp changed something
+__device__ __forceinline__ void bag_range(const BagK& fd, long long b, int* begin, int* end, bool* bad) {
+  long long o0, o1;
+  if (fd.off_dtype == RBX_I64) {
+    o0 = static_cast<const long long*>(fd.offsets)[b];
+    o1 = static_cast<const long long*>(fd.offsets)[b + 1];
+  } else {
+    o0 = static_cast<const int*>(fd.offsets)[b];
+    o1 = static_cast<const int*>(fd.offsets)[b + 1];
+  }
+  const long long n = fd.nnz;
+  const long long lo = o0 < 0 ? 0 : (o0 > n ? n : o0);
+  const long long hi = o1 < lo ? lo : (o1 > n ? n : o1);
+  *begin = static_cast<int>(lo);
+  *end = static_cast<int>(hi);
+  *bad = (lo != o0) || (hi != o1);
+}
+
+// ---- forward -------------------------------------------------------------------------------------------------------
+// The constants below are embed_seq_kernel's (RBX_SEQ_WAVES, RBX_SEQ_U, RBX_SEQ_IPL16, RBX_SEQ_SG16 / _SG32): the
+// bit-equality of the two paths rests on equal chunks, batches and sub-group counts.
+constexpr int kCsrWaves = 4;
+constexpr int kCsrU = 4;               // rows in flight per lane
+constexpr int kCsrIpl = 4;             // ids per lane per chunk
+
+template <int G, int R, int NV, bool VEC>
+__global__ __launch_bounds__(256, kCsrWaves) void embed_csr_kernel(const BagPack P, const int F, const long long B,
+                                                                   float* __restrict__ out, const long long stride_b,
+                                                                   float* __restrict__ row_scale,
+                                                                   int* __restrict__ status) {
+  constexpr int W = G / R;                                // lanes that hold one row
+  using Frag = RowFrag<W, NV, VEC>;
+  constexpr int U = kCsrU;
+  constexpr int IPL = kCsrIpl;
+  constexpr int C = G * IPL;                              // lookups per chunk
+  constexpr int GPB = 256 / G;
+  __shared__ int s_id[GPB][C];
+  const int lane_w = threadIdx.x % W;
+  const int sub = (threadIdx.x % G) / W;
+  const int lane_g = threadIdx.x % G;
+  const int gidx = threadIdx.x / G;
+  const int gshift = (threadIdx.x & 63) & ~(G - 1);       // first lane of the group inside its wave
+  const unsigned long long gmask = (G == 64) ? ~0ull : ((1ull << G) - 1ull);
+  const unsigned long long below = (1ull << lane_g) - 1ull;
+  volatile int* my_id = s_id[gidx];
+  constexpr int GPW = 64 / G;
+  const long long tasks_per_bag = (B + GPW - 1) / GPW;
+  const long long ntasks = tasks_per_bag * F;
+  const long long nwaves = static_cast<long long>(gridDim.x) * 4;
+  for (long long t = static_cast<long long>(blockIdx.x) * 4 + threadIdx.x / 64; t < ntasks; t += nwaves) {
+    const int f = __builtin_amdgcn_readfirstlane(static_cast<int>(t / tasks_per_bag));
+    const long long b = (t - f * tasks_per_bag) * GPW + (threadIdx.x & 63) / G;
+    const bool alive = b < B;
+    const BagK& fd = P.f[f];
+    const int pool = fd.pool, dim = fd.dim, dt = fd.idx_dtype;
+    const bool id_pool = (pool == RBX_POOL_MEAN_ID || pool == RBX_POOL_SUM_ID);
+    int begin = 0, end = 0;
+    if (alive) {
+      bool bad;
+      bag_range(fd, b, &begin, &end, &bad);
+      if (bad && lane_g == 0 && status != nullptr) atomicOr(status, kStatusBadOffsets);
+    }
+    const int L = end - begin;
+    float* dst = out + b * stride_b + fd.out_off;
+    Frag acc;
+    acc.zero();
+    float count = 0.f;
+    int Lmax = L;                                         // wave-uniform number of chunks: the longest bag of the wave
+#pragma unroll
+    for (int o = 32; o >= G && o > 0; o >>= 1) {
+      const int other = __shfl_xor(Lmax, o, 64);
+      Lmax = other > Lmax ? other : Lmax;
+    }
+    for (int c0 = 0; c0 < Lmax; c0 += C) {
+      long long raw[IPL];
+#pragma unroll
+      for (int i = 0; i < IPL; ++i) {                     // (1a) one coalesced sweep of id loads; l < L <=> inside [begin, end)
+        const int l = c0 + i * G + lane_g;
+        raw[i] = (l < L) ? load_raw(fd.indices, (static_cast<long long>(begin) + l) * fd.idx_stride, dt) : 0;
+      }
+      int nvalid = 0;
+#pragma unroll
+      for (int i = 0; i < IPL; ++i) {                     // (1b) classify + compact
+        const int l = c0 + i * G + lane_g;
+        const long long id = decode_id(raw[i], dt);
+        const bool live = l < L;
+        const bool in_range = id >= 0 && id < fd.vocab;
+        if (live && !in_range && status != nullptr) atomicOr(status, kStatusBadId);
+        const bool use = live && in_range && !(id_pool && id == fd.mask_id);
+        const unsigned long long m = (__ballot(use) >> gshift) & gmask;
+        if (use) my_id[nvalid + __popcll(m & below)] = static_cast<int>(id);
+        nvalid += __popcll(m);
+      }
+      __builtin_amdgcn_wave_barrier();
+      int nmax = nvalid;                                   // wave-uniform batch count
+#pragma unroll
+      for (int o = 32; o >= G && o > 0; o >>= 1) {
+        const int other = __shfl_xor(nmax, o, 64);
+        nmax = other > nmax ? other : nmax;
+      }
+      for (int k0 = 0; k0 < nmax; k0 += U * R) {          // (2) dense row batches
+        int idu[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int k = k0 + u * R + sub;
+          idu[u] = (k < nvalid) ? my_id[k] : -1;
+        }
+        Frag r[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          r[u].zero();
+          if (idu[u] >= 0) r[u].load(fd.table + static_cast<long long>(idu[u]) * dim, dim, lane_w);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          acc.add(r[u]);
+          if (pool == RBX_POOL_MEAN_VALUE) {
+            const float sm = group_sum<W>(r[u].hsum());   // value mask: row sum != 0
+            count += (sm != 0.f) ? 1.f : 0.f;
+          } else if (pool == RBX_POOL_MEAN_ID) {
+            count += (idu[u] >= 0) ? 1.f : 0.f;
+          }
+        }
+      }
+      __builtin_amdgcn_wave_barrier();
+    }
+#pragma unroll
+    for (int o = W; o < G; o <<= 1) {                     // every lane joins the butterfly
+      acc.xor_add(o);
+      count += __shfl_xor(count, o, 64);
+    }
+    if (!alive || sub != 0) continue;
+    if (pool == RBX_POOL_MEAN_VALUE || pool == RBX_POOL_MEAN_ID) {
+      const float inv = 1.0f / (count + fd.eps);          // an empty bag: 0 * (1 / eps) = 0
+      acc.scale(inv);
+      if (row_scale != nullptr && lane_w == 0) row_scale[static_cast<long long>(fd.slot) * B + b] = inv;
+    }
+    acc.store(dst, dim, lane_w);
+  }
+}
+
+template <int G, int NV, bool VEC>
+static int launch_csr(const BagPack& pack, int F, int64_t B, float* out, int64_t stride_b, float* row_scale, int* status,
+                      hipStream_t s) {
+  constexpr int SG = (G <= 8) ? 16 : ((G == 16) ? 32 : 64);    // lanes per bag: launch_fwd's rule for sequences
+  long long blocks = ((B + 64 / SG - 1) / (64 / SG) * F + 3) / 4;   // 4 wave tasks per workgroup
+  const long long cap = static_cast<long long>(kCUs) * 64;
+  if (blocks > cap) blocks = cap;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL((embed_csr_kernel<SG, SG / G, NV, VEC>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, pack, F,
+                     static_cast<long long>(B), out, static_cast<long long>(stride_b), row_scale, status);
+  return check_launch("embed_csr_kernel");
+}
+
+template <bool VEC>
+static int dispatch_csr(int units, const BagPack& pack, int F, int64_t B, float* out, int64_t stride_b, float* row_scale,
+                        int* status, hipStream_t s) {
+  switch (pow2_ceil(units)) {
+    case 1: return launch_csr<1, 1, VEC>(pack, F, B, out, stride_b, row_scale, status, s);
+    case 2: return launch_csr<2, 1, VEC>(pack, F, B, out, stride_b, row_scale, status, s);
+    case 4: return launch_csr<4, 1, VEC>(pack, F, B, out, stride_b, row_scale, status, s);
+    case 8: return launch_csr<8, 1, VEC>(pack, F, B, out, stride_b, row_scale, status, s);
+    case 16: return launch_csr<16, 1, VEC>(pack, F, B, out, stride_b, row_scale, status, s);
+    case 32: return launch_csr<32, 1, VEC>(pack, F, B, out, stride_b, row_scale, status, s);
+    case 64: return launch_csr<64, 1, VEC>(pack, F, B, out, stride_b, row_scale, status, s);
+    case 128: return launch_csr<64, 2, VEC>(pack, F, B, out, stride_b, row_scale, status, s);
+    case 256: return launch_csr<64, 4, VEC>(pack, F, B, out, stride_b, row_scale, status, s);
+    default: return fail(RBX_ERR_UNSUPPORTED, "embedding dim too large for one lane group (units=%d)", units);
+  }
+}
+
+static int compact(int64_t v) { return (v == RBX_NO_ID || v < INT_MIN || v > INT_MAX) ? kNoId : static_cast<int>(v); }
+
+// Validate the public descriptors; convert descriptor i into out[i] (slot = i).
+static int pack_bags(const rbx_bag_t* bags, int n, int64_t batch, BagK* out) {
+  if (bags == nullptr) return fail(RBX_ERR_INVALID, "bags is NULL");
+  if (n <= 0 || n > RBX_MAX_BAGS) return fail(RBX_ERR_INVALID, "n_bags=%d not in [1,%d]", n, RBX_MAX_BAGS);
+  if (batch < 0) return fail(RBX_ERR_INVALID, "negative batch");
+  if (batch > static_cast<int64_t>(kLocalMask)) return fail(RBX_ERR_UNSUPPORTED, "batch=%lld exceeds 2^26 bags per call", (long long)batch);
+  unsigned long long total = 0;
+  for (int i = 0; i < n; ++i) {
+    const rbx_bag_t& g = bags[i];
+    if (g.pool == RBX_POOL_NONE || g.pool == RBX_POOL_CONCAT)
+      return fail(RBX_ERR_UNSUPPORTED, "bag %d: pool mode %d keeps one slot per id; ragged bags are pooled (sum / mean)", i, g.pool);
+    if (g.pool < RBX_POOL_NONE || g.pool > RBX_POOL_CONCAT) return fail(RBX_ERR_INVALID, "bag %d: bad pool mode %d", i, g.pool);
+    if (g.dim <= 0 || g.dim > 1024) return fail(RBX_ERR_UNSUPPORTED, "bag %d: dim=%d not in [1,1024]", i, g.dim);
+    if (g.nnz < 0 || g.nnz > static_cast<int64_t>(kLocalMask))
+      return fail(RBX_ERR_UNSUPPORTED, "bag %d: nnz=%lld not in [0, 2^26]", i, (long long)g.nnz);
+    if (g.nnz > 0 && g.indices == nullptr) return fail(RBX_ERR_INVALID, "bag %d: indices is NULL", i);
+    if (g.offsets == nullptr) return fail(RBX_ERR_INVALID, "bag %d: offsets is NULL", i);
+    if (g.table == nullptr) return fail(RBX_ERR_INVALID, "bag %d: table is NULL", i);
+    if (g.indices_dtype < RBX_I32 || g.indices_dtype > RBX_F64) return fail(RBX_ERR_INVALID, "bag %d: bad indices_dtype", i);
+    if (g.offsets_dtype != RBX_I32 && g.offsets_dtype != RBX_I64)
+      return fail(RBX_ERR_INVALID, "bag %d: offsets must be int32 or int64", i);
+    if (g.vocab <= 0 || g.vocab > INT_MAX) return fail(RBX_ERR_INVALID, "bag %d: vocab=%lld", i, (long long)g.vocab);
+    if (g.out_off < 0 || g.out_off > INT_MAX) return fail(RBX_ERR_INVALID, "bag %d: out_off", i);
+    total += static_cast<unsigned long long>(g.nnz);
+    BagK& k = out[i];
+    k.indices = g.indices;
+    k.offsets = g.offsets;
+    k.table = g.table;
+    k.idx_stride = g.indices_stride;
+    k.nnz = static_cast<int>(g.nnz);
+    k.vocab = static_cast<int>(g.vocab);
+    k.mask_id = compact(g.mask_id);
+    k.pad_id = compact(g.padding_idx);
+    k.out_off = static_cast<int>(g.out_off);
+    k.dim = static_cast<short>(g.dim);
+    k.idx_dtype = static_cast<unsigned char>(g.indices_dtype);
+    k.off_dtype = static_cast<unsigned char>(g.offsets_dtype);
+    k.pool = static_cast<unsigned char>(g.pool);
+    k.slot = static_cast<unsigned char>(i);
+    k.reserved = 0;
+    k.eps = g.eps;
+  }
+  if (total >= (1ull << 31)) return fail(RBX_ERR_UNSUPPORTED, "nnz of the call = %llu, limit 2^31", total);
+  return RBX_OK;
+}
+
+static bool bag_vec_ok(const rbx_bag_t& g, const float* out, int64_t stride_b) {
+  if (g.dim % 4 != 0 || g.out_off % 4 != 0 || stride_b % 4 != 0) return false;
+  if ((reinterpret_cast<uintptr_t>(g.table) & 15) != 0) return false;
+  if ((reinterpret_cast<uintptr_t>(out) & 15) != 0) return false;
+  return true;
+}
+
+// ---- backward: lookup -> bag map, (row, bag) pairs -----------------------------------------------------------------
+// grid (x, bag descriptors of the plan); 16 lane groups of 16 lanes per workgroup, a group per bag: the bags of a
+// descriptor are consecutive ranges of its index array, so neighbouring groups store neighbouring runs.
+__global__ __launch_bounds__(256) void csr_bag_map_kernel(const BagPack P, const BagLookups LK, const long long B,
+                                                          int* __restrict__ map, int* __restrict__ status) {
+  const BagK& fd = P.f[blockIdx.y];
+  int* __restrict__ my = map + LK.lk_off[blockIdx.y];
+  const int lane = threadIdx.x & 15;
+  for (long long b = static_cast<long long>(blockIdx.x) * 16 + (threadIdx.x >> 4); b < B;
+       b += static_cast<long long>(gridDim.x) * 16) {
+    int begin, end;
+    bool bad;
+    bag_range(fd, b, &begin, &end, &bad);
+    if (bad && lane == 0 && status != nullptr) atomicOr(status, kStatusBadOffsets);
+    for (int j = begin + lane; j < end; j += 16) my[j] = static_cast<int>(b);
+  }
+}
+
+// build_keys_kernel's tile structure (one workgroup per sort tile, the tile's digit counts out of the same pass) over
+// lookups that are positions of index arrays: position j of descriptor `lo` is a pair iff the map names a bag for it.
+template <int RB>
+__global__ __launch_bounds__(kSortThreads) void csr_keys_kernel(const KeyPack P, const int n_cat, const SegPack S,
+                                                                const unsigned sentinel, const int* __restrict__ map,
+                                                                unsigned* __restrict__ keys0, unsigned* __restrict__ vals0,
+                                                                unsigned* __restrict__ keys1, unsigned* __restrict__ vals1,
+                                                                int* __restrict__ status, unsigned* __restrict__ fin,
+                                                                unsigned* __restrict__ hist, const int chain_passes,
+                                                                const unsigned n_tiles) {
+  constexpr int R = 1 << RB;
+  constexpr int kCP = (RB == 8) ? kChainPasses : 1;      // (the chained sort runs 8-bit digits only)
+  if (blockIdx.x == 0 && threadIdx.x == 0) {             // fix-up work-list length and arrival counter (rbx_segreduce.h)
+    fin[0] = 0;
+    fin[1] = 0;
+    fin[2] = 0;
+  }
+  __shared__ KeyField sf[RBX_MAX_FIELDS];
+  {
+    const int words = n_cat * static_cast<int>(sizeof(KeyField) / 4);
+    const int* src = reinterpret_cast<const int*>(&P);
+    int* dst = reinterpret_cast<int*>(sf);
+    for (int i = threadIdx.x; i < words; i += blockDim.x) dst[i] = src[i];
+  }
+  __shared__ unsigned cnt[kCP][R];
+  for (int d = threadIdx.x; d < kCP * R; d += kSortThreads) (&cnt[0][0])[d] = 0;
+  __syncthreads();
+  int seg;
+  unsigned tile0, tile_n;
+  seg_of_tile(S, blockIdx.x, &seg, &tile0, &tile_n);
+  const unsigned row0 = S.row0[seg];
+  const int fp = S.first_pass[seg];
+  unsigned* __restrict__ keys = (fp & 1) ? keys1 : keys0;
+  unsigned* __restrict__ vals = (fp & 1) ? vals1 : vals0;
+#pragma unroll
+  for (int it = 0; it < kSortItems; ++it) {
+    const unsigned off = it * kSortThreads + threadIdx.x;
+    if (off >= tile_n) break;
+    const unsigned j = tile0 + off;
+    int lo = 0, hi = n_cat - 1;                          // last descriptor with lk_off <= j
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (sf[mid].lk_off <= j) lo = mid; else hi = mid - 1;
+    }
+    const KeyField& fd = sf[lo];
+    const unsigned local = j - fd.lk_off;                // position inside the descriptor's index array (< nnz)
+    const int bag = map[j];
+    unsigned key = sentinel;
+    if (bag >= 0) {
+      const long long id = load_id(fd.ids, static_cast<long long>(local) * fd.stride_b, fd.dtype);
+      if (id < 0 || id >= fd.vocab) {
+        if (status != nullptr) atomicOr(status, kStatusBadId);
+      } else {
+        const bool id_pool = fd.pool == RBX_POOL_MEAN_ID || fd.pool == RBX_POOL_SUM_ID;
+        if (id != fd.pad_id && !(id_pool && id == fd.mask_id)) key = fd.row_base + static_cast<unsigned>(id);
+      }
+    }
+    keys[j] = key;
+    vals[j] = (static_cast<unsigned>(lo) << kLocalBits) | static_cast<unsigned>(bag < 0 ? 0 : bag);
+    if (chain_passes > 0) {
+#pragma unroll
+      for (int k = 0; k < kCP; ++k)
+        if (fp + k < chain_passes) atomicAdd(&cnt[k][seg_digit<RB>(key, sentinel, row0, k * RB)], 1u);
+    } else if (fp == 0) {
+      atomicAdd(&cnt[0][seg_digit<RB>(key, sentinel, row0, 0)], 1u);
+    }
+  }
+  if (chain_passes > 0) {
+    // [pass][tile][digit] counts, [pass][tile] flags: the layout radix_scatter_kernel<RB, true> reads (rbx_embed_bwd.hip)
+    __syncthreads();
+    const size_t plane = static_cast<size_t>(n_tiles) * R;
+    unsigned* flags = hist + 2 * plane * chain_passes;
+    for (int k = 0; fp + k < chain_passes; ++k) {
+      unsigned* h = hist + plane * (fp + k) + static_cast<size_t>(blockIdx.x) * R;
+      for (int d = threadIdx.x; d < R; d += kSortThreads) h[d] = cnt[k < kCP ? k : 0][d];
+      if (threadIdx.x == 0) flags[static_cast<size_t>(fp + k) * n_tiles + blockIdx.x] = 0u;
+    }
+    return;
+  }
+  if (fp != 0) return;
+  __syncthreads();
+  // histogram layout: segment, then digit, then tile of the segment (what the flat exclusive scan expects)
+  const unsigned t_in = blockIdx.x - S.tile0[seg], nt = S.tile0[seg + 1] - S.tile0[seg];
+  unsigned* h = hist + static_cast<size_t>(S.tile0[seg]) * R + t_in;
+  for (int d = threadIdx.x; d < R; d += kSortThreads) h[static_cast<size_t>(d) * nt] = cnt[0][d];
+}
+
+// ---- host plan: the bags as seq_len = 1 fields of make_plan, descriptor i owning nnz_i lookups ----------------------
+struct CsrPlan {
+  BwdPlan p;
+  BagPack bags;             // the descriptors that take part (grad != NULL), in the plan's order
+  BagLookups lk;
+  size_t off_map = 0, bytes = 0;
+};
+
+static int csr_plan(const rbx_bag_t* bags, int n, int64_t batch, const float* dout, int64_t stride_b, CsrPlan* c) {
+  BagK all[RBX_MAX_BAGS];
+  int rc = pack_bags(bags, n, batch, all);
+  if (rc != RBX_OK) return rc;
+  rbx_field_t fields[RBX_MAX_BAGS];
+  unsigned long long lookups_of[RBX_MAX_BAGS];
+  for (int i = 0; i < n; ++i) {
+    const rbx_bag_t& g = bags[i];
+    rbx_field_t& f = fields[i];
+    f.ids = g.indices != nullptr ? g.indices : static_cast<const void*>(g.table);   // (nnz == 0: never read)
+    f.table = g.table;
+    f.grad = g.grad;
+    f.ids_stride_b = g.indices_stride;
+    f.ids_stride_l = 0;
+    f.vocab = g.vocab;
+    f.padding_idx = g.padding_idx;
+    f.mask_id = g.mask_id;
+    f.out_off = g.out_off;
+    f.dim = g.dim;
+    f.seq_len = 1;
+    f.ids_dtype = g.indices_dtype;
+    f.kind = RBX_FIELD_CATEGORICAL;
+    f.pool = g.pool;
+    f.eps = g.eps;
+    f.table_stride = 0;
+    lookups_of[i] = static_cast<unsigned long long>(g.nnz);
+  }
+  rc = make_plan(fields, n, batch, dout, stride_b, &c->p, 0, lookups_of);
+  if (rc != RBX_OK) return rc;
+  int k = 0;
+  for (int i = 0; i < n; ++i) {
+    if (bags[i].grad == nullptr) continue;                // frozen: make_plan skipped it
+    c->bags.f[k] = all[i];
+    c->lk.lk_off[k] = c->p.keys.f[k].lk_off;
+    ++k;
+  }
+  c->off_map = c->p.bytes;
+  c->bytes = c->p.bytes + (static_cast<size_t>(c->p.n_lookups) * 4 + 255) / 256 * 256;
+  return RBX_OK;
+}
+
+template <int RB>
+static int launch_csr_keys(const CsrPlan& c, char* ws, int* status, hipStream_t s) {
+  const BwdPlan& p = c.p;
+  const bool chained = p.chained && RB == 8;
+  hipLaunchKernelGGL(csr_keys_kernel<RB>, dim3(p.n_tiles), dim3(kSortThreads), 0, s, p.keys, p.n_cat, p.segs, p.total_rows,
+                     reinterpret_cast<const int*>(ws + c.off_map), reinterpret_cast<unsigned*>(ws + p.off_keys[0]),
+                     reinterpret_cast<unsigned*>(ws + p.off_vals[0]), reinterpret_cast<unsigned*>(ws + p.off_keys[1]),
+                     reinterpret_cast<unsigned*>(ws + p.off_vals[1]), status, reinterpret_cast<unsigned*>(ws + p.off_fin),
+                     reinterpret_cast<unsigned*>(ws + p.off_hist), chained ? p.passes : 0, p.n_tiles);
+  return check_launch("csr_keys_kernel");
+}
+
+}  // namespace rbx
+
+extern "C" int rbx_embed_csr_fwd(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, float* d_out, int64_t out_stride_b,
+                                 float* d_row_scale, int32_t* d_status, void* stream) {
+  using namespace rbx;
+  BagK all[RBX_MAX_BAGS];
+  int rc = pack_bags(bags, n_bags, batch, all);
+  if (rc != RBX_OK) return rc;
+  if (batch == 0) return RBX_OK;
+  if (d_out == nullptr) return fail(RBX_ERR_INVALID, "d_out is NULL");
+  // (float4 | scalar) launches; every dim is checked before the first launch, so a refused call writes nothing
+  BagPack pack[2];
+  int cnt[2] = {0, 0}, units[2] = {1, 1};
+  for (int i = 0; i < n_bags; ++i) {
+    const bool vec = bag_vec_ok(bags[i], d_out, out_stride_b);
+    const int k = vec ? 0 : 1;
+    pack[k].f[cnt[k]++] = all[i];
+    const int u = vec ? bags[i].dim / 4 : bags[i].dim;
+    if (u > units[k]) units[k] = u;
+  }
+  for (int k = 0; k < 2; ++k)
+    if (cnt[k] > 0 && pow2_ceil(units[k]) > 256)
+      return fail(RBX_ERR_UNSUPPORTED, "embedding dim too large for one lane group (%s units=%d)", k == 0 ? "float4" : "scalar",
+                  units[k]);
+  for (int k = 0; k < 2; ++k) {
+    if (cnt[k] == 0) continue;
+    rc = (k == 0) ? dispatch_csr<true>(units[k], pack[k], cnt[k], batch, d_out, out_stride_b, d_row_scale, d_status,
+                                       as_stream(stream))
+                  : dispatch_csr<false>(units[k], pack[k], cnt[k], batch, d_out, out_stride_b, d_row_scale, d_status,
+                                        as_stream(stream));
+    if (rc != RBX_OK) return rc;
+  }
+  return RBX_OK;
+}
+
+extern "C" size_t rbx_embed_csr_bwd_workspace_size(const rbx_bag_t* bags, int32_t n_bags, int64_t batch) {
+  rbx::CsrPlan c;
+  if (rbx::csr_plan(bags, n_bags, batch, nullptr, 0, &c) != RBX_OK) return 0;
+  return c.bytes;
+}
+
+extern "C" int rbx_embed_csr_sort(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, void* d_workspace,
+                                  size_t workspace_bytes, int32_t* d_status, void* stream) {
+  using namespace rbx;
+  CsrPlan c;
+  int rc = csr_plan(bags, n_bags, batch, nullptr, 0, &c);
+  if (rc != RBX_OK) return rc;
+  const BwdPlan& p = c.p;
+  if (p.n_lookups == 0 || batch == 0) return RBX_OK;
+  if (d_workspace == nullptr || workspace_bytes < c.bytes)
+    return fail(RBX_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, c.bytes);
+  char* ws = static_cast<char*>(d_workspace);
+  hipStream_t s = as_stream(stream);
+  int* map = reinterpret_cast<int*>(ws + c.off_map);
+  if (hipMemsetAsync(map, 0xFF, static_cast<size_t>(p.n_lookups) * 4, s) != hipSuccess)   // -1: outside every bag
+    return fail(RBX_ERR_LAUNCH, "clearing the lookup -> bag map failed");
+  long long bx = (batch + 15) / 16;
+  if (bx > kCUs * 8) bx = kCUs * 8;
+  hipLaunchKernelGGL(csr_bag_map_kernel, dim3(static_cast<unsigned>(bx), p.n_cat), dim3(256), 0, s, c.bags, c.lk,
+                     static_cast<long long>(batch), map, d_status);
+  rc = check_launch("csr_bag_map_kernel");
+  if (rc != RBX_OK) return rc;
+  switch (p.radix_bits) {
+    case 8: rc = launch_csr_keys<8>(c, ws, d_status, s); break;
+    case 10: rc = launch_csr_keys<10>(c, ws, d_status, s); break;
+    default: rc = launch_csr_keys<11>(c, ws, d_status, s); break;
+  }
+  if (rc != RBX_OK) return rc;
+  return run_sort_passes(p, ws, s);
+}
+
+extern "C" int rbx_embed_csr_bwd(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, const float* d_dout,
+                                 int64_t out_stride_b, const float* d_row_scale, int32_t accumulate, void* d_workspace,
+                                 size_t workspace_bytes, void* stream) {
+  using namespace rbx;
+  if (d_dout == nullptr) return fail(RBX_ERR_INVALID, "d_dout is NULL");
+  CsrPlan c;
+  int rc = csr_plan(bags, n_bags, batch, d_dout, out_stride_b, &c);
+  if (rc != RBX_OK) return rc;
+  if (c.p.n_lookups == 0 || batch == 0) return RBX_OK;
+  if (d_workspace == nullptr || workspace_bytes < c.bytes)
+    return fail(RBX_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, c.bytes);
+  return generic_reduce(c.p, d_dout, out_stride_b, nullptr, d_row_scale, batch, accumulate, static_cast<char*>(d_workspace),
+                        as_stream(stream));
+}

@@ -17,80 +17,9 @@
 // The simple (one id per sample) path is unrolled x4 so that four dependent
 // id->row chains per lane are in flight; sequence pools unroll over L instead.
 // HBM-bound: no LDS tiling of rows (each row is used once), no MFMA.
-#include "rbx_internal.h"
+#include "rbx_rowfrag.h"
 
 namespace rbx {
-
-template <bool VEC>
-struct Acc;
-template <>
-struct Acc<true> {
-  float4 v;
-  __device__ __forceinline__ void zero() { v = make_float4(0.f, 0.f, 0.f, 0.f); }
-  __device__ __forceinline__ void add(const Acc& o) { v.x += o.v.x; v.y += o.v.y; v.z += o.v.z; v.w += o.v.w; }
-  __device__ __forceinline__ void scale(float s) { v.x *= s; v.y *= s; v.z *= s; v.w *= s; }
-  __device__ __forceinline__ float hsum() const { return (v.x + v.y) + (v.z + v.w); }
-  __device__ __forceinline__ void load(const float* p) { v = *reinterpret_cast<const float4*>(p); }
-  __device__ __forceinline__ void store(float* p) const { *reinterpret_cast<float4*>(p) = v; }
-  __device__ __forceinline__ void xor_add(int o) {
-    v.x += __shfl_xor(v.x, o, 64); v.y += __shfl_xor(v.y, o, 64);
-    v.z += __shfl_xor(v.z, o, 64); v.w += __shfl_xor(v.w, o, 64);
-  }
-};
-template <>
-struct Acc<false> {
-  float v;
-  __device__ __forceinline__ void zero() { v = 0.f; }
-  __device__ __forceinline__ void add(const Acc& o) { v += o.v; }
-  __device__ __forceinline__ void scale(float s) { v *= s; }
-  __device__ __forceinline__ float hsum() const { return v; }
-  __device__ __forceinline__ void load(const float* p) { v = *p; }
-  __device__ __forceinline__ void store(float* p) const { *p = v; }
-  __device__ __forceinline__ void xor_add(int o) { v += __shfl_xor(v, o, 64); }
-};
-
-// One lane's share of a row: NV units, unit u covers elements [(lane_g + u*G)*W, +W).
-template <int G, int NV, bool VEC>
-struct RowFrag {
-  static constexpr int W = VEC ? 4 : 1;
-  Acc<VEC> a[NV];
-  __device__ __forceinline__ void zero() {
-#pragma unroll
-    for (int u = 0; u < NV; ++u) a[u].zero();
-  }
-  __device__ __forceinline__ void load(const float* row, int dim, int lane_g) {
-#pragma unroll
-    for (int u = 0; u < NV; ++u) {
-      const int e = (lane_g + u * G) * W;
-      if (e < dim) a[u].load(row + e); else a[u].zero();
-    }
-  }
-  __device__ __forceinline__ void store(float* row, int dim, int lane_g) const {
-#pragma unroll
-    for (int u = 0; u < NV; ++u) {
-      const int e = (lane_g + u * G) * W;
-      if (e < dim) a[u].store(row + e);
-    }
-  }
-  __device__ __forceinline__ void add(const RowFrag& o) {
-#pragma unroll
-    for (int u = 0; u < NV; ++u) a[u].add(o.a[u]);
-  }
-  __device__ __forceinline__ void scale(float s) {
-#pragma unroll
-    for (int u = 0; u < NV; ++u) a[u].scale(s);
-  }
-  __device__ __forceinline__ float hsum() const {
-    float s = 0.f;
-#pragma unroll
-    for (int u = 0; u < NV; ++u) s += a[u].hsum();
-    return s;
-  }
-  __device__ __forceinline__ void xor_add(int o) {
-#pragma unroll
-    for (int u = 0; u < NV; ++u) a[u].xor_add(o);
-  }
-};
 
 template <int G, int NV, bool VEC>
 __global__ __launch_bounds__(256) void embed_fwd_kernel(const FieldPack P, const int F, const long long B,

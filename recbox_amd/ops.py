@@ -617,6 +617,204 @@ def embed_lookup(plan, inputs, params, pad_rows=False):
     return _EmbedLookup.apply(plan, len(inputs), train, pad_rows, *inputs, *params)
 
 
+# ---- ragged bags (CSR): indices / offsets gather-pool -----------------------------------------------------------------
+class Bags(object):
+    """One ragged multi-hot feature of a batch, the layout of ``nn.EmbeddingBag``: ``indices`` flat ``[nnz]`` ids (int32 /
+    int64 / float32 / float64, any element stride), ``offsets`` ``[B + 1]`` (int32 / int64, contiguous); bag ``b`` is
+    ``indices[offsets[b]:offsets[b + 1]]``.  ``offsets[0] > 0``, ``offsets[B] < nnz`` and empty bags are fine.  Nothing
+    here reads device memory: ``nnz`` and ``B`` come from the shapes."""
+    __slots__ = ("indices", "offsets")
+
+    def __init__(self, indices, offsets):
+        _require_cuda(indices, "bag indices")
+        _require_cuda(offsets, "bag offsets")
+        if indices.device != offsets.device:
+            raise ValueError("bag indices and offsets live on different devices (%s, %s)" % (indices.device, offsets.device))
+        if indices.dim() != 1 or offsets.dim() != 1:
+            raise ValueError("bag indices and offsets must be 1-D, got %s and %s" % (tuple(indices.shape), tuple(offsets.shape)))
+        if offsets.numel() < 1:
+            raise ValueError("bag offsets need B + 1 >= 1 entries")
+        if indices.dtype not in _DTYPE_CODE:
+            raise TypeError("bag indices must be int32 / int64 / float32 / float64, got %s" % indices.dtype)
+        if offsets.dtype not in (torch.int32, torch.int64):
+            raise TypeError("bag offsets must be int32 or int64, got %s" % offsets.dtype)
+        if offsets.numel() > 1 and offsets.stride(0) != 1:
+            raise ValueError("bag offsets must be contiguous")
+        self.indices, self.offsets = indices, offsets
+
+    @property
+    def batch(self):
+        return self.offsets.numel() - 1
+
+    @property
+    def nnz(self):
+        return self.indices.numel()
+
+
+def bags_from_padded(ids, mask_id):
+    """``[B, L]`` padded ids -> ``Bags`` of the ids that differ from ``mask_id``, in order (int64 offsets).  ATen glue with a
+    host sync (the number of live ids decides a shape): a converter for tests and data preparation, not meant for a captured
+    step -- a loader that holds ragged histories builds ``Bags`` directly."""
+    _require_cuda(ids, "ids")
+    if ids.dim() != 2:
+        raise ValueError("expected padded ids of shape [B, L], got %s" % (tuple(ids.shape),))
+    keep = ids != mask_id
+    offsets = torch.zeros(ids.shape[0] + 1, dtype=torch.int64, device=ids.device)
+    torch.cumsum(keep.sum(1), 0, out=offsets[1:])
+    return Bags(ids[keep], offsets)
+
+
+class BagSpec(object):
+    """Static description of one ragged feature inside a BagPlan: ``pool`` one of POOL_SUM / POOL_SUM_ID / POOL_MEAN_ID /
+    POOL_MEAN_VALUE, ``param`` the index of its table in the call's parameter list."""
+    __slots__ = ("name", "dim", "out_off", "param", "pool", "vocab", "padding_idx", "mask_id", "eps")
+
+    def __init__(self, name, dim, out_off, param, pool, vocab, padding_idx=None, mask_id=None, eps=0.0):
+        self.name, self.dim, self.out_off, self.param, self.pool = name, dim, out_off, param, pool
+        self.vocab, self.padding_idx, self.mask_id, self.eps = vocab, padding_idx, mask_id, eps
+
+
+class BagPlan(object):
+    """A reusable, pre-filled rbx_bag_t array; only pointers, strides, dtypes and nnz are rewritten per call."""
+
+    def __init__(self, specs, width=None):
+        if not 0 < len(specs) <= _lib.RBX_MAX_BAGS:
+            raise NotImplementedError("a single call supports 1..%d ragged features, got %d" % (_lib.RBX_MAX_BAGS, len(specs)))
+        self.specs = list(specs)
+        self.n = len(self.specs)
+        self.width = int(width) if width is not None else max(s.out_off + s.dim for s in self.specs)
+        self.arr = (_lib.rbx_bag_t * self.n)()
+        self.needs_row_scale = any(s.pool in (POOL_MEAN_VALUE, POOL_MEAN_ID) for s in self.specs)
+        for f, s in zip(self.arr, self.specs):
+            if s.pool in (POOL_NONE, POOL_CONCAT):
+                raise NotImplementedError("feature '%s': ragged bags are pooled (sum / mean); pool mode %d keeps one slot "
+                                          "per id" % (s.name, s.pool))
+            f.pool, f.dim, f.vocab, f.out_off, f.eps = s.pool, s.dim, s.vocab, s.out_off, s.eps
+            f.padding_idx = RBX_NO_ID if s.padding_idx is None else int(s.padding_idx)
+            f.mask_id = RBX_NO_ID if s.mask_id is None else int(s.mask_id)
+
+    def bind_inputs(self, bags):
+        """Point the descriptors at this batch; returns (B, kept tensors: indices and offsets of every feature in turn)."""
+        keep, B = [], None
+        for f, s, g in zip(self.arr, self.specs, bags):
+            if not isinstance(g, Bags):
+                raise TypeError("feature '%s': expected ops.Bags, got %s" % (s.name, type(g).__name__))
+            if B is None:
+                B = g.batch
+            elif g.batch != B:
+                raise ValueError("feature '%s': batch %d != %d" % (s.name, g.batch, B))
+            self._bind_one(f, g.indices, g.offsets)
+            keep += [g.indices, g.offsets]
+        return B, keep
+
+    @staticmethod
+    def _bind_one(f, indices, offsets):
+        f.indices, f.offsets = indices.data_ptr(), offsets.data_ptr()
+        f.nnz = indices.numel()
+        f.indices_stride = indices.stride(0) if indices.numel() > 1 else 1
+        f.indices_dtype, f.offsets_dtype = _DTYPE_CODE[indices.dtype], _DTYPE_CODE[offsets.dtype]
+
+    def bind_tensors(self, tensors):
+        for k, f in enumerate(self.arr):
+            self._bind_one(f, tensors[2 * k], tensors[2 * k + 1])
+
+    def bind_params(self, params, grads=None):
+        for f, s in zip(self.arr, self.specs):
+            f.table = params[s.param].data_ptr()
+            g = grads[s.param] if grads is not None else None
+            f.grad = g.data_ptr() if g is not None else None
+
+
+class _EmbedBags(torch.autograd.Function):
+    """out[B, width] = pooled gather over ragged bags (rbx_embed_csr_fwd); backward = the sorted segmented scatter-add
+    over the lookups that exist (rbx_embed_csr_sort in the forward, on the current stream; rbx_embed_csr_bwd).  Plain
+    autograd semantics: freshly zeroed dense gradients (or, for a table another lookup of the pass has already written,
+    that node's gradient: config.share_table_grads).  No host sync beyond the id check config.check_ids asks for."""
+
+    @staticmethod
+    def forward(ctx, plan, n_bags, train, *tensors):
+        inputs, params = tensors[:2 * n_bags], tensors[2 * n_bags:]
+        for p in params:
+            _require_cuda(p, "embedding parameter")
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise RuntimeError("recbox_amd: embedding parameters must be contiguous fp32")
+        plan.bind_tensors(inputs)
+        plan.bind_params(params)
+        B = inputs[1].numel() - 1
+        dev = params[0].device
+        out = torch.empty((B, plan.width), dtype=torch.float32, device=dev)
+        row_scale = torch.empty((plan.n, B), dtype=torch.float32, device=dev) if plan.needs_row_scale else None
+        status = _status_word(dev)
+        check(_timed(("embed_csr_fwd", plan.n, plan.width, B),
+                     lambda: lib.rbx_embed_csr_fwd(plan.arr, plan.n, B, _ptr(out), out.stride(0) if B > 1 else plan.width,
+                                                   _ptr(row_scale), _ptr(status), _stream())))
+        _check_status(status)
+        ctx.plan, ctx.inputs, ctx.row_scale, ctx.B, ctx.params = plan, inputs, row_scale, B, params
+        ctx.ws, ctx.ws_bytes = None, 0
+        if train:
+            _note_readers(ctx, params)
+        if B > 0 and train:
+            ctx.ws, ctx.ws_bytes = _EmbedBags._sort(plan, params, [p if p.requires_grad else None for p in params], B, dev)
+        return out
+
+    @staticmethod
+    def _sort(plan, params, grads, B, dev):
+        plan.bind_params(params, grads)
+        ws_bytes = lib.rbx_embed_csr_bwd_workspace_size(plan.arr, plan.n, B)
+        if ws_bytes == 0:
+            msg = _lib.last_error()
+            if "too large" in msg or "exceeds" in msg or "limit" in msg:
+                raise NotImplementedError(msg)
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+        check(lib.rbx_embed_csr_sort(plan.arr, plan.n, B, _ptr(ws), ws_bytes, None, _stream()))
+        return ws, ws_bytes
+
+    @staticmethod
+    def backward(ctx, dout):
+        plan, params, B = ctx.plan, ctx.params, ctx.B
+        if dout.stride(1) != 1 or dout.dtype != torch.float32:
+            dout = dout.contiguous().float()
+        first = 3 + len(ctx.inputs)
+        want = [ctx.needs_input_grad[first + i] for i in range(len(params))]
+        head = (None, None, None) + (None,) * len(ctx.inputs)
+        adopted = _adopt_grads(ctx, params, want) if B > 0 else None
+        grads = adopted if adopted is not None else _flat_zero_grads(params, want, dout.device)
+        if B == 0:
+            return head + tuple(grads)
+        plan.bind_tensors(ctx.inputs)
+        if ctx.ws is not None and [p.requires_grad for p in params] == list(want):
+            plan.bind_params(params, grads)
+            ws, ws_bytes = ctx.ws, ctx.ws_bytes
+        else:                                          # e.g. torch.autograd.grad on a subset: sort now
+            ws, ws_bytes = _EmbedBags._sort(plan, params, grads, B, dout.device)
+        check(lib.rbx_embed_csr_bwd(plan.arr, plan.n, B, _ptr(dout), dout.stride(0) if B > 1 else plan.width,
+                                    _ptr(ctx.row_scale), 1 if adopted is not None else 0, _ptr(ws), ws_bytes, _stream()))
+        if adopted is not None:                        # the rows went into the gradient another node of this pass returned
+            for p, w in zip(params, want):
+                if w:
+                    touched.pop(id(p), None)           # (its touched-row record names that node's rows only)
+            return head + (None,) * len(params)
+        _publish_grads(ctx, params, grads)
+        return head + tuple(grads)
+
+
+def embed_bags(plan_or_specs, bags, params):
+    """Pooled lookup over ragged bags: ``plan_or_specs`` a ``BagPlan`` or a list of ``BagSpec``, ``bags`` one ``Bags`` per
+    spec, ``params`` the distinct tables the specs' ``param`` indices name.  Returns ``[B, width]``; slot ``i`` holds the pool
+    of feature ``i`` (an empty bag: zeros).  An ``nn.EmbeddingBag(mode="sum" / "mean")`` call maps onto one spec with
+    POOL_SUM / POOL_MEAN_ID (``mask_id=None``, ``eps=0`` divides by the bag length)."""
+    plan = plan_or_specs if isinstance(plan_or_specs, BagPlan) else BagPlan(plan_or_specs)
+    params = list(params)
+    for g in bags:
+        if not isinstance(g, Bags):
+            raise TypeError("embed_bags takes ops.Bags, got %s" % type(g).__name__)
+    for p in params:
+        _require_cuda(p, "embedding parameter")
+    _, tensors = plan.bind_inputs(bags)
+    train = torch.is_grad_enabled() and any(p.requires_grad for p in params)   # grad mode is off inside forward()
+    return _EmbedBags.apply(plan, plan.n, train, *tensors, *params)
+
+
 class _Interaction(torch.autograd.Function):
     """InnerProductInteraction on [B, F, D]; the [F, D] block of a sample may be the leading columns of a wider row
     (batch stride > F * D): it is read in place.  The gradient is a tight [B, F, D] tensor of its own."""

@@ -65,7 +65,79 @@ class EmbeddingLayer(nn.Module):
                 raise ValueError("unknown feature class %s" % type(fea).__name__)
         return sparse, dense_l
 
+    def _forward_with_bags(self, x, features, squeeze_dim):
+        """Some sequence features arrive as ``ops.Bags`` (ragged indices / offsets) instead of ``[B, L]`` ids: they go
+        through ``ops.embed_bags`` (rbx_embed_csr_*), every other feature through the usual plan (rbx_embed_fwd), and the
+        slots are joined by columns in feature order.  Tables shared between the two calls get one gradient: the second
+        backward node of the pass adds its rows into the first one's (ops.config.share_table_grads)."""
+        key = ("bags", tuple(id(f) for f in features), squeeze_dim,
+               tuple(("bags" if isinstance(x[f.name], ops.Bags) else x[f.name].shape[1]) if isinstance(f, SequenceFeature)
+                     else 0 for f in features))
+        cached = self._plans.get(key)
+        if cached is None:
+            order, padded, specs, tables, off = [], [], [], [], 0
+            for fea in features:
+                if isinstance(fea, DenseFeature):
+                    continue
+                if not isinstance(x[fea.name], ops.Bags):
+                    sparse, _ = self._lookups(x, [fea])
+                    order.append(("padded", len(padded)))
+                    padded += sparse
+                    continue
+                if not isinstance(fea, SequenceFeature):
+                    raise ValueError("feature '%s': only a SequenceFeature takes ops.Bags" % fea.name)
+                if fea.pooling == "concat":
+                    raise ValueError("feature '%s': pooling='concat' keeps one slot per position; ragged ops.Bags need "
+                                     "pooling 'sum' or 'mean'" % fea.name)
+                if fea.pooling not in ("sum", "mean"):
+                    raise ValueError("Sequence pooling method supports only pooling in %s, got %s." %
+                                     (["sum", "mean"], fea.pooling))
+                table = self.embed_dict[fea.name if fea.shared_with is None else fea.shared_with]
+                if not any(t is table for t in tables):
+                    tables.append(table)
+                param = [i for i, t in enumerate(tables) if t is table][0]
+                mask_id = fea.padding_idx if fea.padding_idx is not None else -1   # InputMask: id != -1
+                specs.append(ops.BagSpec(fea.name, table.embedding_dim, off, param,
+                                         POOL_SUM_ID if fea.pooling == "sum" else POOL_MEAN_ID, table.num_embeddings,
+                                         padding_idx=table.padding_idx, mask_id=mask_id, eps=1e-16))
+                order.append(("bags", len(specs) - 1))
+                off += table.embedding_dim
+            n_sparse = len(order)
+            if squeeze_dim:
+                for fea in features:
+                    if isinstance(fea, DenseFeature):
+                        order.append(("padded", len(padded)))
+                        padded.append(host.Lookup(fea.name, FIELD_DENSE, None, 1))
+            cached = (host.Plan(padded) if padded else None, ops.BagPlan(specs), tables, order, n_sparse)
+            self._plans[key] = cached
+        plan, bag_plan, tables, order, n_sparse = cached
+        out_p = plan.run([x[lk.name] for lk in plan.lookups]) if plan is not None else None
+        out_b = ops.embed_bags(bag_plan, [x[s.name] for s in bag_plan.specs], [t.weight for t in tables])
+        pieces, dims, concat = [], set(), False
+        for kind, i in order:
+            if kind == "padded":
+                sp = plan.specs[i]
+                pieces.append(out_p[:, sp.out_off:sp.out_off + sp.width])
+                concat = concat or sp.pool == POOL_CONCAT
+                if sp.kind != FIELD_DENSE:
+                    dims.add(sp.dim)
+            else:
+                sp = bag_plan.specs[i]
+                pieces.append(out_b[:, sp.out_off:sp.out_off + sp.dim])
+                dims.add(sp.dim)
+        out = torch.cat(pieces, 1)
+        if squeeze_dim:
+            return out
+        if len(dims) != 1:
+            raise RuntimeError("Sizes of tensors must match except in dimension 1 (embed_dim differs across features)")
+        if concat:
+            raise RuntimeError("Tensors must have same number of dimensions (mixing pooling='concat' "
+                               "with pooled/sparse features)")
+        return out.view(out.shape[0], n_sparse, dims.pop())
+
     def forward(self, x, features, squeeze_dim=False):
+        if any(isinstance(x[f.name], ops.Bags) for f in features):
+            return self._forward_with_bags(x, features, squeeze_dim)
         key = (tuple(id(f) for f in features), squeeze_dim,
                tuple(x[f.name].shape[1] if isinstance(f, SequenceFeature) else 0 for f in features))
         cached = self._plans.get(key)
