@@ -163,7 +163,30 @@ int rbx_embed_bwd_indexed(const rbx_field_t* fields, int32_t n_fields, int64_t b
  *                       that share a `table` pointer are merged, accumulate as there, no float atomics: bit-identical
  *                       from run to run.  The mean scale is read per bag (d_row_scale[i * batch + b]).
  * Limits: n_bags <= RBX_MAX_BAGS; nnz of one descriptor and batch at most 2^26; the nnz of a call together below 2^31
- * (positions outside every bag take part in the sort as dropped pairs); dims as rbx_embed_fwd (1..256 lane-group units). */
+ * (positions outside every bag take part in the sort as dropped pairs); dims as rbx_embed_fwd (1..256 lane-group units).
+ *
+ * Per-sample weights (torch's per_sample_weights; RBX_POOL_SUM and RBX_POOL_SUM_ID only).  rbx_bag_t is unchanged: the
+ * weights travel as a host array of n_bags device pointers, entry i an fp32 [bags[i].nnz] contiguous array whose element
+ * j belongs to indices[j], or NULL = descriptor i is unweighted (a call may mix both; d_weights itself may be NULL).
+ *   out[b, slot]  = sum over the usable j of bag b of  w[j] * table[id_j]
+ *   dTable[id_j] += w[j] * dY[b, slot]                (the padding_idx row stays zero)
+ *   dw[j]         = < dY[b, slot], table[id_j] >      for usable j inside a bag, 0 for every other position
+ * "usable" as above: inside a clamped bag, id in [0, vocab), not the mask_id of RBX_POOL_SUM_ID.  The padding_idx id is
+ * read and weighted in the forward like any row and gets the dw of that read; only its table-gradient row is zero.  A
+ * non-NULL weight array (or weight gradient) on a mean-pool descriptor returns RBX_ERR_UNSUPPORTED with nothing launched.
+ * No weight is read outside w[0, nnz): weights are read at the positions ids are read at.  No float atomics; with every
+ * weight exactly 1.0f outputs and table gradients are bit-equal to the unweighted calls on the same bags.
+ *   rbx_embed_csr_fwd_weighted   rbx_embed_csr_fwd with the factor; unweighted descriptors run as they do there (a mean
+ *                                pool among them is computed, but its row scale is not kept: no d_row_scale here).
+ *   rbx_embed_csr_sort_weighted  rbx_embed_csr_sort with pairs whose value is the lookup's position inside its index
+ *                                array instead of the bag; same workspace size (rbx_embed_csr_bwd_workspace_size).  The
+ *                                workspace it leaves is for rbx_embed_csr_bwd_weighted only, and that call takes no other.
+ *   rbx_embed_csr_bwd_weighted   rbx_embed_csr_bwd over that sort: bag = map[position], factor = w[position].  Mean-pool
+ *                                descriptors with a gradient are refused by both (RBX_ERR_UNSUPPORTED): their backward
+ *                                needs the row scale of the unweighted path.
+ *   rbx_embed_csr_weight_grad    d_dweights: host array of n_bags device pointers, entry i an fp32 [nnz] array or NULL (no
+ *                                gradient wanted).  Every element of a non-NULL array is defined after the call (cleared
+ *                                by a memset node, then the usable positions are written).  Needs no sort. */
 #define RBX_MAX_BAGS 32
 typedef struct rbx_bag {
   const void*  indices;          /* [nnz] ids */
@@ -191,6 +214,15 @@ int rbx_embed_csr_sort(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, voi
 int rbx_embed_csr_bwd(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, const float* d_dout, int64_t out_stride_b,
                       const float* d_row_scale, int32_t accumulate, void* d_workspace, size_t workspace_bytes,
                       void* stream);
+int rbx_embed_csr_fwd_weighted(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, const float* const* d_weights,
+                               float* d_out, int64_t out_stride_b, int32_t* d_status, void* stream);
+int rbx_embed_csr_sort_weighted(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, void* d_workspace,
+                                size_t workspace_bytes, int32_t* d_status, void* stream);
+int rbx_embed_csr_bwd_weighted(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, const float* const* d_weights,
+                               const float* d_dout, int64_t out_stride_b, int32_t accumulate, void* d_workspace,
+                               size_t workspace_bytes, void* stream);
+int rbx_embed_csr_weight_grad(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, const float* d_dout,
+                              int64_t out_stride_b, float* const* d_dweights, int32_t* d_status, void* stream);
 
 /* ---- K4: InnerProductInteraction / rechub FM on a materialised [B,F,D] tensor ---
  * ranking/pytorch/layers/interactions/inner_product.py:40-56,

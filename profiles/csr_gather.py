@@ -6,7 +6,8 @@ gradient, so that no zero fill is inside the bracket) with HIP events on torch's
     python profiles/csr_gather.py [--repeats 20] [--rows 10000000] [--out FILE]
 
 Cases: (1) every bag 50 ids = the padded L = 50 call's lookups; (2) lengths uniform in 1 .. 50 against the same ids padded
-to 50; (3) skewed lengths (bags of 1 .. 9 ids, 0.1 % of them 1 000 .. 5 000) against the same nnz spread evenly."""
+to 50; (3) skewed lengths (bags of 1 .. 9 ids, 0.1 % of them 1 000 .. 5 000) against the same nnz spread evenly; (4) case 2's bags
+under SUM_ID with and without per-sample weights, and the weight-gradient call."""
 import argparse
 import os
 import statistics
@@ -88,6 +89,47 @@ class Ragged(object):
                                          self.ws.data_ptr(), self.nbytes, ops._stream()))
 
 
+class Weighted(object):
+    """Case 2's bags under SUM_ID, without and with per-sample weights (the ``_weighted`` entry points and the
+    weight-gradient kernel)."""
+
+    def __init__(self, emb, grad, bags, weighted):
+        self.plan = ops.BagPlan([ops.BagSpec("h", D, 0, 0, _lib.POOL_SUM_ID, emb.num_embeddings, mask_id=0)])
+        self.w, self.g, self.weighted = emb.weight, grad, weighted
+        self.out = torch.empty(B, D, device="cuda")
+        self.plan.bind_inputs([bags])
+        self.plan.bind_params([self.w], [self.g])
+        self.nbytes = lib.rbx_embed_csr_bwd_workspace_size(self.plan.arr, 1, B)
+        self.ws = torch.empty(self.nbytes, dtype=torch.uint8, device="cuda")
+        self.lookups = bags.nnz
+        self.weights = torch.rand(bags.nnz, device="cuda") * 2 - 1
+        self.dw = torch.empty(bags.nnz, device="cuda")
+        self.warr, self.dwarr = ops._ptr_array([self.weights]), ops._ptr_array([self.dw])
+
+    def fwd(self):
+        if self.weighted:
+            _lib.check(lib.rbx_embed_csr_fwd_weighted(self.plan.arr, 1, B, self.warr, self.out.data_ptr(), D, None, ops._stream()))
+        else:
+            _lib.check(lib.rbx_embed_csr_fwd(self.plan.arr, 1, B, self.out.data_ptr(), D, None, None, ops._stream()))
+
+    def sort(self):
+        if self.weighted:
+            _lib.check(lib.rbx_embed_csr_sort_weighted(self.plan.arr, 1, B, self.ws.data_ptr(), self.nbytes, None, ops._stream()))
+        else:
+            _lib.check(lib.rbx_embed_csr_sort(self.plan.arr, 1, B, self.ws.data_ptr(), self.nbytes, None, ops._stream()))
+
+    def bwd(self):
+        if self.weighted:
+            _lib.check(lib.rbx_embed_csr_bwd_weighted(self.plan.arr, 1, B, self.warr, self.out.data_ptr(), D, 1, self.ws.data_ptr(),
+                                                      self.nbytes, ops._stream()))
+        else:
+            _lib.check(lib.rbx_embed_csr_bwd(self.plan.arr, 1, B, self.out.data_ptr(), D, None, 1, self.ws.data_ptr(), self.nbytes,
+                                             ops._stream()))
+
+    def wgrad(self):
+        _lib.check(lib.rbx_embed_csr_weight_grad(self.plan.arr, 1, B, self.out.data_ptr(), D, self.dwarr, None, ops._stream()))
+
+
 def bags_of(lengths, rows, gen):
     offsets = torch.zeros(B + 1, dtype=torch.int64)
     torch.cumsum(lengths, 0, out=offsets[1:])
@@ -148,6 +190,11 @@ def main():
     even[:total - int(even.sum())] += 1
     case("3. skewed lengths (1 .. 9, 0.1 pct of the bags 1 000 .. 5 000) against the same nnz spread evenly", ["even", "skewed"],
          [Ragged(emb, grad, bags_of(even, a.rows, gen)), Ragged(emb, grad, bags_of(skew, a.rows, gen))], a.repeats, lines)
+    plain, scored = Weighted(emb, grad, uni, False), Weighted(emb, grad, uni, True)
+    case("4. case 2's bags under SUM_ID, unweighted against random per-sample weights", ["unweighted", "weighted"],
+         [plain, scored], a.repeats, lines)
+    g = bracket([scored.wgrad], a.repeats)[0]
+    lines.append("\nweight gradient (memset of dw + csr_weight_grad_kernel): %.1f us (%.1f .. %.1f)" % g)
     text = "\n".join(lines) + "\n"
     print(text)
     if a.out:

@@ -111,6 +111,10 @@ SIGNATURES = {
     "rbx_embed_csr_bwd_workspace_size": (_sz, [_BP, _i32, _i64]),
     "rbx_embed_csr_sort": (ctypes.c_int, [_BP, _i32, _i64, _P, _sz, _P, _P]),
     "rbx_embed_csr_bwd": (ctypes.c_int, [_BP, _i32, _i64, _P, _i64, _P, _i32, _P, _sz, _P]),
+    "rbx_embed_csr_fwd_weighted": (ctypes.c_int, [_BP, _i32, _i64, _PP, _P, _i64, _P, _P]),
+    "rbx_embed_csr_sort_weighted": (ctypes.c_int, [_BP, _i32, _i64, _P, _sz, _P, _P]),
+    "rbx_embed_csr_bwd_weighted": (ctypes.c_int, [_BP, _i32, _i64, _PP, _P, _i64, _i32, _P, _sz, _P]),
+    "rbx_embed_csr_weight_grad": (ctypes.c_int, [_BP, _i32, _i64, _P, _i64, _PP, _P, _P]),
     "rbx_shard_int_chunk": (_sz, [_GP]),
     "rbx_shard_float_rows": (_sz, [_GP]),
     "rbx_shard_route_workspace_size": (_sz, [_GP, _i32]),

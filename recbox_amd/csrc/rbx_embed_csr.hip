@@ -20,8 +20,16 @@
 // gradient row and the mean scale (row_scale[slot * B + bag]) are read per bag and never expanded per lookup.
 // User-supplied offsets are clamped to 0 <= begin <= end <= nnz before any index is read (status bit 1 when that
 // changed anything): no input makes a kernel read outside indices[0, nnz).
+// Per-sample weights (sum pools only; torch's per_sample_weights).  A parallel array of fp32 [nnz] weight pointers, one
+// per descriptor, NULL = unweighted.  Forward: embed_csr_weighted_kernel, embed_csr_kernel's sweep with the weight loaded
+// beside the id and compacted beside it (a second LDS list), acc += w * row in the same chunk / list / U / R order: all
+// weights 1.0f give the unweighted call's bits.  Table gradient: the weighted sort's pair value names the lookup's POSITION
+// inside its descriptor's index array (csr_keys_kernel<RB, true>), and WeightedBagPolicy reads bag = map[position] and
+// w[position] -- rbx_embed_bwd_indexed's indirection plus one factor; passes, reduce and fix-ups unchanged.  Weight
+// gradient: csr_weight_grad_kernel, a lane group per bag, dw[j] = <dY[bag, slot], table[id_j]>; no sort involved.
 #include "rbx_bwd_common.h"
 #include "rbx_rowfrag.h"
+#include "rbx_segreduce.h"
 
 namespace rbx {
 
@@ -46,6 +54,8 @@ struct BagK {               // 64 B; RBX_MAX_BAGS of them (2 KiB) travel in the 
 static_assert(sizeof(BagK) == 64, "BagK must stay 64 bytes");
 struct BagPack { BagK f[RBX_MAX_BAGS]; };
 struct BagLookups { unsigned lk_off[RBX_MAX_BAGS]; };   // first lookup of every bag descriptor in the call's sort
+struct BagWeights { const float* w[RBX_MAX_BAGS]; };    // per-sample weights of the descriptors of a BagPack, same order
+struct BagWeightGrads { float* dw[RBX_MAX_BAGS]; };     // ... and where their gradients go
 
 // [begin, end) of bag b, clamped into [0, nnz]; *bad: the clamp changed something
 __device__ __forceinline__ void bag_range(const BagK& fd, long long b, int* begin, int* end, bool* bad) {
@@ -188,6 +198,249 @@ __global__ __launch_bounds__(256, kCsrWaves) void embed_csr_kernel(const BagPack
   }
 }
 
+// ---- forward with per-sample weights --------------------------------------------------------------------------------
+// embed_csr_kernel for the sum pools with one factor per lookup: the weight is loaded in the id's coalesced sweep,
+// compacted beside the id (a second list: 8 KB of LDS per workgroup) and multiplied into the row before the add.  Chunk
+// size, list order, U and R are embed_csr_kernel's, and x * 1.0f is x: all-ones weights give that kernel's bits.
+template <int G, int R, int NV, bool VEC>
+__global__ __launch_bounds__(256, kCsrWaves) void embed_csr_weighted_kernel(const BagPack P, const BagWeights WP, const int F,
+                                                                            const long long B, float* __restrict__ out,
+                                                                            const long long stride_b,
+                                                                            int* __restrict__ status) {
+  constexpr int W = G / R;                                // lanes that hold one row
+  using Frag = RowFrag<W, NV, VEC>;
+  constexpr int U = kCsrU;
+  constexpr int IPL = kCsrIpl;
+  constexpr int C = G * IPL;                              // lookups per chunk
+  constexpr int GPB = 256 / G;
+  __shared__ int s_id[GPB][C];
+  __shared__ float s_w[GPB][C];
+  const int lane_w = threadIdx.x % W;
+  const int sub = (threadIdx.x % G) / W;
+  const int lane_g = threadIdx.x % G;
+  const int gidx = threadIdx.x / G;
+  const int gshift = (threadIdx.x & 63) & ~(G - 1);       // first lane of the group inside its wave
+  const unsigned long long gmask = (G == 64) ? ~0ull : ((1ull << G) - 1ull);
+  const unsigned long long below = (1ull << lane_g) - 1ull;
+  volatile int* my_id = s_id[gidx];
+  volatile float* my_w = s_w[gidx];
+  constexpr int GPW = 64 / G;
+  const long long tasks_per_bag = (B + GPW - 1) / GPW;
+  const long long ntasks = tasks_per_bag * F;
+  const long long nwaves = static_cast<long long>(gridDim.x) * 4;
+  for (long long t = static_cast<long long>(blockIdx.x) * 4 + threadIdx.x / 64; t < ntasks; t += nwaves) {
+    const int f = __builtin_amdgcn_readfirstlane(static_cast<int>(t / tasks_per_bag));
+    const long long b = (t - f * tasks_per_bag) * GPW + (threadIdx.x & 63) / G;
+    const bool alive = b < B;
+    const BagK& fd = P.f[f];
+    const float* __restrict__ wsrc = WP.w[f];
+    const int dim = fd.dim, dt = fd.idx_dtype;
+    const bool id_pool = fd.pool == RBX_POOL_SUM_ID;
+    int begin = 0, end = 0;
+    if (alive) {
+      bool bad;
+      bag_range(fd, b, &begin, &end, &bad);
+      if (bad && lane_g == 0 && status != nullptr) atomicOr(status, kStatusBadOffsets);
+    }
+    const int L = end - begin;
+    Frag acc;
+    acc.zero();
+    int Lmax = L;                                         // wave-uniform number of chunks: the longest bag of the wave
+#pragma unroll
+    for (int o = 32; o >= G && o > 0; o >>= 1) {
+      const int other = __shfl_xor(Lmax, o, 64);
+      Lmax = other > Lmax ? other : Lmax;
+    }
+    for (int c0 = 0; c0 < Lmax; c0 += C) {
+      long long raw[IPL];
+      float wraw[IPL];
+#pragma unroll
+      for (int i = 0; i < IPL; ++i) {                     // (1a) ids and weights, one coalesced sweep; l < L <=> inside [begin, end)
+        const int l = c0 + i * G + lane_g;
+        raw[i] = (l < L) ? load_raw(fd.indices, (static_cast<long long>(begin) + l) * fd.idx_stride, dt) : 0;
+        wraw[i] = (l < L) ? wsrc[static_cast<long long>(begin) + l] : 0.f;
+      }
+      int nvalid = 0;
+#pragma unroll
+      for (int i = 0; i < IPL; ++i) {                     // (1b) classify + compact
+        const int l = c0 + i * G + lane_g;
+        const long long id = decode_id(raw[i], dt);
+        const bool live = l < L;
+        const bool in_range = id >= 0 && id < fd.vocab;
+        if (live && !in_range && status != nullptr) atomicOr(status, kStatusBadId);
+        const bool use = live && in_range && !(id_pool && id == fd.mask_id);
+        const unsigned long long m = (__ballot(use) >> gshift) & gmask;
+        if (use) {
+          const int at = nvalid + __popcll(m & below);
+          my_id[at] = static_cast<int>(id);
+          my_w[at] = wraw[i];
+        }
+        nvalid += __popcll(m);
+      }
+      __builtin_amdgcn_wave_barrier();
+      int nmax = nvalid;                                   // wave-uniform batch count
+#pragma unroll
+      for (int o = 32; o >= G && o > 0; o >>= 1) {
+        const int other = __shfl_xor(nmax, o, 64);
+        nmax = other > nmax ? other : nmax;
+      }
+      for (int k0 = 0; k0 < nmax; k0 += U * R) {          // (2) dense row batches
+        int idu[U];
+        float wu[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int k = k0 + u * R + sub;
+          idu[u] = (k < nvalid) ? my_id[k] : -1;
+          wu[u] = (k < nvalid) ? my_w[k] : 0.f;
+        }
+        Frag r[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          r[u].zero();
+          if (idu[u] >= 0) r[u].load(fd.table + static_cast<long long>(idu[u]) * dim, dim, lane_w);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          r[u].scale(wu[u]);
+          acc.add(r[u]);
+        }
+      }
+      __builtin_amdgcn_wave_barrier();
+    }
+#pragma unroll
+    for (int o = W; o < G; o <<= 1) acc.xor_add(o);       // every lane joins the butterfly
+    if (!alive || sub != 0) continue;
+    acc.store(out + b * stride_b + fd.out_off, dim, lane_w);
+  }
+}
+
+// ---- weight gradient: dw[j] = <dY[bag, slot], table[id_j]> -----------------------------------------------------------
+// The forward's mapping once more: a lane group per bag, the bag's dY fragment loaded once, the ids swept and compacted
+// with their positions, U rows in flight, the dot reduced over the W lanes that hold a row and stored by the first of
+// them.  Only usable positions are written: the host clears dw[0, nnz) in front of the launch, so masked and
+// out-of-range ids and the positions outside every bag read 0.
+template <int W, int NV>
+__device__ __forceinline__ float row_dot(const RowFrag<W, NV, true>& a, const RowFrag<W, NV, true>& b) {
+  float s = 0.f;
+#pragma unroll
+  for (int u = 0; u < NV; ++u)
+    s += (a.a[u].v.x * b.a[u].v.x + a.a[u].v.y * b.a[u].v.y) + (a.a[u].v.z * b.a[u].v.z + a.a[u].v.w * b.a[u].v.w);
+  return s;
+}
+template <int W, int NV>
+__device__ __forceinline__ float row_dot(const RowFrag<W, NV, false>& a, const RowFrag<W, NV, false>& b) {
+  float s = 0.f;
+#pragma unroll
+  for (int u = 0; u < NV; ++u) s += a.a[u].v * b.a[u].v;
+  return s;
+}
+
+template <int G, int R, int NV, bool VEC>
+__global__ __launch_bounds__(256, kCsrWaves) void csr_weight_grad_kernel(const BagPack P, const BagWeightGrads DW, const int F,
+                                                                         const long long B, const float* __restrict__ dout,
+                                                                         const long long stride_b,
+                                                                         int* __restrict__ status) {
+  constexpr int W = G / R;
+  using Frag = RowFrag<W, NV, VEC>;
+  constexpr int U = kCsrU;
+  constexpr int IPL = kCsrIpl;
+  constexpr int C = G * IPL;
+  constexpr int GPB = 256 / G;
+  __shared__ int s_id[GPB][C];
+  __shared__ int s_pos[GPB][C];
+  const int lane_w = threadIdx.x % W;
+  const int sub = (threadIdx.x % G) / W;
+  const int lane_g = threadIdx.x % G;
+  const int gidx = threadIdx.x / G;
+  const int gshift = (threadIdx.x & 63) & ~(G - 1);
+  const unsigned long long gmask = (G == 64) ? ~0ull : ((1ull << G) - 1ull);
+  const unsigned long long below = (1ull << lane_g) - 1ull;
+  volatile int* my_id = s_id[gidx];
+  volatile int* my_pos = s_pos[gidx];
+  constexpr int GPW = 64 / G;
+  const long long tasks_per_bag = (B + GPW - 1) / GPW;
+  const long long ntasks = tasks_per_bag * F;
+  const long long nwaves = static_cast<long long>(gridDim.x) * 4;
+  for (long long t = static_cast<long long>(blockIdx.x) * 4 + threadIdx.x / 64; t < ntasks; t += nwaves) {
+    const int f = __builtin_amdgcn_readfirstlane(static_cast<int>(t / tasks_per_bag));
+    const long long b = (t - f * tasks_per_bag) * GPW + (threadIdx.x & 63) / G;
+    const bool alive = b < B;
+    const BagK& fd = P.f[f];
+    float* __restrict__ dw = DW.dw[f];
+    const int dim = fd.dim, dt = fd.idx_dtype;
+    const bool id_pool = fd.pool == RBX_POOL_SUM_ID;
+    int begin = 0, end = 0;
+    Frag dy;
+    dy.zero();
+    if (alive) {
+      bool bad;
+      bag_range(fd, b, &begin, &end, &bad);
+      if (bad && lane_g == 0 && status != nullptr) atomicOr(status, kStatusBadOffsets);
+      dy.load(dout + b * stride_b + fd.out_off, dim, lane_w);
+    }
+    const int L = end - begin;
+    int Lmax = L;
+#pragma unroll
+    for (int o = 32; o >= G && o > 0; o >>= 1) {
+      const int other = __shfl_xor(Lmax, o, 64);
+      Lmax = other > Lmax ? other : Lmax;
+    }
+    for (int c0 = 0; c0 < Lmax; c0 += C) {
+      long long raw[IPL];
+#pragma unroll
+      for (int i = 0; i < IPL; ++i) {
+        const int l = c0 + i * G + lane_g;
+        raw[i] = (l < L) ? load_raw(fd.indices, (static_cast<long long>(begin) + l) * fd.idx_stride, dt) : 0;
+      }
+      int nvalid = 0;
+#pragma unroll
+      for (int i = 0; i < IPL; ++i) {
+        const int l = c0 + i * G + lane_g;
+        const long long id = decode_id(raw[i], dt);
+        const bool live = l < L;
+        const bool in_range = id >= 0 && id < fd.vocab;
+        if (live && !in_range && status != nullptr) atomicOr(status, kStatusBadId);
+        const bool use = live && in_range && !(id_pool && id == fd.mask_id);
+        const unsigned long long m = (__ballot(use) >> gshift) & gmask;
+        if (use) {
+          const int at = nvalid + __popcll(m & below);
+          my_id[at] = static_cast<int>(id);
+          my_pos[at] = begin + l;                          // < end <= nnz
+        }
+        nvalid += __popcll(m);
+      }
+      __builtin_amdgcn_wave_barrier();
+      int nmax = nvalid;
+#pragma unroll
+      for (int o = 32; o >= G && o > 0; o >>= 1) {
+        const int other = __shfl_xor(nmax, o, 64);
+        nmax = other > nmax ? other : nmax;
+      }
+      for (int k0 = 0; k0 < nmax; k0 += U * R) {
+        int idu[U], pu[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int k = k0 + u * R + sub;
+          idu[u] = (k < nvalid) ? my_id[k] : -1;
+          pu[u] = (k < nvalid) ? my_pos[k] : 0;
+        }
+        Frag r[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          r[u].zero();
+          if (idu[u] >= 0) r[u].load(fd.table + static_cast<long long>(idu[u]) * dim, dim, lane_w);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const float d = group_sum<W>(row_dot(r[u], dy));  // (every lane of the wave is here: the loop bounds are wave-uniform)
+          if (idu[u] >= 0 && lane_w == 0) dw[pu[u]] = d;
+        }
+      }
+      __builtin_amdgcn_wave_barrier();
+    }
+  }
+}
+
 template <int G, int NV, bool VEC>
 static int launch_csr(const BagPack& pack, int F, int64_t B, float* out, int64_t stride_b, float* row_scale, int* status,
                       hipStream_t s) {
@@ -216,6 +469,53 @@ static int dispatch_csr(int units, const BagPack& pack, int F, int64_t B, float*
     case 256: return launch_csr<64, 4, VEC>(pack, F, B, out, stride_b, row_scale, status, s);
     default: return fail(RBX_ERR_UNSUPPORTED, "embedding dim too large for one lane group (units=%d)", units);
   }
+}
+
+// launch_csr / dispatch_csr for the two kernels of the weighted path: GRAD = false the weighted forward (writes `out`),
+// GRAD = true the weight gradient (reads `dout`, writes through `dw`)
+template <bool GRAD, int G, int NV, bool VEC>
+static int launch_csr_weighted(const BagPack& pack, const BagWeights& w, const BagWeightGrads& dw, int F, int64_t B,
+                               float* out, const float* dout, int64_t stride_b, int* status, hipStream_t s) {
+  constexpr int SG = (G <= 8) ? 16 : ((G == 16) ? 32 : 64);
+  long long blocks = ((B + 64 / SG - 1) / (64 / SG) * F + 3) / 4;
+  const long long cap = static_cast<long long>(kCUs) * 64;
+  if (blocks > cap) blocks = cap;
+  if (blocks < 1) blocks = 1;
+  if constexpr (GRAD) {
+    hipLaunchKernelGGL((csr_weight_grad_kernel<SG, SG / G, NV, VEC>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, pack,
+                       dw, F, static_cast<long long>(B), dout, static_cast<long long>(stride_b), status);
+    return check_launch("csr_weight_grad_kernel");
+  } else {
+    hipLaunchKernelGGL((embed_csr_weighted_kernel<SG, SG / G, NV, VEC>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s,
+                       pack, w, F, static_cast<long long>(B), out, static_cast<long long>(stride_b), status);
+    return check_launch("embed_csr_weighted_kernel");
+  }
+}
+
+template <bool GRAD, bool VEC>
+static int dispatch_csr_weighted(int units, const BagPack& pack, const BagWeights& w, const BagWeightGrads& dw, int F, int64_t B,
+                                 float* out, const float* dout, int64_t stride_b, int* status, hipStream_t s) {
+  switch (pow2_ceil(units)) {
+    case 1: return launch_csr_weighted<GRAD, 1, 1, VEC>(pack, w, dw, F, B, out, dout, stride_b, status, s);
+    case 2: return launch_csr_weighted<GRAD, 2, 1, VEC>(pack, w, dw, F, B, out, dout, stride_b, status, s);
+    case 4: return launch_csr_weighted<GRAD, 4, 1, VEC>(pack, w, dw, F, B, out, dout, stride_b, status, s);
+    case 8: return launch_csr_weighted<GRAD, 8, 1, VEC>(pack, w, dw, F, B, out, dout, stride_b, status, s);
+    case 16: return launch_csr_weighted<GRAD, 16, 1, VEC>(pack, w, dw, F, B, out, dout, stride_b, status, s);
+    case 32: return launch_csr_weighted<GRAD, 32, 1, VEC>(pack, w, dw, F, B, out, dout, stride_b, status, s);
+    case 64: return launch_csr_weighted<GRAD, 64, 1, VEC>(pack, w, dw, F, B, out, dout, stride_b, status, s);
+    case 128: return launch_csr_weighted<GRAD, 64, 2, VEC>(pack, w, dw, F, B, out, dout, stride_b, status, s);
+    case 256: return launch_csr_weighted<GRAD, 64, 4, VEC>(pack, w, dw, F, B, out, dout, stride_b, status, s);
+    default: return fail(RBX_ERR_UNSUPPORTED, "embedding dim too large for one lane group (units=%d)", units);
+  }
+}
+
+// a weight array (or a weight gradient) belongs to a sum pool: torch's rule for per_sample_weights
+static int check_weighted_pools(const rbx_bag_t* bags, int n, const void* const* per_bag, const char* what) {
+  for (int i = 0; per_bag != nullptr && i < n; ++i)
+    if (per_bag[i] != nullptr && bags[i].pool != RBX_POOL_SUM && bags[i].pool != RBX_POOL_SUM_ID)
+      return fail(RBX_ERR_UNSUPPORTED, "bag %d: %s with pool mode %d; per-sample weights go with RBX_POOL_SUM / RBX_POOL_SUM_ID "
+                  "only (weighted mean pools are not implemented)", i, what, bags[i].pool);
+  return RBX_OK;
 }
 
 static int compact(int64_t v) { return (v == RBX_NO_ID || v < INT_MIN || v > INT_MAX) ? kNoId : static_cast<int>(v); }
@@ -293,7 +593,8 @@ __global__ __launch_bounds__(256) void csr_bag_map_kernel(const BagPack P, const
 
 // build_keys_kernel's tile structure (one workgroup per sort tile, the tile's digit counts out of the same pass) over
 // lookups that are positions of index arrays: position j of descriptor `lo` is a pair iff the map names a bag for it.
-template <int RB>
+// POS (the weighted sort): the pair's value names the position inside the descriptor's index array instead of the bag.
+template <int RB, bool POS = false>
 __global__ __launch_bounds__(kSortThreads) void csr_keys_kernel(const KeyPack P, const int n_cat, const SegPack S,
                                                                 const unsigned sentinel, const int* __restrict__ map,
                                                                 unsigned* __restrict__ keys0, unsigned* __restrict__ vals0,
@@ -349,7 +650,8 @@ __global__ __launch_bounds__(kSortThreads) void csr_keys_kernel(const KeyPack P,
       }
     }
     keys[j] = key;
-    vals[j] = (static_cast<unsigned>(lo) << kLocalBits) | static_cast<unsigned>(bag < 0 ? 0 : bag);
+    if constexpr (POS) vals[j] = (static_cast<unsigned>(lo) << kLocalBits) | local;
+    else vals[j] = (static_cast<unsigned>(lo) << kLocalBits) | static_cast<unsigned>(bag < 0 ? 0 : bag);
     if (chain_passes > 0) {
 #pragma unroll
       for (int k = 0; k < kCP; ++k)
@@ -427,16 +729,92 @@ static int csr_plan(const rbx_bag_t* bags, int n, int64_t batch, const float* do
   return RBX_OK;
 }
 
-template <int RB>
+template <int RB, bool POS = false>
 static int launch_csr_keys(const CsrPlan& c, char* ws, int* status, hipStream_t s) {
   const BwdPlan& p = c.p;
   const bool chained = p.chained && RB == 8;
-  hipLaunchKernelGGL(csr_keys_kernel<RB>, dim3(p.n_tiles), dim3(kSortThreads), 0, s, p.keys, p.n_cat, p.segs, p.total_rows,
+  hipLaunchKernelGGL((csr_keys_kernel<RB, POS>), dim3(p.n_tiles), dim3(kSortThreads), 0, s, p.keys, p.n_cat, p.segs, p.total_rows,
                      reinterpret_cast<const int*>(ws + c.off_map), reinterpret_cast<unsigned*>(ws + p.off_keys[0]),
                      reinterpret_cast<unsigned*>(ws + p.off_vals[0]), reinterpret_cast<unsigned*>(ws + p.off_keys[1]),
                      reinterpret_cast<unsigned*>(ws + p.off_vals[1]), status, reinterpret_cast<unsigned*>(ws + p.off_fin),
                      reinterpret_cast<unsigned*>(ws + p.off_hist), chained ? p.passes : 0, p.n_tiles);
   return check_launch("csr_keys_kernel");
+}
+
+// ---- weighted reduce: a lookup contributes w[position] * dY[map[position], slot] --------------------------------------
+// GenericPolicy for pairs whose value is a position (csr_keys_kernel<RB, true>): the bag comes from the lookup -> bag map
+// of the sort, the factor from the descriptor's weight array (NULL: 1).  prefetch / flush are GenericPolicy's.
+struct WeightedBagPolicy {
+  static constexpr bool kHasCount = false;
+  struct Args {
+    const float* dout;
+    long long stride_b;
+    const int* map;
+    int accumulate;
+    unsigned lk_off[RBX_MAX_BAGS];        // by descriptor index (RedField::slot)
+    const float* w[RBX_MAX_BAGS];
+  };
+  template <class F>
+  static __device__ __forceinline__ void fetch(const Args& a, const RedField& fd, unsigned pos, int lane_g, F& frag, float& w) {
+    const int bag = a.map[a.lk_off[fd.slot] + pos];
+    const float* wp = a.w[fd.slot];
+    w = (wp != nullptr) ? wp[pos] : 1.0f;
+    frag.load_from(a.dout + static_cast<long long>(bag) * a.stride_b + fd.out_off, fd.dim, lane_g);
+  }
+  static __device__ __forceinline__ float weight(const Args&, float w) { return w; }
+  template <class F>
+  static __device__ __forceinline__ void prefetch(const Args& a, const RedField& fd, unsigned row, int lane_g, F& pre) {
+    if (a.accumulate) pre.add_from(fd.grad + static_cast<size_t>(row) * fd.dim, fd.dim, lane_g);
+  }
+  template <class F>
+  static __device__ __forceinline__ void prefetch_raw(const Args& a, const RedField& fd, unsigned row, int lane_g, F& pre) {
+    if (a.accumulate) pre.load_from(fd.grad + static_cast<size_t>(row) * fd.dim, fd.dim, lane_g);
+  }
+  template <class F>
+  static __device__ __forceinline__ void flush(const Args&, const RedField& fd, unsigned row, const F& acc, float, const F& pre,
+                                               int lane_g) {
+    F out = acc;
+    frag_add(out, pre);
+    out.store_nt(fd.grad + static_cast<size_t>(row) * fd.dim, fd.dim, lane_g);
+  }
+};
+
+// the sort of both paths: map, pairs (POS: position-valued), radix passes
+static int csr_sort(const rbx_bag_t* bags, int n_bags, int64_t batch, void* d_workspace, size_t workspace_bytes,
+                    int* d_status, hipStream_t s, bool pos) {
+  CsrPlan c;
+  int rc = csr_plan(bags, n_bags, batch, nullptr, 0, &c);
+  if (rc != RBX_OK) return rc;
+  const BwdPlan& p = c.p;
+  if (p.n_lookups == 0 || batch == 0) return RBX_OK;
+  if (d_workspace == nullptr || workspace_bytes < c.bytes)
+    return fail(RBX_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, c.bytes);
+  char* ws = static_cast<char*>(d_workspace);
+  int* map = reinterpret_cast<int*>(ws + c.off_map);
+  if (hipMemsetAsync(map, 0xFF, static_cast<size_t>(p.n_lookups) * 4, s) != hipSuccess)   // -1: outside every bag
+    return fail(RBX_ERR_LAUNCH, "clearing the lookup -> bag map failed");
+  long long bx = (batch + 15) / 16;
+  if (bx > kCUs * 8) bx = kCUs * 8;
+  hipLaunchKernelGGL(csr_bag_map_kernel, dim3(static_cast<unsigned>(bx), p.n_cat), dim3(256), 0, s, c.bags, c.lk,
+                     static_cast<long long>(batch), map, d_status);
+  rc = check_launch("csr_bag_map_kernel");
+  if (rc != RBX_OK) return rc;
+  switch (p.radix_bits) {
+    case 8: rc = pos ? launch_csr_keys<8, true>(c, ws, d_status, s) : launch_csr_keys<8>(c, ws, d_status, s); break;
+    case 10: rc = pos ? launch_csr_keys<10, true>(c, ws, d_status, s) : launch_csr_keys<10>(c, ws, d_status, s); break;
+    default: rc = pos ? launch_csr_keys<11, true>(c, ws, d_status, s) : launch_csr_keys<11>(c, ws, d_status, s); break;
+  }
+  if (rc != RBX_OK) return rc;
+  return run_sort_passes(p, ws, s);
+}
+
+// a mean pool's backward needs the row scale the unweighted forward leaves; the weighted entry points carry none
+static int check_no_trained_mean(const rbx_bag_t* bags, int n, const char* who) {
+  for (int i = 0; bags != nullptr && i < n; ++i)
+    if (bags[i].grad != nullptr && (bags[i].pool == RBX_POOL_MEAN_ID || bags[i].pool == RBX_POOL_MEAN_VALUE))
+      return fail(RBX_ERR_UNSUPPORTED, "%s: bag %d is a mean pool with a gradient; its backward goes through rbx_embed_csr_sort / "
+                  "rbx_embed_csr_bwd (d_row_scale)", who, i);
+  return RBX_OK;
 }
 
 }  // namespace rbx
@@ -482,32 +860,7 @@ extern "C" size_t rbx_embed_csr_bwd_workspace_size(const rbx_bag_t* bags, int32_
 
 extern "C" int rbx_embed_csr_sort(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, void* d_workspace,
                                   size_t workspace_bytes, int32_t* d_status, void* stream) {
-  using namespace rbx;
-  CsrPlan c;
-  int rc = csr_plan(bags, n_bags, batch, nullptr, 0, &c);
-  if (rc != RBX_OK) return rc;
-  const BwdPlan& p = c.p;
-  if (p.n_lookups == 0 || batch == 0) return RBX_OK;
-  if (d_workspace == nullptr || workspace_bytes < c.bytes)
-    return fail(RBX_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, c.bytes);
-  char* ws = static_cast<char*>(d_workspace);
-  hipStream_t s = as_stream(stream);
-  int* map = reinterpret_cast<int*>(ws + c.off_map);
-  if (hipMemsetAsync(map, 0xFF, static_cast<size_t>(p.n_lookups) * 4, s) != hipSuccess)   // -1: outside every bag
-    return fail(RBX_ERR_LAUNCH, "clearing the lookup -> bag map failed");
-  long long bx = (batch + 15) / 16;
-  if (bx > kCUs * 8) bx = kCUs * 8;
-  hipLaunchKernelGGL(csr_bag_map_kernel, dim3(static_cast<unsigned>(bx), p.n_cat), dim3(256), 0, s, c.bags, c.lk,
-                     static_cast<long long>(batch), map, d_status);
-  rc = check_launch("csr_bag_map_kernel");
-  if (rc != RBX_OK) return rc;
-  switch (p.radix_bits) {
-    case 8: rc = launch_csr_keys<8>(c, ws, d_status, s); break;
-    case 10: rc = launch_csr_keys<10>(c, ws, d_status, s); break;
-    default: rc = launch_csr_keys<11>(c, ws, d_status, s); break;
-  }
-  if (rc != RBX_OK) return rc;
-  return run_sort_passes(p, ws, s);
+  return rbx::csr_sort(bags, n_bags, batch, d_workspace, workspace_bytes, d_status, rbx::as_stream(stream), false);
 }
 
 extern "C" int rbx_embed_csr_bwd(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, const float* d_dout,
@@ -523,4 +876,137 @@ extern "C" int rbx_embed_csr_bwd(const rbx_bag_t* bags, int32_t n_bags, int64_t 
     return fail(RBX_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, c.bytes);
   return generic_reduce(c.p, d_dout, out_stride_b, nullptr, d_row_scale, batch, accumulate, static_cast<char*>(d_workspace),
                         as_stream(stream));
+}
+
+// ---- per-sample weights ----------------------------------------------------------------------------------------------
+extern "C" int rbx_embed_csr_fwd_weighted(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, const float* const* d_weights,
+                                          float* d_out, int64_t out_stride_b, int32_t* d_status, void* stream) {
+  using namespace rbx;
+  BagK all[RBX_MAX_BAGS];
+  int rc = pack_bags(bags, n_bags, batch, all);
+  if (rc != RBX_OK) return rc;
+  rc = check_weighted_pools(bags, n_bags, reinterpret_cast<const void* const*>(d_weights), "a weight array");
+  if (rc != RBX_OK) return rc;
+  if (batch == 0) return RBX_OK;
+  if (d_out == nullptr) return fail(RBX_ERR_INVALID, "d_out is NULL");
+  // (float4 | scalar) x (unweighted | weighted) launches: a descriptor without weights takes embed_csr_kernel as it
+  // would in rbx_embed_csr_fwd.  Every dim is checked before the first launch, so a refused call writes nothing.
+  BagPack pack[4];
+  BagWeights wts[2];
+  int cnt[4] = {0, 0, 0, 0}, units[4] = {1, 1, 1, 1};
+  for (int i = 0; i < n_bags; ++i) {
+    const bool vec = bag_vec_ok(bags[i], d_out, out_stride_b);
+    const float* w = d_weights != nullptr ? d_weights[i] : nullptr;
+    const int k = (vec ? 0 : 1) + (w != nullptr ? 2 : 0);
+    if (w != nullptr) wts[k - 2].w[cnt[k]] = w;
+    pack[k].f[cnt[k]++] = all[i];
+    const int u = vec ? bags[i].dim / 4 : bags[i].dim;
+    if (u > units[k]) units[k] = u;
+  }
+  for (int k = 0; k < 4; ++k)
+    if (cnt[k] > 0 && pow2_ceil(units[k]) > 256)
+      return fail(RBX_ERR_UNSUPPORTED, "embedding dim too large for one lane group (%s units=%d)", k % 2 == 0 ? "float4" : "scalar",
+                  units[k]);
+  hipStream_t s = as_stream(stream);
+  const BagWeightGrads none = {};
+  for (int k = 0; k < 4; ++k) {
+    if (cnt[k] == 0) continue;
+    switch (k) {
+      case 0: rc = dispatch_csr<true>(units[k], pack[k], cnt[k], batch, d_out, out_stride_b, nullptr, d_status, s); break;
+      case 1: rc = dispatch_csr<false>(units[k], pack[k], cnt[k], batch, d_out, out_stride_b, nullptr, d_status, s); break;
+      case 2: rc = dispatch_csr_weighted<false, true>(units[k], pack[k], wts[0], none, cnt[k], batch, d_out, nullptr, out_stride_b,
+                                                      d_status, s); break;
+      default: rc = dispatch_csr_weighted<false, false>(units[k], pack[k], wts[1], none, cnt[k], batch, d_out, nullptr,
+                                                        out_stride_b, d_status, s); break;
+    }
+    if (rc != RBX_OK) return rc;
+  }
+  return RBX_OK;
+}
+
+extern "C" int rbx_embed_csr_sort_weighted(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, void* d_workspace,
+                                           size_t workspace_bytes, int32_t* d_status, void* stream) {
+  int rc = rbx::check_no_trained_mean(bags, n_bags, "rbx_embed_csr_sort_weighted");
+  if (rc != RBX_OK) return rc;
+  return rbx::csr_sort(bags, n_bags, batch, d_workspace, workspace_bytes, d_status, rbx::as_stream(stream), true);
+}
+
+extern "C" int rbx_embed_csr_bwd_weighted(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, const float* const* d_weights,
+                                          const float* d_dout, int64_t out_stride_b, int32_t accumulate, void* d_workspace,
+                                          size_t workspace_bytes, void* stream) {
+  using namespace rbx;
+  if (d_dout == nullptr) return fail(RBX_ERR_INVALID, "d_dout is NULL");
+  int rc = check_no_trained_mean(bags, n_bags, "rbx_embed_csr_bwd_weighted");
+  if (rc != RBX_OK) return rc;
+  CsrPlan c;
+  rc = csr_plan(bags, n_bags, batch, d_dout, out_stride_b, &c);
+  if (rc != RBX_OK) return rc;
+  rc = check_weighted_pools(bags, n_bags, reinterpret_cast<const void* const*>(d_weights), "a weight array");
+  if (rc != RBX_OK) return rc;
+  const BwdPlan& p = c.p;
+  if (p.n_lookups == 0 || batch == 0) return RBX_OK;
+  if (d_workspace == nullptr || workspace_bytes < c.bytes)
+    return fail(RBX_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, c.bytes);
+  char* ws = static_cast<char*>(d_workspace);
+  WeightedBagPolicy::Args args = {};
+  args.dout = d_dout;
+  args.stride_b = out_stride_b;
+  args.map = reinterpret_cast<const int*>(ws + c.off_map);
+  args.accumulate = accumulate;
+  for (int k = 0; k < p.n_cat; ++k) {
+    const int i = p.red.f[k].slot;                         // the descriptor's index in `bags`
+    args.lk_off[i] = p.keys.f[k].lk_off;
+    args.w[i] = d_weights != nullptr ? d_weights[i] : nullptr;
+  }
+  const int cur = p.passes & 1;
+  const unsigned* keys = reinterpret_cast<const unsigned*>(ws + p.off_keys[cur]);
+  const unsigned* vals = reinterpret_cast<const unsigned*>(ws + p.off_vals[cur]);
+  return p.vec ? dispatch_reduce<WeightedBagPolicy, true>(p, args, keys, vals, ws, as_stream(stream))
+               : dispatch_reduce<WeightedBagPolicy, false>(p, args, keys, vals, ws, as_stream(stream));
+}
+
+extern "C" int rbx_embed_csr_weight_grad(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, const float* d_dout,
+                                         int64_t out_stride_b, float* const* d_dweights, int32_t* d_status, void* stream) {
+  using namespace rbx;
+  BagK all[RBX_MAX_BAGS];
+  int rc = pack_bags(bags, n_bags, batch, all);
+  if (rc != RBX_OK) return rc;
+  if (d_dweights == nullptr) return fail(RBX_ERR_INVALID, "d_dweights is NULL");
+  rc = check_weighted_pools(bags, n_bags, reinterpret_cast<const void* const*>(d_dweights), "a weight gradient");
+  if (rc != RBX_OK) return rc;
+  if (batch > 0 && d_dout == nullptr) return fail(RBX_ERR_INVALID, "d_dout is NULL");
+  BagPack pack[2];
+  BagWeightGrads dws[2];
+  int cnt[2] = {0, 0}, units[2] = {1, 1};
+  for (int i = 0; i < n_bags; ++i) {
+    if (d_dweights[i] == nullptr) continue;
+    const bool vec = bag_vec_ok(bags[i], d_dout, out_stride_b);
+    const int k = vec ? 0 : 1;
+    dws[k].dw[cnt[k]] = d_dweights[i];
+    pack[k].f[cnt[k]++] = all[i];
+    const int u = vec ? bags[i].dim / 4 : bags[i].dim;
+    if (u > units[k]) units[k] = u;
+  }
+  for (int k = 0; k < 2; ++k)
+    if (cnt[k] > 0 && pow2_ceil(units[k]) > 256)
+      return fail(RBX_ERR_UNSUPPORTED, "embedding dim too large for one lane group (%s units=%d)", k == 0 ? "float4" : "scalar",
+                  units[k]);
+  hipStream_t s = as_stream(stream);
+  // dw is fully defined after the call: everything the kernel does not write (masked and out-of-range ids, positions
+  // outside every bag, a batch of zero bags) is cleared here
+  for (int i = 0; i < n_bags; ++i)
+    if (d_dweights[i] != nullptr && bags[i].nnz > 0 &&
+        hipMemsetAsync(d_dweights[i], 0, static_cast<size_t>(bags[i].nnz) * 4, s) != hipSuccess)
+      return fail(RBX_ERR_LAUNCH, "clearing a weight gradient failed");
+  if (batch == 0) return RBX_OK;
+  const BagWeights none = {};
+  for (int k = 0; k < 2; ++k) {
+    if (cnt[k] == 0) continue;
+    rc = (k == 0) ? dispatch_csr_weighted<true, true>(units[k], pack[k], none, dws[k], cnt[k], batch, nullptr, d_dout, out_stride_b,
+                                                      d_status, s)
+                  : dispatch_csr_weighted<true, false>(units[k], pack[k], none, dws[k], cnt[k], batch, nullptr, d_dout,
+                                                       out_stride_b, d_status, s);
+    if (rc != RBX_OK) return rc;
+  }
+  return RBX_OK;
 }

@@ -622,12 +622,21 @@ class Bags(object):
     """One ragged multi-hot feature of a batch, the layout of ``nn.EmbeddingBag``: ``indices`` flat ``[nnz]`` ids (int32 /
     int64 / float32 / float64, any element stride), ``offsets`` ``[B + 1]`` (int32 / int64, contiguous); bag ``b`` is
     ``indices[offsets[b]:offsets[b + 1]]``.  ``offsets[0] > 0``, ``offsets[B] < nnz`` and empty bags are fine.  Nothing
-    here reads device memory: ``nnz`` and ``B`` come from the shapes."""
-    __slots__ = ("indices", "offsets")
+    here reads device memory: ``nnz`` and ``B`` come from the shapes.  ``weights`` (optional): float32 ``[nnz]`` on the same
+    device, ``weights[j]`` the factor of ``indices[j]`` (``per_sample_weights``; sum pools only); it may require a gradient."""
+    __slots__ = ("indices", "offsets", "weights")
 
-    def __init__(self, indices, offsets):
+    def __init__(self, indices, offsets, weights=None):
         _require_cuda(indices, "bag indices")
         _require_cuda(offsets, "bag offsets")
+        if weights is not None:
+            _require_cuda(weights, "bag weights")
+            if weights.dtype != torch.float32:
+                raise TypeError("bag weights must be float32, got %s" % weights.dtype)
+            if weights.dim() != 1 or weights.numel() != indices.numel() or weights.device != indices.device:
+                raise ValueError("bag weights must be 1-D with one entry per index on the indices' device, got %s on %s for "
+                                 "%d indices on %s" % (tuple(weights.shape), weights.device, indices.numel(), indices.device))
+            weights = weights.contiguous()
         if indices.device != offsets.device:
             raise ValueError("bag indices and offsets live on different devices (%s, %s)" % (indices.device, offsets.device))
         if indices.dim() != 1 or offsets.dim() != 1:
@@ -640,7 +649,7 @@ class Bags(object):
             raise TypeError("bag offsets must be int32 or int64, got %s" % offsets.dtype)
         if offsets.numel() > 1 and offsets.stride(0) != 1:
             raise ValueError("bag offsets must be contiguous")
-        self.indices, self.offsets = indices, offsets
+        self.indices, self.offsets, self.weights = indices, offsets, weights
 
     @property
     def batch(self):
@@ -651,17 +660,22 @@ class Bags(object):
         return self.indices.numel()
 
 
-def bags_from_padded(ids, mask_id):
-    """``[B, L]`` padded ids -> ``Bags`` of the ids that differ from ``mask_id``, in order (int64 offsets).  ATen glue with a
+def bags_from_padded(ids, mask_id, weights=None):
+    """``[B, L]`` padded ids -> ``Bags`` of the ids that differ from ``mask_id``, in order (int64 offsets); ``weights``
+    (optional, ``[B, L]`` float32) goes through the same selection.  ATen glue with a
     host sync (the number of live ids decides a shape): a converter for tests and data preparation, not meant for a captured
     step -- a loader that holds ragged histories builds ``Bags`` directly."""
     _require_cuda(ids, "ids")
     if ids.dim() != 2:
         raise ValueError("expected padded ids of shape [B, L], got %s" % (tuple(ids.shape),))
+    if weights is not None:
+        _require_cuda(weights, "weights")
+        if tuple(weights.shape) != tuple(ids.shape):
+            raise ValueError("expected weights of the ids' shape %s, got %s" % (tuple(ids.shape), tuple(weights.shape)))
     keep = ids != mask_id
     offsets = torch.zeros(ids.shape[0] + 1, dtype=torch.int64, device=ids.device)
     torch.cumsum(keep.sum(1), 0, out=offsets[1:])
-    return Bags(ids[keep], offsets)
+    return Bags(ids[keep], offsets, weights[keep] if weights is not None else None)
 
 
 class BagSpec(object):
@@ -699,6 +713,12 @@ class BagPlan(object):
         for f, s, g in zip(self.arr, self.specs, bags):
             if not isinstance(g, Bags):
                 raise TypeError("feature '%s': expected ops.Bags, got %s" % (s.name, type(g).__name__))
+            if getattr(g, "weights", None) is not None and self.needs_row_scale:
+                if s.pool in (POOL_MEAN_VALUE, POOL_MEAN_ID):
+                    raise NotImplementedError("feature '%s': per-sample weights go with the sum pools only; weighted mean "
+                                              "pools are not implemented" % s.name)
+                raise NotImplementedError("feature '%s': a call with weighted bags takes sum pools only; give the mean-pooled "
+                                          "features an embed_bags call of their own" % s.name)
             if B is None:
                 B = g.batch
             elif g.batch != B:
@@ -729,11 +749,13 @@ class _EmbedBags(torch.autograd.Function):
     """out[B, width] = pooled gather over ragged bags (rbx_embed_csr_fwd); backward = the sorted segmented scatter-add
     over the lookups that exist (rbx_embed_csr_sort in the forward, on the current stream; rbx_embed_csr_bwd).  Plain
     autograd semantics: freshly zeroed dense gradients (or, for a table another lookup of the pass has already written,
-    that node's gradient: config.share_table_grads).  No host sync beyond the id check config.check_ids asks for."""
+    that node's gradient: config.share_table_grads).  No host sync beyond the id check config.check_ids asks for.
+    ``weights``: one entry per bag, a float32 [nnz] tensor or None.  With any of them set the three calls are the
+    ``_weighted`` ones, and rbx_embed_csr_weight_grad runs in the backward for the weights that want a gradient."""
 
     @staticmethod
     def forward(ctx, plan, n_bags, train, *tensors):
-        inputs, params = tensors[:2 * n_bags], tensors[2 * n_bags:]
+        inputs, weights, params = tensors[:2 * n_bags], tensors[2 * n_bags:3 * n_bags], tensors[3 * n_bags:]
         for p in params:
             _require_cuda(p, "embedding parameter")
             if p.dtype != torch.float32 or not p.is_contiguous():
@@ -743,22 +765,31 @@ class _EmbedBags(torch.autograd.Function):
         B = inputs[1].numel() - 1
         dev = params[0].device
         out = torch.empty((B, plan.width), dtype=torch.float32, device=dev)
-        row_scale = torch.empty((plan.n, B), dtype=torch.float32, device=dev) if plan.needs_row_scale else None
         status = _status_word(dev)
-        check(_timed(("embed_csr_fwd", plan.n, plan.width, B),
-                     lambda: lib.rbx_embed_csr_fwd(plan.arr, plan.n, B, _ptr(out), out.stride(0) if B > 1 else plan.width,
-                                                   _ptr(row_scale), _ptr(status), _stream())))
+        stride = out.stride(0) if B > 1 else plan.width
+        ctx.warr = _ptr_array(weights) if any(w is not None for w in weights) else None
+        if ctx.warr is None:
+            row_scale = torch.empty((plan.n, B), dtype=torch.float32, device=dev) if plan.needs_row_scale else None
+            check(_timed(("embed_csr_fwd", plan.n, plan.width, B),
+                         lambda: lib.rbx_embed_csr_fwd(plan.arr, plan.n, B, _ptr(out), stride, _ptr(row_scale), _ptr(status),
+                                                       _stream())))
+        else:
+            row_scale = None
+            check(_timed(("embed_csr_fwd_weighted", plan.n, plan.width, B),
+                         lambda: lib.rbx_embed_csr_fwd_weighted(plan.arr, plan.n, B, ctx.warr, _ptr(out), stride, _ptr(status),
+                                                                _stream())))
         _check_status(status)
-        ctx.plan, ctx.inputs, ctx.row_scale, ctx.B, ctx.params = plan, inputs, row_scale, B, params
+        ctx.plan, ctx.inputs, ctx.row_scale, ctx.B, ctx.params, ctx.weights = plan, inputs, row_scale, B, params, weights
         ctx.ws, ctx.ws_bytes = None, 0
         if train:
             _note_readers(ctx, params)
         if B > 0 and train:
-            ctx.ws, ctx.ws_bytes = _EmbedBags._sort(plan, params, [p if p.requires_grad else None for p in params], B, dev)
+            ctx.ws, ctx.ws_bytes = _EmbedBags._sort(plan, params, [p if p.requires_grad else None for p in params], B, dev,
+                                                    ctx.warr is not None)
         return out
 
     @staticmethod
-    def _sort(plan, params, grads, B, dev):
+    def _sort(plan, params, grads, B, dev, weighted=False):
         plan.bind_params(params, grads)
         ws_bytes = lib.rbx_embed_csr_bwd_workspace_size(plan.arr, plan.n, B)
         if ws_bytes == 0:
@@ -766,29 +797,47 @@ class _EmbedBags(torch.autograd.Function):
             if "too large" in msg or "exceeds" in msg or "limit" in msg:
                 raise NotImplementedError(msg)
         ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-        check(lib.rbx_embed_csr_sort(plan.arr, plan.n, B, _ptr(ws), ws_bytes, None, _stream()))
+        if weighted:                                   # pairs that name the lookup's position: rbx_embed_csr_bwd_weighted's
+            check(lib.rbx_embed_csr_sort_weighted(plan.arr, plan.n, B, _ptr(ws), ws_bytes, None, _stream()))
+        else:
+            check(lib.rbx_embed_csr_sort(plan.arr, plan.n, B, _ptr(ws), ws_bytes, None, _stream()))
         return ws, ws_bytes
 
     @staticmethod
     def backward(ctx, dout):
-        plan, params, B = ctx.plan, ctx.params, ctx.B
+        plan, params, B, n = ctx.plan, ctx.params, ctx.B, len(ctx.weights)
         if dout.stride(1) != 1 or dout.dtype != torch.float32:
             dout = dout.contiguous().float()
-        first = 3 + len(ctx.inputs)
+        first = 3 + len(ctx.inputs) + n
         want = [ctx.needs_input_grad[first + i] for i in range(len(params))]
-        head = (None, None, None) + (None,) * len(ctx.inputs)
+        want_w = [ctx.needs_input_grad[first - n + i] for i in range(n)]
+        stride = dout.stride(0) if B > 1 else plan.width
+        plan.bind_tensors(ctx.inputs)
+        dws = [None] * n
+        if any(want_w):                                    # dw = <dY, row>: reads the tables, needs no sort
+            plan.bind_params(params)
+            dws = [torch.empty_like(w) if k else None for w, k in zip(ctx.weights, want_w)]
+            check(lib.rbx_embed_csr_weight_grad(plan.arr, plan.n, B, _ptr(dout), stride, _ptr_array(dws), None, _stream()))
+        head = (None, None, None) + (None,) * len(ctx.inputs) + tuple(dws)
+        if not any(want):                                  # frozen tables
+            return head + (None,) * len(params)
         adopted = _adopt_grads(ctx, params, want) if B > 0 else None
         grads = adopted if adopted is not None else _flat_zero_grads(params, want, dout.device)
         if B == 0:
             return head + tuple(grads)
-        plan.bind_tensors(ctx.inputs)
+        weighted = ctx.warr is not None
         if ctx.ws is not None and [p.requires_grad for p in params] == list(want):
             plan.bind_params(params, grads)
             ws, ws_bytes = ctx.ws, ctx.ws_bytes
         else:                                          # e.g. torch.autograd.grad on a subset: sort now
-            ws, ws_bytes = _EmbedBags._sort(plan, params, grads, B, dout.device)
-        check(lib.rbx_embed_csr_bwd(plan.arr, plan.n, B, _ptr(dout), dout.stride(0) if B > 1 else plan.width,
-                                    _ptr(ctx.row_scale), 1 if adopted is not None else 0, _ptr(ws), ws_bytes, _stream()))
+            ws, ws_bytes = _EmbedBags._sort(plan, params, grads, B, dout.device, weighted)
+        accumulate = 1 if adopted is not None else 0
+        if weighted:
+            check(lib.rbx_embed_csr_bwd_weighted(plan.arr, plan.n, B, ctx.warr, _ptr(dout), stride, accumulate, _ptr(ws),
+                                                 ws_bytes, _stream()))
+        else:
+            check(lib.rbx_embed_csr_bwd(plan.arr, plan.n, B, _ptr(dout), stride, _ptr(ctx.row_scale), accumulate, _ptr(ws),
+                                        ws_bytes, _stream()))
         if adopted is not None:                        # the rows went into the gradient another node of this pass returned
             for p, w in zip(params, want):
                 if w:
@@ -798,11 +847,17 @@ class _EmbedBags(torch.autograd.Function):
         return head + tuple(grads)
 
 
+def _ptr_array(tensors):
+    """Host array of device pointers, NULL where the entry is None."""
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() if t is not None else None for t in tensors])
+
+
 def embed_bags(plan_or_specs, bags, params):
     """Pooled lookup over ragged bags: ``plan_or_specs`` a ``BagPlan`` or a list of ``BagSpec``, ``bags`` one ``Bags`` per
     spec, ``params`` the distinct tables the specs' ``param`` indices name.  Returns ``[B, width]``; slot ``i`` holds the pool
     of feature ``i`` (an empty bag: zeros).  An ``nn.EmbeddingBag(mode="sum" / "mean")`` call maps onto one spec with
-    POOL_SUM / POOL_MEAN_ID (``mask_id=None``, ``eps=0`` divides by the bag length)."""
+    POOL_SUM / POOL_MEAN_ID (``mask_id=None``, ``eps=0`` divides by the bag length); ``per_sample_weights`` are the
+    ``weights`` of the ``Bags`` (sum pools only), and a weight tensor that requires a gradient gets one."""
     plan = plan_or_specs if isinstance(plan_or_specs, BagPlan) else BagPlan(plan_or_specs)
     params = list(params)
     for g in bags:
@@ -811,8 +866,9 @@ def embed_bags(plan_or_specs, bags, params):
     for p in params:
         _require_cuda(p, "embedding parameter")
     _, tensors = plan.bind_inputs(bags)
+    weights = [getattr(g, "weights", None) for g in bags]
     train = torch.is_grad_enabled() and any(p.requires_grad for p in params)   # grad mode is off inside forward()
-    return _EmbedBags.apply(plan, plan.n, train, *tensors, *params)
+    return _EmbedBags.apply(plan, plan.n, train, *tensors, *weights, *params)
 
 
 class _Interaction(torch.autograd.Function):

@@ -69,13 +69,18 @@ class EmbeddingLayer(nn.Module):
         """Some sequence features arrive as ``ops.Bags`` (ragged indices / offsets) instead of ``[B, L]`` ids: they go
         through ``ops.embed_bags`` (rbx_embed_csr_*), every other feature through the usual plan (rbx_embed_fwd), and the
         slots are joined by columns in feature order.  Tables shared between the two calls get one gradient: the second
-        backward node of the pass adds its rows into the first one's (ops.config.share_table_grads)."""
+        backward node of the pass adds its rows into the first one's (ops.config.share_table_grads).  ``Bags`` that carry
+        per-sample weights (pooling='sum' only) get an ``embed_bags`` call of their own, beside the unweighted ones'."""
+        def weighted(f):
+            return getattr(x[f.name], "weights", None) is not None
+
         key = ("bags", tuple(id(f) for f in features), squeeze_dim,
-               tuple(("bags" if isinstance(x[f.name], ops.Bags) else x[f.name].shape[1]) if isinstance(f, SequenceFeature)
-                     else 0 for f in features))
+               tuple((("wbags" if weighted(f) else "bags") if isinstance(x[f.name], ops.Bags) else x[f.name].shape[1])
+                     if isinstance(f, SequenceFeature) else 0 for f in features))
         cached = self._plans.get(key)
         if cached is None:
-            order, padded, specs, tables, off = [], [], [], [], 0
+            order, padded = [], []
+            specs, tables, offs = ([], []), ([], []), [0, 0]          # [0] the unweighted bags' call, [1] the weighted ones'
             for fea in features:
                 if isinstance(fea, DenseFeature):
                     continue
@@ -92,27 +97,33 @@ class EmbeddingLayer(nn.Module):
                 if fea.pooling not in ("sum", "mean"):
                     raise ValueError("Sequence pooling method supports only pooling in %s, got %s." %
                                      (["sum", "mean"], fea.pooling))
+                g = 1 if weighted(fea) else 0
+                if g and fea.pooling == "mean":
+                    raise NotImplementedError("feature '%s': per-sample weights go with pooling='sum' only; weighted mean "
+                                              "pools are not implemented" % fea.name)
                 table = self.embed_dict[fea.name if fea.shared_with is None else fea.shared_with]
-                if not any(t is table for t in tables):
-                    tables.append(table)
-                param = [i for i, t in enumerate(tables) if t is table][0]
+                if not any(t is table for t in tables[g]):
+                    tables[g].append(table)
+                param = [i for i, t in enumerate(tables[g]) if t is table][0]
                 mask_id = fea.padding_idx if fea.padding_idx is not None else -1   # InputMask: id != -1
-                specs.append(ops.BagSpec(fea.name, table.embedding_dim, off, param,
-                                         POOL_SUM_ID if fea.pooling == "sum" else POOL_MEAN_ID, table.num_embeddings,
-                                         padding_idx=table.padding_idx, mask_id=mask_id, eps=1e-16))
-                order.append(("bags", len(specs) - 1))
-                off += table.embedding_dim
+                specs[g].append(ops.BagSpec(fea.name, table.embedding_dim, offs[g], param,
+                                            POOL_SUM_ID if fea.pooling == "sum" else POOL_MEAN_ID, table.num_embeddings,
+                                            padding_idx=table.padding_idx, mask_id=mask_id, eps=1e-16))
+                order.append(("bags", (g, len(specs[g]) - 1)))
+                offs[g] += table.embedding_dim
             n_sparse = len(order)
             if squeeze_dim:
                 for fea in features:
                     if isinstance(fea, DenseFeature):
                         order.append(("padded", len(padded)))
                         padded.append(host.Lookup(fea.name, FIELD_DENSE, None, 1))
-            cached = (host.Plan(padded) if padded else None, ops.BagPlan(specs), tables, order, n_sparse)
+            cached = (host.Plan(padded) if padded else None, [ops.BagPlan(sp) if sp else None for sp in specs], tables, order,
+                      n_sparse)
             self._plans[key] = cached
-        plan, bag_plan, tables, order, n_sparse = cached
+        plan, bag_plans, tables, order, n_sparse = cached
         out_p = plan.run([x[lk.name] for lk in plan.lookups]) if plan is not None else None
-        out_b = ops.embed_bags(bag_plan, [x[s.name] for s in bag_plan.specs], [t.weight for t in tables])
+        out_b = [ops.embed_bags(bp, [x[s.name] for s in bp.specs], [t.weight for t in tb]) if bp is not None else None
+                 for bp, tb in zip(bag_plans, tables)]
         pieces, dims, concat = [], set(), False
         for kind, i in order:
             if kind == "padded":
@@ -122,8 +133,8 @@ class EmbeddingLayer(nn.Module):
                 if sp.kind != FIELD_DENSE:
                     dims.add(sp.dim)
             else:
-                sp = bag_plan.specs[i]
-                pieces.append(out_b[:, sp.out_off:sp.out_off + sp.dim])
+                sp = bag_plans[i[0]].specs[i[1]]
+                pieces.append(out_b[i[0]][:, sp.out_off:sp.out_off + sp.dim])
                 dims.add(sp.dim)
         out = torch.cat(pieces, 1)
         if squeeze_dim:
