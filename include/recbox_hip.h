@@ -224,6 +224,40 @@ int rbx_embed_csr_bwd_weighted(const rbx_bag_t* bags, int32_t n_bags, int64_t ba
 int rbx_embed_csr_weight_grad(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, const float* d_dout,
                               int64_t out_stride_b, float* const* d_dweights, int32_t* d_status, void* stream);
 
+/* The long-bag form of the three bag-walking calls above.  They map one lane group to one bag whatever its length, so a
+ * few bags of thousands of ids keep a wave (and the launch) waiting for one group.  The `_long` calls take a
+ * long_threshold T: a bag of at least T ids (after the clamp) is cut into segments of RBX_CSR_SEGMENT consecutive ids, a
+ * wave per segment over the whole grid, and the segments' partial sums are added in ascending segment order.
+ *   - a bag shorter than T is summed by its lane group exactly as in the calls above: the same bits;
+ *   - a bag of T ids or more has its own, fixed summation order: bit-identical from run to run, NOT bit-equal to the
+ *     padded call -- it meets the float64 bound of the sum instead.  With every weight 1.0f the weighted long call is
+ *     bit-equal to the unweighted long call;
+ *   - long_threshold 0 = never: the calls above, bit for bit (the workspace is then the 256-byte header only).
+ * The long bags are found on the device (no host read of offsets: the calls stay capturable in a hipGraph).
+ * d_workspace: rbx_embed_csr_fwd_long_workspace_size bytes for the same bags / batch / threshold -- one size serves the
+ * three calls; it depends on nnz, dim, batch and the threshold only (no pointer of the descriptors is read), is at least
+ * the header for nnz == 0 and never shrinks when an nnz grows.  A smaller workspace returns RBX_ERR_WORKSPACE.  The
+ * call clears the header itself (a memset node).  Afterwards the header's int32 word RBX_CSR_WS_SEGMENTS holds the number
+ * of segments and word RBX_CSR_WS_LONG_BAGS the number of bags that took the long form -- tests and profiles read them.
+ * Well-formed offsets cannot exceed the workspace (the bag lengths of a descriptor sum to at most nnz).  Malformed ones
+ * (overlapping bags) can: a bag that finds the list or the partial area full is walked by its lane group in the same
+ * launch, as in the calls above; the two words may then read beyond what was used, and every kernel clamps them.  No
+ * input makes a kernel read outside indices[0, nnz) or write outside the workspace and d_out; status bits as above.
+ * Refusals (pools, dims, NULLs) are those of the calls above and are made before anything is launched. */
+#define RBX_CSR_SEGMENT 256      /* ids per segment: a multiple of every lane-group chunk (64, 128, 256) */
+#define RBX_CSR_WS_SEGMENTS 0    /* int32 word index into the workspace header */
+#define RBX_CSR_WS_LONG_BAGS 1
+size_t rbx_embed_csr_fwd_long_workspace_size(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, int64_t long_threshold);
+int rbx_embed_csr_fwd_long(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, int64_t long_threshold, float* d_out,
+                           int64_t out_stride_b, float* d_row_scale, void* d_workspace, size_t workspace_bytes,
+                           int32_t* d_status, void* stream);
+int rbx_embed_csr_fwd_weighted_long(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, int64_t long_threshold,
+                                    const float* const* d_weights, float* d_out, int64_t out_stride_b, void* d_workspace,
+                                    size_t workspace_bytes, int32_t* d_status, void* stream);
+int rbx_embed_csr_weight_grad_long(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, int64_t long_threshold,
+                                   const float* d_dout, int64_t out_stride_b, float* const* d_dweights, void* d_workspace,
+                                   size_t workspace_bytes, int32_t* d_status, void* stream);
+
 /* ---- K4: InnerProductInteraction / rechub FM on a materialised [B,F,D] tensor ---
  * ranking/pytorch/layers/interactions/inner_product.py:40-56,
  * third_party/rechub/basic/layers.py:286-292.

@@ -6,8 +6,10 @@ gradient, so that no zero fill is inside the bracket) with HIP events on torch's
     python profiles/csr_gather.py [--repeats 20] [--rows 10000000] [--out FILE]
 
 Cases: (1) every bag 50 ids = the padded L = 50 call's lookups; (2) lengths uniform in 1 .. 50 against the same ids padded
-to 50; (3) skewed lengths (bags of 1 .. 9 ids, 0.1 % of them 1 000 .. 5 000) against the same nnz spread evenly; (4) case 2's bags
-under SUM_ID with and without per-sample weights, and the weight-gradient call."""
+to 50; (3) skewed lengths (bags of 1 .. 9 ids, 0.1 % of them 1 000 .. 5 000) against the same nnz spread evenly, the skewed
+batch with the long-bag form off (threshold 0: a lane group per bag) and on (``--threshold``, default the one in force)
+alternating; (4) case 2's bags under SUM_ID with and without per-sample weights, and the weight-gradient call.  Every CSR
+variant calls what ``ops.embed_bags`` calls: the ``_long`` entry points with the threshold, the plain ones at 0."""
 import argparse
 import os
 import statistics
@@ -66,8 +68,20 @@ class Padded(object):
                                      self.nbytes, ops._stream()))
 
 
+def long_workspace(plan, threshold):
+    nbytes = lib.rbx_embed_csr_fwd_long_workspace_size(plan.arr, plan.n, B, threshold)
+    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device="cuda"), nbytes
+
+
+def long_counts(ws):
+    """(bags that took the long form, segments) of the last ``_long`` call over this workspace."""
+    words = ws[:8].view(torch.int32).tolist()
+    return words[_lib.CSR_WS_LONG_BAGS], words[_lib.CSR_WS_SEGMENTS]
+
+
 class Ragged(object):
-    def __init__(self, emb, grad, bags):
+    def __init__(self, emb, grad, bags, threshold=None):
+        self.threshold = ops.bag_long_threshold() if threshold is None else threshold
         self.plan = ops.BagPlan([ops.BagSpec("h", D, 0, 0, _lib.POOL_MEAN_ID, emb.num_embeddings, mask_id=0, eps=1e-16)])
         self.bags, self.w, self.g = bags, emb.weight, grad
         self.out = torch.empty(B, D, device="cuda")
@@ -77,9 +91,15 @@ class Ragged(object):
         self.nbytes = lib.rbx_embed_csr_bwd_workspace_size(self.plan.arr, 1, B)
         self.ws = torch.empty(self.nbytes, dtype=torch.uint8, device="cuda")
         self.lookups = bags.nnz
+        self.lws, self.lbytes = long_workspace(self.plan, self.threshold)
 
     def fwd(self):
-        _lib.check(lib.rbx_embed_csr_fwd(self.plan.arr, 1, B, self.out.data_ptr(), D, self.scale.data_ptr(), None, ops._stream()))
+        if self.threshold > 0:
+            _lib.check(lib.rbx_embed_csr_fwd_long(self.plan.arr, 1, B, self.threshold, self.out.data_ptr(), D, self.scale.data_ptr(),
+                                                  self.lws.data_ptr(), self.lbytes, None, ops._stream()))
+        else:
+            _lib.check(lib.rbx_embed_csr_fwd(self.plan.arr, 1, B, self.out.data_ptr(), D, self.scale.data_ptr(), None,
+                                             ops._stream()))
 
     def sort(self):
         _lib.check(lib.rbx_embed_csr_sort(self.plan.arr, 1, B, self.ws.data_ptr(), self.nbytes, None, ops._stream()))
@@ -105,10 +125,18 @@ class Weighted(object):
         self.weights = torch.rand(bags.nnz, device="cuda") * 2 - 1
         self.dw = torch.empty(bags.nnz, device="cuda")
         self.warr, self.dwarr = ops._ptr_array([self.weights]), ops._ptr_array([self.dw])
+        self.threshold = ops.bag_long_threshold()
+        self.lws, self.lbytes = long_workspace(self.plan, self.threshold)
 
     def fwd(self):
-        if self.weighted:
+        T, ws, nb = self.threshold, self.lws.data_ptr(), self.lbytes
+        if self.weighted and T > 0:
+            _lib.check(lib.rbx_embed_csr_fwd_weighted_long(self.plan.arr, 1, B, T, self.warr, self.out.data_ptr(), D, ws, nb, None,
+                                                           ops._stream()))
+        elif self.weighted:
             _lib.check(lib.rbx_embed_csr_fwd_weighted(self.plan.arr, 1, B, self.warr, self.out.data_ptr(), D, None, ops._stream()))
+        elif T > 0:
+            _lib.check(lib.rbx_embed_csr_fwd_long(self.plan.arr, 1, B, T, self.out.data_ptr(), D, None, ws, nb, None, ops._stream()))
         else:
             _lib.check(lib.rbx_embed_csr_fwd(self.plan.arr, 1, B, self.out.data_ptr(), D, None, None, ops._stream()))
 
@@ -127,7 +155,11 @@ class Weighted(object):
                                              ops._stream()))
 
     def wgrad(self):
-        _lib.check(lib.rbx_embed_csr_weight_grad(self.plan.arr, 1, B, self.out.data_ptr(), D, self.dwarr, None, ops._stream()))
+        if self.threshold > 0:
+            _lib.check(lib.rbx_embed_csr_weight_grad_long(self.plan.arr, 1, B, self.threshold, self.out.data_ptr(), D, self.dwarr,
+                                                          self.lws.data_ptr(), self.lbytes, None, ops._stream()))
+        else:
+            _lib.check(lib.rbx_embed_csr_weight_grad(self.plan.arr, 1, B, self.out.data_ptr(), D, self.dwarr, None, ops._stream()))
 
 
 def bags_of(lengths, rows, gen):
@@ -163,7 +195,10 @@ def main():
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--rows", type=int, default=10000000)
     ap.add_argument("--out", default="", help="also write the markdown report to this file")
+    ap.add_argument("--threshold", type=int, default=None, help="ops.bag_long_threshold for the run (default: the one in force)")
     a = ap.parse_args()
+    if a.threshold is not None:
+        ops.bag_long_threshold(a.threshold)
     gen = torch.Generator().manual_seed(7)
     emb = torch.nn.Embedding(a.rows, D).cuda()
     grad = torch.zeros_like(emb.weight)
@@ -172,8 +207,8 @@ def main():
                                 text=True).stdout.strip() or "working tree"
     except OSError:
         commit = "working tree"
-    lines = ["box: %s, torch %s; commit: %s; B = %d, table %d x %d, MEAN_ID, %d repeats, variants alternating"
-             % (torch.cuda.get_device_name(0), torch.__version__, commit, B, a.rows, D, a.repeats)]
+    lines = ["box: %s, torch %s; commit: %s; B = %d, table %d x %d, MEAN_ID, %d repeats, variants alternating; long-bag threshold %d"
+             % (torch.cuda.get_device_name(0), torch.__version__, commit, B, a.rows, D, a.repeats, ops.bag_long_threshold())]
     full = bags_of(torch.full((B,), L, dtype=torch.int64), a.rows, gen)
     pad = Padded(emb, grad, full.indices.view(B, L))
     case("1. every bag %d ids (the padded call's lookups; `padded again` = its run-to-run spread)" % L,
@@ -188,8 +223,16 @@ def main():
     total = int(skew.sum())
     even = torch.full((B,), total // B, dtype=torch.int64)
     even[:total - int(even.sum())] += 1
-    case("3. skewed lengths (1 .. 9, 0.1 pct of the bags 1 000 .. 5 000) against the same nnz spread evenly", ["even", "skewed"],
-         [Ragged(emb, grad, bags_of(even, a.rows, gen)), Ragged(emb, grad, bags_of(skew, a.rows, gen))], a.repeats, lines)
+    skewed = bags_of(skew, a.rows, gen)
+    walked, handed = Ragged(emb, grad, skewed, threshold=0), Ragged(emb, grad, skewed)
+    case("3. skewed lengths (1 .. 9, 0.1 pct of the bags 1 000 .. 5 000) against the same nnz spread evenly",
+         ["even", "skewed, threshold 0", "skewed, threshold %d" % handed.threshold],
+         [Ragged(emb, grad, bags_of(even, a.rows, gen)), walked, handed], a.repeats, lines)
+    torch.cuda.synchronize()
+    same = torch.equal(walked.out[(skew < max(handed.threshold, 1)).cuda()], handed.out[(skew < max(handed.threshold, 1)).cuda()])
+    err = float((walked.out - handed.out).abs().max())
+    lines.append("\nlong form on the skewed batch: %d bags in %d segments; bags below the threshold bit-equal to threshold 0: %s; "
+                 "max |difference| over all bags %.3g" % (long_counts(handed.lws) + (same, err)))
     plain, scored = Weighted(emb, grad, uni, False), Weighted(emb, grad, uni, True)
     case("4. case 2's bags under SUM_ID, unweighted against random per-sample weights", ["unweighted", "weighted"],
          [plain, scored], a.repeats, lines)

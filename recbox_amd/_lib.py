@@ -48,6 +48,8 @@ class rbx_field_t(ctypes.Structure):
 
 RBX_MAX_BAGS = 32
 STATUS_BAD_ID, STATUS_BAD_OFFSETS = 1, 2     # bits of the kernels' status word
+CSR_SEGMENT = 256                            # RBX_CSR_SEGMENT: ids per segment of a long bag
+CSR_WS_SEGMENTS, CSR_WS_LONG_BAGS = 0, 1     # int32 words of the long-bag workspace header
 
 
 class rbx_bag_t(ctypes.Structure):
@@ -115,6 +117,10 @@ SIGNATURES = {
     "rbx_embed_csr_sort_weighted": (ctypes.c_int, [_BP, _i32, _i64, _P, _sz, _P, _P]),
     "rbx_embed_csr_bwd_weighted": (ctypes.c_int, [_BP, _i32, _i64, _PP, _P, _i64, _i32, _P, _sz, _P]),
     "rbx_embed_csr_weight_grad": (ctypes.c_int, [_BP, _i32, _i64, _P, _i64, _PP, _P, _P]),
+    "rbx_embed_csr_fwd_long_workspace_size": (_sz, [_BP, _i32, _i64, _i64]),
+    "rbx_embed_csr_fwd_long": (ctypes.c_int, [_BP, _i32, _i64, _i64, _P, _i64, _P, _P, _sz, _P, _P]),
+    "rbx_embed_csr_fwd_weighted_long": (ctypes.c_int, [_BP, _i32, _i64, _i64, _PP, _P, _i64, _P, _sz, _P, _P]),
+    "rbx_embed_csr_weight_grad_long": (ctypes.c_int, [_BP, _i32, _i64, _i64, _P, _i64, _PP, _P, _sz, _P, _P]),
     "rbx_shard_int_chunk": (_sz, [_GP]),
     "rbx_shard_float_rows": (_sz, [_GP]),
     "rbx_shard_route_workspace_size": (_sz, [_GP, _i32]),

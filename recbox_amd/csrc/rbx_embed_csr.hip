@@ -75,6 +75,94 @@ __device__ __forceinline__ void bag_range(const BagK& fd, long long b, int* begi
   *bad = (lo != o0) || (hi != o1);
 }
 
+// ---- the long-bag form: a bag of >= T ids is cut into segments of RBX_CSR_SEGMENT ids, a wave per segment ---------------
+// MODE of the three bag-walking kernels: kWalk = a lane group per bag whatever its length (the existing entry points);
+// kHandOff = the same, but a group whose bag has L >= T appends a record to the workspace and neither sweeps nor stores;
+// kSegments = a wave task is one segment of a recorded bag: the wave's lane groups take consecutive S / (64 / G) ids each
+// and walk them exactly as a lane group walks a bag (chunk / list / U / R), the closing butterfly runs over the whole wave,
+// and the partial row (and count) goes to the workspace.  csr_long_finish_kernel sums a bag's partials in ascending
+// segment order: a fixed order, so two runs give the same bits.
+// One 64-bit atomicAdd per long bag hands out (record index, first segment slot) together: records are ordered by their
+// first slot and a segment task finds its bag by binary search.  Capacities are static (long_plan); well-formed offsets
+// cannot exceed them, and a bag whose indices come back beyond either is walked by its lane group in that same launch.
+constexpr int kWalk = 0, kHandOff = 1, kSegments = 2;
+constexpr int kSeg = RBX_CSR_SEGMENT;
+
+struct LongRec { int desc, cls, bag, begin, end, seg0, r0, r1; };   // 32 B; begin == end: refused (walked by its lane group)
+struct LongArgs {
+  unsigned long long* hdr;  // high word: long bags, low word: segments handed out
+  LongRec* recs;            // [cap_bags]
+  float* part;              // [cap_segs][pstride] partial rows
+  float* pcnt;              // [cap_segs] partial counts of the mean pools
+  int T, cap_bags, cap_segs, pstride;
+  int cls;                  // the launch's class (float4 | scalar, unweighted | weighted): a segment kernel takes its own
+};
+
+// one lane of the group; returns 1 when the bag now belongs to the segment kernel
+__device__ __forceinline__ int long_append(const LongArgs& la, int desc, long long bag, int begin, int end) {
+  const unsigned nseg = static_cast<unsigned>((end - begin + kSeg - 1) / kSeg);
+  const unsigned long long cur = __hip_atomic_load(la.hdr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if ((cur >> 32) >= static_cast<unsigned long long>(la.cap_bags) ||
+      (cur & 0xFFFFFFFFull) + nseg > static_cast<unsigned long long>(la.cap_segs))
+    return 0;                                             // already full (overlapping bags): the counters stop growing
+  const unsigned long long old = atomicAdd(la.hdr, (1ull << 32) | nseg);
+  const unsigned long long bi = old >> 32, s0 = old & 0xFFFFFFFFull;
+  if (bi >= static_cast<unsigned long long>(la.cap_bags)) return 0;
+  const bool ok = s0 + nseg <= static_cast<unsigned long long>(la.cap_segs);
+  LongRec r;
+  r.desc = desc;
+  r.cls = la.cls;
+  r.bag = static_cast<int>(bag);
+  r.begin = ok ? begin : 0;
+  r.end = ok ? end : 0;
+  r.seg0 = static_cast<int>(s0 < 0x7FFFFFFFull ? s0 : 0x7FFFFFFFull);
+  r.r0 = r.r1 = 0;
+  la.recs[bi] = r;
+  return ok ? 1 : 0;
+}
+
+// the counts a later kernel of the call reads, clamped to the capacities
+__device__ __forceinline__ void long_counts(const LongArgs& la, int* n_bags, long long* n_segs) {
+  const unsigned long long h = *la.hdr;
+  const unsigned long long nb = h >> 32, ns = h & 0xFFFFFFFFull;
+  *n_bags = static_cast<int>(nb < static_cast<unsigned long long>(la.cap_bags) ? nb : la.cap_bags);
+  *n_segs = (*n_bags == 0) ? 0 : static_cast<long long>(ns < static_cast<unsigned long long>(la.cap_segs) ? ns : la.cap_segs);
+}
+
+// the record of segment slot s (wave-uniform: the fields come back in SGPRs): the last one with seg0 <= s
+__device__ __forceinline__ LongRec long_find(const LongArgs& la, int n_bags, long long s) {
+  int lo = 0, hi = n_bags - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (la.recs[mid].seg0 <= s) lo = mid; else hi = mid - 1;
+  }
+  const LongRec v = la.recs[lo];
+  LongRec r;
+  r.desc = __builtin_amdgcn_readfirstlane(v.desc);
+  r.cls = __builtin_amdgcn_readfirstlane(v.cls);
+  r.bag = __builtin_amdgcn_readfirstlane(v.bag);
+  r.begin = __builtin_amdgcn_readfirstlane(v.begin);
+  r.end = __builtin_amdgcn_readfirstlane(v.end);
+  r.seg0 = __builtin_amdgcn_readfirstlane(v.seg0);
+  r.r0 = r.r1 = 0;
+  return r;
+}
+
+// [begin, end) of lane group `gi` (of GPW per wave) inside segment slot s of record r; empty when the slot is not r's
+template <int GPW>
+__device__ __forceinline__ void long_sub_range(const LongRec& r, long long s, int gi, int* begin, int* end) {
+  constexpr int kSub = kSeg / GPW;                        // a multiple of the group's chunk 4 * G (G = 64 / GPW >= 16)
+  const long long seg_b = static_cast<long long>(r.begin) + (s - r.seg0) * kSeg;
+  const long long seg_e = seg_b + kSeg < r.end ? seg_b + kSeg : r.end;
+  long long gb = seg_b + static_cast<long long>(gi) * kSub;
+  if (s < r.seg0 || gb > seg_e) gb = seg_e;
+  if (gb < r.begin) gb = r.begin;                         // (an empty record: begin == end)
+  long long ge = gb + kSub < seg_e ? gb + kSub : seg_e;
+  if (ge < gb) ge = gb;
+  *begin = static_cast<int>(gb);
+  *end = static_cast<int>(ge);
+}
+
 // ---- forward -------------------------------------------------------------------------------------------------------
 // The constants below are embed_seq_kernel's (RBX_SEQ_WAVES, RBX_SEQ_U, RBX_SEQ_IPL16, RBX_SEQ_SG16 / _SG32): the
 // bit-equality of the two paths rests on equal chunks, batches and sub-group counts.
@@ -82,11 +170,11 @@ constexpr int kCsrWaves = 4;
 constexpr int kCsrU = 4;               // rows in flight per lane
 constexpr int kCsrIpl = 4;             // ids per lane per chunk
 
-template <int G, int R, int NV, bool VEC>
+template <int G, int R, int NV, bool VEC, int MODE = kWalk>
 __global__ __launch_bounds__(256, kCsrWaves) void embed_csr_kernel(const BagPack P, const int F, const long long B,
                                                                    float* __restrict__ out, const long long stride_b,
                                                                    float* __restrict__ row_scale,
-                                                                   int* __restrict__ status) {
+                                                                   int* __restrict__ status, const LongArgs LA) {
   constexpr int W = G / R;                                // lanes that hold one row
   using Frag = RowFrag<W, NV, VEC>;
   constexpr int U = kCsrU;
@@ -104,22 +192,42 @@ __global__ __launch_bounds__(256, kCsrWaves) void embed_csr_kernel(const BagPack
   volatile int* my_id = s_id[gidx];
   constexpr int GPW = 64 / G;
   const long long tasks_per_bag = (B + GPW - 1) / GPW;
-  const long long ntasks = tasks_per_bag * F;
+  long long ntasks = tasks_per_bag * F;
+  int n_long = 0;
+  if constexpr (MODE == kSegments) long_counts(LA, &n_long, &ntasks);    // a wave task = one segment slot
   const long long nwaves = static_cast<long long>(gridDim.x) * 4;
   for (long long t = static_cast<long long>(blockIdx.x) * 4 + threadIdx.x / 64; t < ntasks; t += nwaves) {
-    const int f = __builtin_amdgcn_readfirstlane(static_cast<int>(t / tasks_per_bag));
-    const long long b = (t - f * tasks_per_bag) * GPW + (threadIdx.x & 63) / G;
-    const bool alive = b < B;
+    int f, begin = 0, end = 0;
+    long long b;
+    bool alive;
+    if constexpr (MODE == kSegments) {
+      const LongRec rec = long_find(LA, n_long, t);
+      if (rec.cls != LA.cls || static_cast<unsigned>(rec.desc) >= static_cast<unsigned>(F)) continue;
+      f = rec.desc;
+      b = rec.bag;
+      alive = true;
+      long_sub_range<GPW>(rec, t, (threadIdx.x & 63) / G, &begin, &end);
+    } else {
+      f = __builtin_amdgcn_readfirstlane(static_cast<int>(t / tasks_per_bag));
+      b = (t - f * tasks_per_bag) * GPW + (threadIdx.x & 63) / G;
+      alive = b < B;
+    }
     const BagK& fd = P.f[f];
     const int pool = fd.pool, dim = fd.dim, dt = fd.idx_dtype;
     const bool id_pool = (pool == RBX_POOL_MEAN_ID || pool == RBX_POOL_SUM_ID);
-    int begin = 0, end = 0;
-    if (alive) {
+    if (MODE != kSegments && alive) {
       bool bad;
       bag_range(fd, b, &begin, &end, &bad);
       if (bad && lane_g == 0 && status != nullptr) atomicOr(status, kStatusBadOffsets);
     }
-    const int L = end - begin;
+    int L = end - begin;
+    bool handed = false;                                  // the bag went to the segment kernel: no sweep, no store here
+    if constexpr (MODE == kHandOff) {
+      int took = 0;
+      if (alive && lane_g == 0 && L >= LA.T) took = long_append(LA, fd.slot, b, begin, end);
+      handed = __shfl(took, 0, G) != 0;
+      if (handed) L = 0;
+    }
     float* dst = out + b * stride_b + fd.out_off;
     Frag acc;
     acc.zero();
@@ -184,11 +292,18 @@ __global__ __launch_bounds__(256, kCsrWaves) void embed_csr_kernel(const BagPack
       __builtin_amdgcn_wave_barrier();
     }
 #pragma unroll
-    for (int o = W; o < G; o <<= 1) {                     // every lane joins the butterfly
+    for (int o = W; o < (MODE == kSegments ? 64 : G); o <<= 1) {   // every lane joins the butterfly (segments: the whole wave)
       acc.xor_add(o);
       count += __shfl_xor(count, o, 64);
     }
-    if (!alive || sub != 0) continue;
+    if constexpr (MODE == kSegments) {                    // t < cap_segs (long_counts); the finish applies the mean scale
+      if ((threadIdx.x & 63) < W) {
+        acc.store(LA.part + t * LA.pstride, dim, lane_w);
+        if (lane_w == 0) LA.pcnt[t] = count;
+      }
+      continue;
+    }
+    if (!alive || sub != 0 || handed) continue;
     if (pool == RBX_POOL_MEAN_VALUE || pool == RBX_POOL_MEAN_ID) {
       const float inv = 1.0f / (count + fd.eps);          // an empty bag: 0 * (1 / eps) = 0
       acc.scale(inv);
@@ -202,11 +317,11 @@ __global__ __launch_bounds__(256, kCsrWaves) void embed_csr_kernel(const BagPack
 // embed_csr_kernel for the sum pools with one factor per lookup: the weight is loaded in the id's coalesced sweep,
 // compacted beside the id (a second list: 8 KB of LDS per workgroup) and multiplied into the row before the add.  Chunk
 // size, list order, U and R are embed_csr_kernel's, and x * 1.0f is x: all-ones weights give that kernel's bits.
-template <int G, int R, int NV, bool VEC>
+template <int G, int R, int NV, bool VEC, int MODE = kWalk>
 __global__ __launch_bounds__(256, kCsrWaves) void embed_csr_weighted_kernel(const BagPack P, const BagWeights WP, const int F,
                                                                             const long long B, float* __restrict__ out,
                                                                             const long long stride_b,
-                                                                            int* __restrict__ status) {
+                                                                            int* __restrict__ status, const LongArgs LA) {
   constexpr int W = G / R;                                // lanes that hold one row
   using Frag = RowFrag<W, NV, VEC>;
   constexpr int U = kCsrU;
@@ -226,23 +341,43 @@ __global__ __launch_bounds__(256, kCsrWaves) void embed_csr_weighted_kernel(cons
   volatile float* my_w = s_w[gidx];
   constexpr int GPW = 64 / G;
   const long long tasks_per_bag = (B + GPW - 1) / GPW;
-  const long long ntasks = tasks_per_bag * F;
+  long long ntasks = tasks_per_bag * F;
+  int n_long = 0;
+  if constexpr (MODE == kSegments) long_counts(LA, &n_long, &ntasks);    // a wave task = one segment slot
   const long long nwaves = static_cast<long long>(gridDim.x) * 4;
   for (long long t = static_cast<long long>(blockIdx.x) * 4 + threadIdx.x / 64; t < ntasks; t += nwaves) {
-    const int f = __builtin_amdgcn_readfirstlane(static_cast<int>(t / tasks_per_bag));
-    const long long b = (t - f * tasks_per_bag) * GPW + (threadIdx.x & 63) / G;
-    const bool alive = b < B;
+    int f, begin = 0, end = 0;
+    long long b;
+    bool alive;
+    if constexpr (MODE == kSegments) {
+      const LongRec rec = long_find(LA, n_long, t);
+      if (rec.cls != LA.cls || static_cast<unsigned>(rec.desc) >= static_cast<unsigned>(F)) continue;
+      f = rec.desc;
+      b = rec.bag;
+      alive = true;
+      long_sub_range<GPW>(rec, t, (threadIdx.x & 63) / G, &begin, &end);
+    } else {
+      f = __builtin_amdgcn_readfirstlane(static_cast<int>(t / tasks_per_bag));
+      b = (t - f * tasks_per_bag) * GPW + (threadIdx.x & 63) / G;
+      alive = b < B;
+    }
     const BagK& fd = P.f[f];
     const float* __restrict__ wsrc = WP.w[f];
     const int dim = fd.dim, dt = fd.idx_dtype;
     const bool id_pool = fd.pool == RBX_POOL_SUM_ID;
-    int begin = 0, end = 0;
-    if (alive) {
+    if (MODE != kSegments && alive) {
       bool bad;
       bag_range(fd, b, &begin, &end, &bad);
       if (bad && lane_g == 0 && status != nullptr) atomicOr(status, kStatusBadOffsets);
     }
-    const int L = end - begin;
+    int L = end - begin;
+    bool handed = false;
+    if constexpr (MODE == kHandOff) {
+      int took = 0;
+      if (alive && lane_g == 0 && L >= LA.T) took = long_append(LA, fd.slot, b, begin, end);
+      handed = __shfl(took, 0, G) != 0;
+      if (handed) L = 0;
+    }
     Frag acc;
     acc.zero();
     int Lmax = L;                                         // wave-uniform number of chunks: the longest bag of the wave
@@ -308,8 +443,12 @@ __global__ __launch_bounds__(256, kCsrWaves) void embed_csr_weighted_kernel(cons
       __builtin_amdgcn_wave_barrier();
     }
 #pragma unroll
-    for (int o = W; o < G; o <<= 1) acc.xor_add(o);       // every lane joins the butterfly
-    if (!alive || sub != 0) continue;
+    for (int o = W; o < (MODE == kSegments ? 64 : G); o <<= 1) acc.xor_add(o);   // every lane joins the butterfly
+    if constexpr (MODE == kSegments) {
+      if ((threadIdx.x & 63) < W) acc.store(LA.part + t * LA.pstride, dim, lane_w);
+      continue;
+    }
+    if (!alive || sub != 0 || handed) continue;
     acc.store(out + b * stride_b + fd.out_off, dim, lane_w);
   }
 }
@@ -335,11 +474,11 @@ __device__ __forceinline__ float row_dot(const RowFrag<W, NV, false>& a, const R
   return s;
 }
 
-template <int G, int R, int NV, bool VEC>
+template <int G, int R, int NV, bool VEC, int MODE = kWalk>
 __global__ __launch_bounds__(256, kCsrWaves) void csr_weight_grad_kernel(const BagPack P, const BagWeightGrads DW, const int F,
                                                                          const long long B, const float* __restrict__ dout,
                                                                          const long long stride_b,
-                                                                         int* __restrict__ status) {
+                                                                         int* __restrict__ status, const LongArgs LA) {
   constexpr int W = G / R;
   using Frag = RowFrag<W, NV, VEC>;
   constexpr int U = kCsrU;
@@ -359,26 +498,46 @@ __global__ __launch_bounds__(256, kCsrWaves) void csr_weight_grad_kernel(const B
   volatile int* my_pos = s_pos[gidx];
   constexpr int GPW = 64 / G;
   const long long tasks_per_bag = (B + GPW - 1) / GPW;
-  const long long ntasks = tasks_per_bag * F;
+  long long ntasks = tasks_per_bag * F;
+  int n_long = 0;
+  if constexpr (MODE == kSegments) long_counts(LA, &n_long, &ntasks);    // a wave task = one segment slot
   const long long nwaves = static_cast<long long>(gridDim.x) * 4;
   for (long long t = static_cast<long long>(blockIdx.x) * 4 + threadIdx.x / 64; t < ntasks; t += nwaves) {
-    const int f = __builtin_amdgcn_readfirstlane(static_cast<int>(t / tasks_per_bag));
-    const long long b = (t - f * tasks_per_bag) * GPW + (threadIdx.x & 63) / G;
-    const bool alive = b < B;
+    int f, begin = 0, end = 0;
+    long long b;
+    bool alive;
+    if constexpr (MODE == kSegments) {
+      const LongRec rec = long_find(LA, n_long, t);
+      if (rec.cls != LA.cls || static_cast<unsigned>(rec.desc) >= static_cast<unsigned>(F)) continue;
+      f = rec.desc;
+      b = rec.bag;
+      alive = true;
+      long_sub_range<GPW>(rec, t, (threadIdx.x & 63) / G, &begin, &end);
+    } else {
+      f = __builtin_amdgcn_readfirstlane(static_cast<int>(t / tasks_per_bag));
+      b = (t - f * tasks_per_bag) * GPW + (threadIdx.x & 63) / G;
+      alive = b < B;
+    }
     const BagK& fd = P.f[f];
     float* __restrict__ dw = DW.dw[f];
     const int dim = fd.dim, dt = fd.idx_dtype;
     const bool id_pool = fd.pool == RBX_POOL_SUM_ID;
-    int begin = 0, end = 0;
     Frag dy;
     dy.zero();
     if (alive) {
-      bool bad;
-      bag_range(fd, b, &begin, &end, &bad);
-      if (bad && lane_g == 0 && status != nullptr) atomicOr(status, kStatusBadOffsets);
+      if constexpr (MODE != kSegments) {
+        bool bad;
+        bag_range(fd, b, &begin, &end, &bad);
+        if (bad && lane_g == 0 && status != nullptr) atomicOr(status, kStatusBadOffsets);
+      }
       dy.load(dout + b * stride_b + fd.out_off, dim, lane_w);
     }
-    const int L = end - begin;
+    int L = end - begin;
+    if constexpr (MODE == kHandOff) {                     // nothing to store at the end: a handed-over bag is an empty one here
+      int took = 0;
+      if (alive && lane_g == 0 && L >= LA.T) took = long_append(LA, fd.slot, b, begin, end);
+      if (__shfl(took, 0, G) != 0) L = 0;
+    }
     int Lmax = L;
 #pragma unroll
     for (int o = 32; o >= G && o > 0; o >>= 1) {
@@ -441,70 +600,77 @@ __global__ __launch_bounds__(256, kCsrWaves) void csr_weight_grad_kernel(const B
   }
 }
 
-template <int G, int NV, bool VEC>
+// the segment kernels' grid: fixed, grid-striding over the segment count in the workspace header
+constexpr int kSegBlocks = kCUs * 4;
+
+template <int G, int NV, bool VEC, int MODE = kWalk>
 static int launch_csr(const BagPack& pack, int F, int64_t B, float* out, int64_t stride_b, float* row_scale, int* status,
-                      hipStream_t s) {
+                      hipStream_t s, const LongArgs& la = LongArgs{}) {
   constexpr int SG = (G <= 8) ? 16 : ((G == 16) ? 32 : 64);    // lanes per bag: launch_fwd's rule for sequences
   long long blocks = ((B + 64 / SG - 1) / (64 / SG) * F + 3) / 4;   // 4 wave tasks per workgroup
   const long long cap = static_cast<long long>(kCUs) * 64;
   if (blocks > cap) blocks = cap;
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL((embed_csr_kernel<SG, SG / G, NV, VEC>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, pack, F,
-                     static_cast<long long>(B), out, static_cast<long long>(stride_b), row_scale, status);
+  if (MODE == kSegments) blocks = kSegBlocks;
+  hipLaunchKernelGGL((embed_csr_kernel<SG, SG / G, NV, VEC, MODE>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, pack,
+                     F, static_cast<long long>(B), out, static_cast<long long>(stride_b), row_scale, status, la);
   return check_launch("embed_csr_kernel");
 }
 
-template <bool VEC>
+template <bool VEC, int MODE = kWalk>
 static int dispatch_csr(int units, const BagPack& pack, int F, int64_t B, float* out, int64_t stride_b, float* row_scale,
-                        int* status, hipStream_t s) {
+                        int* status, hipStream_t s, const LongArgs& la = LongArgs{}) {
   switch (pow2_ceil(units)) {
-    case 1: return launch_csr<1, 1, VEC>(pack, F, B, out, stride_b, row_scale, status, s);
-    case 2: return launch_csr<2, 1, VEC>(pack, F, B, out, stride_b, row_scale, status, s);
-    case 4: return launch_csr<4, 1, VEC>(pack, F, B, out, stride_b, row_scale, status, s);
-    case 8: return launch_csr<8, 1, VEC>(pack, F, B, out, stride_b, row_scale, status, s);
-    case 16: return launch_csr<16, 1, VEC>(pack, F, B, out, stride_b, row_scale, status, s);
-    case 32: return launch_csr<32, 1, VEC>(pack, F, B, out, stride_b, row_scale, status, s);
-    case 64: return launch_csr<64, 1, VEC>(pack, F, B, out, stride_b, row_scale, status, s);
-    case 128: return launch_csr<64, 2, VEC>(pack, F, B, out, stride_b, row_scale, status, s);
-    case 256: return launch_csr<64, 4, VEC>(pack, F, B, out, stride_b, row_scale, status, s);
+    case 1: return launch_csr<1, 1, VEC, MODE>(pack, F, B, out, stride_b, row_scale, status, s, la);
+    case 2: return launch_csr<2, 1, VEC, MODE>(pack, F, B, out, stride_b, row_scale, status, s, la);
+    case 4: return launch_csr<4, 1, VEC, MODE>(pack, F, B, out, stride_b, row_scale, status, s, la);
+    case 8: return launch_csr<8, 1, VEC, MODE>(pack, F, B, out, stride_b, row_scale, status, s, la);
+    case 16: return launch_csr<16, 1, VEC, MODE>(pack, F, B, out, stride_b, row_scale, status, s, la);
+    case 32: return launch_csr<32, 1, VEC, MODE>(pack, F, B, out, stride_b, row_scale, status, s, la);
+    case 64: return launch_csr<64, 1, VEC, MODE>(pack, F, B, out, stride_b, row_scale, status, s, la);
+    case 128: return launch_csr<64, 2, VEC, MODE>(pack, F, B, out, stride_b, row_scale, status, s, la);
+    case 256: return launch_csr<64, 4, VEC, MODE>(pack, F, B, out, stride_b, row_scale, status, s, la);
     default: return fail(RBX_ERR_UNSUPPORTED, "embedding dim too large for one lane group (units=%d)", units);
   }
 }
 
 // launch_csr / dispatch_csr for the two kernels of the weighted path: GRAD = false the weighted forward (writes `out`),
 // GRAD = true the weight gradient (reads `dout`, writes through `dw`)
-template <bool GRAD, int G, int NV, bool VEC>
+template <bool GRAD, int G, int NV, bool VEC, int MODE = kWalk>
 static int launch_csr_weighted(const BagPack& pack, const BagWeights& w, const BagWeightGrads& dw, int F, int64_t B,
-                               float* out, const float* dout, int64_t stride_b, int* status, hipStream_t s) {
+                               float* out, const float* dout, int64_t stride_b, int* status, hipStream_t s,
+                               const LongArgs& la = LongArgs{}) {
   constexpr int SG = (G <= 8) ? 16 : ((G == 16) ? 32 : 64);
   long long blocks = ((B + 64 / SG - 1) / (64 / SG) * F + 3) / 4;
   const long long cap = static_cast<long long>(kCUs) * 64;
   if (blocks > cap) blocks = cap;
   if (blocks < 1) blocks = 1;
+  if (MODE == kSegments) blocks = kSegBlocks;
   if constexpr (GRAD) {
-    hipLaunchKernelGGL((csr_weight_grad_kernel<SG, SG / G, NV, VEC>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, pack,
-                       dw, F, static_cast<long long>(B), dout, static_cast<long long>(stride_b), status);
+    hipLaunchKernelGGL((csr_weight_grad_kernel<SG, SG / G, NV, VEC, MODE>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s,
+                       pack, dw, F, static_cast<long long>(B), dout, static_cast<long long>(stride_b), status, la);
     return check_launch("csr_weight_grad_kernel");
   } else {
-    hipLaunchKernelGGL((embed_csr_weighted_kernel<SG, SG / G, NV, VEC>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s,
-                       pack, w, F, static_cast<long long>(B), out, static_cast<long long>(stride_b), status);
+    hipLaunchKernelGGL((embed_csr_weighted_kernel<SG, SG / G, NV, VEC, MODE>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0,
+                       s, pack, w, F, static_cast<long long>(B), out, static_cast<long long>(stride_b), status, la);
     return check_launch("embed_csr_weighted_kernel");
   }
 }
 
-template <bool GRAD, bool VEC>
+template <bool GRAD, bool VEC, int MODE = kWalk>
 static int dispatch_csr_weighted(int units, const BagPack& pack, const BagWeights& w, const BagWeightGrads& dw, int F, int64_t B,
-                                 float* out, const float* dout, int64_t stride_b, int* status, hipStream_t s) {
+                                 float* out, const float* dout, int64_t stride_b, int* status, hipStream_t s,
+                                 const LongArgs& la = LongArgs{}) {
   switch (pow2_ceil(units)) {
-    case 1: return launch_csr_weighted<GRAD, 1, 1, VEC>(pack, w, dw, F, B, out, dout, stride_b, status, s);
-    case 2: return launch_csr_weighted<GRAD, 2, 1, VEC>(pack, w, dw, F, B, out, dout, stride_b, status, s);
-    case 4: return launch_csr_weighted<GRAD, 4, 1, VEC>(pack, w, dw, F, B, out, dout, stride_b, status, s);
-    case 8: return launch_csr_weighted<GRAD, 8, 1, VEC>(pack, w, dw, F, B, out, dout, stride_b, status, s);
-    case 16: return launch_csr_weighted<GRAD, 16, 1, VEC>(pack, w, dw, F, B, out, dout, stride_b, status, s);
-    case 32: return launch_csr_weighted<GRAD, 32, 1, VEC>(pack, w, dw, F, B, out, dout, stride_b, status, s);
-    case 64: return launch_csr_weighted<GRAD, 64, 1, VEC>(pack, w, dw, F, B, out, dout, stride_b, status, s);
-    case 128: return launch_csr_weighted<GRAD, 64, 2, VEC>(pack, w, dw, F, B, out, dout, stride_b, status, s);
-    case 256: return launch_csr_weighted<GRAD, 64, 4, VEC>(pack, w, dw, F, B, out, dout, stride_b, status, s);
+    case 1: return launch_csr_weighted<GRAD, 1, 1, VEC, MODE>(pack, w, dw, F, B, out, dout, stride_b, status, s, la);
+    case 2: return launch_csr_weighted<GRAD, 2, 1, VEC, MODE>(pack, w, dw, F, B, out, dout, stride_b, status, s, la);
+    case 4: return launch_csr_weighted<GRAD, 4, 1, VEC, MODE>(pack, w, dw, F, B, out, dout, stride_b, status, s, la);
+    case 8: return launch_csr_weighted<GRAD, 8, 1, VEC, MODE>(pack, w, dw, F, B, out, dout, stride_b, status, s, la);
+    case 16: return launch_csr_weighted<GRAD, 16, 1, VEC, MODE>(pack, w, dw, F, B, out, dout, stride_b, status, s, la);
+    case 32: return launch_csr_weighted<GRAD, 32, 1, VEC, MODE>(pack, w, dw, F, B, out, dout, stride_b, status, s, la);
+    case 64: return launch_csr_weighted<GRAD, 64, 1, VEC, MODE>(pack, w, dw, F, B, out, dout, stride_b, status, s, la);
+    case 128: return launch_csr_weighted<GRAD, 64, 2, VEC, MODE>(pack, w, dw, F, B, out, dout, stride_b, status, s, la);
+    case 256: return launch_csr_weighted<GRAD, 64, 4, VEC, MODE>(pack, w, dw, F, B, out, dout, stride_b, status, s, la);
     default: return fail(RBX_ERR_UNSUPPORTED, "embedding dim too large for one lane group (units=%d)", units);
   }
 }
@@ -817,6 +983,184 @@ static int check_no_trained_mean(const rbx_bag_t* bags, int n, const char* who) 
   return RBX_OK;
 }
 
+// ---- the long-bag form, host side and finish ---------------------------------------------------------------------------
+// A wave per recorded bag: the partial rows of its segments are summed in ascending slot order, the mean pools get
+// 1 / (count + eps) over the partial counts summed the same way, and the row and row_scale[slot * B + bag] go where the
+// lane-group kernel would have put them.  P holds every descriptor of the call by index (LongRec::desc).
+__global__ __launch_bounds__(256) void csr_long_finish_kernel(const BagPack P, const int F, const long long B,
+                                                              float* __restrict__ out, const long long stride_b,
+                                                              float* __restrict__ row_scale, const LongArgs LA) {
+  int n_long;
+  long long n_segs;
+  long_counts(LA, &n_long, &n_segs);
+  const int lane = threadIdx.x & 63;
+  for (long long r = static_cast<long long>(blockIdx.x) * 4 + threadIdx.x / 64; r < n_long;
+       r += static_cast<long long>(gridDim.x) * 4) {
+    const LongRec rec = LA.recs[r];
+    if (rec.end <= rec.begin || static_cast<unsigned>(rec.desc) >= static_cast<unsigned>(F)) continue;   // refused: walked in place
+    const long long nseg = (static_cast<long long>(rec.end) - rec.begin + kSeg - 1) / kSeg;
+    if (rec.seg0 < 0 || rec.seg0 + nseg > n_segs || rec.bag < 0 || rec.bag >= B) continue;              // (long_append checked)
+    const BagK& fd = P.f[rec.desc];
+    const bool mean = fd.pool == RBX_POOL_MEAN_VALUE || fd.pool == RBX_POOL_MEAN_ID;
+    float inv = 1.0f;
+    if (mean) {
+      float count = 0.f;
+      for (long long j = 0; j < nseg; ++j) count += LA.pcnt[rec.seg0 + j];
+      inv = 1.0f / (count + fd.eps);
+      if (row_scale != nullptr && lane == 0) row_scale[static_cast<long long>(fd.slot) * B + rec.bag] = inv;
+    }
+    float* dst = out + rec.bag * stride_b + fd.out_off;
+    const float* src = LA.part + static_cast<long long>(rec.seg0) * LA.pstride;
+    for (int d = lane; d < fd.dim; d += 64) {
+      float a = 0.f;
+      for (long long j = 0; j < nseg; ++j) a += src[j * LA.pstride + d];
+      dst[d] = mean ? a * inv : a;
+    }
+  }
+}
+
+// Workspace of the long-bag calls: [header 256 B | records | partial rows | partial counts], sized from static values.
+// Well-formed offsets give at most nnz_i / T bags of >= T ids in descriptor i (and at most `batch`), and their segments
+// number sum(ceil(L / S)) <= nnz_i / S + that many.
+struct LongPlan {
+  int T = 0, cap_bags = 0, cap_segs = 0, pstride = 4;
+  size_t off_recs = 0, off_part = 0, off_cnt = 0, bytes = 0;
+};
+constexpr size_t kLongHeader = 256;
+
+static int long_plan(const rbx_bag_t* bags, int n, int64_t batch, int64_t threshold, LongPlan* lp) {
+  if (bags == nullptr) return fail(RBX_ERR_INVALID, "bags is NULL");
+  if (n <= 0 || n > RBX_MAX_BAGS) return fail(RBX_ERR_INVALID, "n_bags=%d not in [1,%d]", n, RBX_MAX_BAGS);
+  if (batch < 0) return fail(RBX_ERR_INVALID, "negative batch");
+  if (batch > static_cast<int64_t>(kLocalMask)) return fail(RBX_ERR_UNSUPPORTED, "batch=%lld exceeds 2^26 bags per call", (long long)batch);
+  if (threshold < 0) return fail(RBX_ERR_INVALID, "negative long_threshold");
+  long long cap_bags = 0, cap_segs = 0;
+  int dim = 1;
+  for (int i = 0; i < n; ++i) {
+    const rbx_bag_t& g = bags[i];
+    if (g.dim <= 0 || g.dim > 1024) return fail(RBX_ERR_UNSUPPORTED, "bag %d: dim=%d not in [1,1024]", i, g.dim);
+    if (g.nnz < 0 || g.nnz > static_cast<int64_t>(kLocalMask))
+      return fail(RBX_ERR_UNSUPPORTED, "bag %d: nnz=%lld not in [0, 2^26]", i, (long long)g.nnz);
+    if (g.dim > dim) dim = g.dim;
+    if (threshold == 0) continue;
+    const long long most = g.nnz / threshold < batch ? g.nnz / threshold : batch;
+    cap_bags += most;
+    cap_segs += g.nnz / kSeg + most;
+  }
+  if (cap_bags == 0) cap_segs = 0;
+  lp->T = threshold > INT_MAX ? INT_MAX : static_cast<int>(threshold);
+  lp->cap_bags = static_cast<int>(cap_bags);             // <= 32 * 2^26 / T
+  lp->cap_segs = static_cast<int>(cap_segs);             // <= 32 * 2^26 / 256 + cap_bags
+  lp->pstride = (dim + 3) / 4 * 4;
+  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+  lp->off_recs = kLongHeader;
+  lp->off_part = lp->off_recs + up(static_cast<size_t>(cap_bags) * sizeof(LongRec));
+  lp->off_cnt = lp->off_part + up(static_cast<size_t>(cap_segs) * lp->pstride * 4);
+  lp->bytes = lp->off_cnt + up(static_cast<size_t>(cap_segs) * 4);
+  return RBX_OK;
+}
+
+static LongArgs long_args(const LongPlan& lp, void* ws) {
+  char* base = static_cast<char*>(ws);
+  LongArgs la;
+  la.hdr = reinterpret_cast<unsigned long long*>(base);
+  la.recs = reinterpret_cast<LongRec*>(base + lp.off_recs);
+  la.part = reinterpret_cast<float*>(base + lp.off_part);
+  la.pcnt = reinterpret_cast<float*>(base + lp.off_cnt);
+  la.T = lp.T;
+  la.cap_bags = lp.cap_bags;
+  la.cap_segs = lp.cap_segs;
+  la.pstride = lp.pstride;
+  la.cls = 0;
+  return la;
+}
+
+// plan + workspace check + the memset node that clears the header; *on: some bag of the call can take the long form
+static int long_begin(const rbx_bag_t* bags, int n, int64_t batch, int64_t threshold, void* ws, size_t ws_bytes, hipStream_t s,
+                      LongPlan* lp, bool* on) {
+  int rc = long_plan(bags, n, batch, threshold, lp);
+  if (rc != RBX_OK) return rc;
+  if (ws == nullptr || ws_bytes < lp->bytes)
+    return fail(RBX_ERR_WORKSPACE, "workspace %zu B < required %zu B", ws == nullptr ? size_t(0) : ws_bytes, lp->bytes);
+  if (hipMemsetAsync(ws, 0, kLongHeader, s) != hipSuccess) return fail(RBX_ERR_LAUNCH, "clearing the long-bag header failed");
+  *on = lp->cap_bags > 0 && batch > 0;
+  return RBX_OK;
+}
+
+// the forward of both long entry points: d_weights == NULL is rbx_embed_csr_fwd_long
+static int csr_fwd_long(const rbx_bag_t* bags, int n_bags, int64_t batch, int64_t threshold, const float* const* d_weights,
+                        bool weighted_call, float* d_out, int64_t out_stride_b, float* d_row_scale, void* d_workspace,
+                        size_t workspace_bytes, int* d_status, hipStream_t s) {
+  BagPack all;
+  int rc = pack_bags(bags, n_bags, batch, all.f);
+  if (rc != RBX_OK) return rc;
+  if (weighted_call) {
+    rc = check_weighted_pools(bags, n_bags, reinterpret_cast<const void* const*>(d_weights), "a weight array");
+    if (rc != RBX_OK) return rc;
+  }
+  if (batch > 0 && d_out == nullptr) return fail(RBX_ERR_INVALID, "d_out is NULL");
+  BagPack pack[4];
+  BagWeights wts[2], wall = {};
+  int cnt[4] = {0, 0, 0, 0}, units[4] = {1, 1, 1, 1};
+  for (int i = 0; i < n_bags; ++i) {
+    const bool vec = bag_vec_ok(bags[i], d_out, out_stride_b);
+    const float* w = d_weights != nullptr ? d_weights[i] : nullptr;
+    const int k = (vec ? 0 : 1) + (w != nullptr ? 2 : 0);
+    if (w != nullptr) wts[k - 2].w[cnt[k]] = w;
+    wall.w[i] = w;
+    pack[k].f[cnt[k]++] = all.f[i];
+    const int u = vec ? bags[i].dim / 4 : bags[i].dim;
+    if (u > units[k]) units[k] = u;
+  }
+  for (int k = 0; k < 4; ++k)
+    if (cnt[k] > 0 && pow2_ceil(units[k]) > 256)
+      return fail(RBX_ERR_UNSUPPORTED, "embedding dim too large for one lane group (%s units=%d)", k % 2 == 0 ? "float4" : "scalar",
+                  units[k]);
+  LongPlan lp;
+  bool on = false;
+  rc = long_begin(bags, n_bags, batch, threshold, d_workspace, workspace_bytes, s, &lp, &on);
+  if (rc != RBX_OK) return rc;
+  if (batch == 0) return RBX_OK;
+  LongArgs la = long_args(lp, d_workspace);
+  const BagWeightGrads none = {};
+  // lane-group kernels of every class first (they fill the list), then the classes' segment kernels, then one finish
+  for (int k = 0; k < 4; ++k) {
+    if (cnt[k] == 0) continue;
+    la.cls = k;
+    const bool vec = k % 2 == 0;
+    if (k < 2) {
+      if (!on) rc = vec ? dispatch_csr<true>(units[k], pack[k], cnt[k], batch, d_out, out_stride_b, d_row_scale, d_status, s)
+                        : dispatch_csr<false>(units[k], pack[k], cnt[k], batch, d_out, out_stride_b, d_row_scale, d_status, s);
+      else rc = vec ? dispatch_csr<true, kHandOff>(units[k], pack[k], cnt[k], batch, d_out, out_stride_b, d_row_scale, d_status, s, la)
+                    : dispatch_csr<false, kHandOff>(units[k], pack[k], cnt[k], batch, d_out, out_stride_b, d_row_scale, d_status, s, la);
+    } else {
+      const BagWeights& w = wts[k - 2];
+      if (!on) rc = vec ? dispatch_csr_weighted<false, true>(units[k], pack[k], w, none, cnt[k], batch, d_out, nullptr, out_stride_b, d_status, s)
+                        : dispatch_csr_weighted<false, false>(units[k], pack[k], w, none, cnt[k], batch, d_out, nullptr, out_stride_b, d_status, s);
+      else rc = vec ? dispatch_csr_weighted<false, true, kHandOff>(units[k], pack[k], w, none, cnt[k], batch, d_out, nullptr, out_stride_b, d_status, s, la)
+                    : dispatch_csr_weighted<false, false, kHandOff>(units[k], pack[k], w, none, cnt[k], batch, d_out, nullptr, out_stride_b, d_status, s, la);
+    }
+    if (rc != RBX_OK) return rc;
+  }
+  if (!on) return RBX_OK;
+  for (int k = 0; k < 4; ++k) {
+    if (cnt[k] == 0) continue;
+    la.cls = k;
+    switch (k) {
+      case 0: rc = dispatch_csr<true, kSegments>(units[k], all, n_bags, batch, d_out, out_stride_b, nullptr, d_status, s, la); break;
+      case 1: rc = dispatch_csr<false, kSegments>(units[k], all, n_bags, batch, d_out, out_stride_b, nullptr, d_status, s, la); break;
+      case 2: rc = dispatch_csr_weighted<false, true, kSegments>(units[k], all, wall, none, n_bags, batch, d_out, nullptr, out_stride_b, d_status, s, la); break;
+      default: rc = dispatch_csr_weighted<false, false, kSegments>(units[k], all, wall, none, n_bags, batch, d_out, nullptr, out_stride_b, d_status, s, la); break;
+    }
+    if (rc != RBX_OK) return rc;
+  }
+  long long fb = (static_cast<long long>(lp.cap_bags) + 3) / 4;
+  if (fb > kCUs * 2) fb = kCUs * 2;
+  hipLaunchKernelGGL(csr_long_finish_kernel, dim3(static_cast<unsigned>(fb)), dim3(256), 0, s, all, n_bags,
+                     static_cast<long long>(batch), d_out, static_cast<long long>(out_stride_b), d_row_scale, la);
+  return check_launch("csr_long_finish_kernel");
+}
+
 }  // namespace rbx
 
 extern "C" int rbx_embed_csr_fwd(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, float* d_out, int64_t out_stride_b,
@@ -1006,6 +1350,87 @@ extern "C" int rbx_embed_csr_weight_grad(const rbx_bag_t* bags, int32_t n_bags, 
                                                       d_status, s)
                   : dispatch_csr_weighted<true, false>(units[k], pack[k], none, dws[k], cnt[k], batch, nullptr, d_dout,
                                                        out_stride_b, d_status, s);
+    if (rc != RBX_OK) return rc;
+  }
+  return RBX_OK;
+}
+
+// ---- the long-bag form (see LongArgs) ----------------------------------------------------------------------------------
+extern "C" size_t rbx_embed_csr_fwd_long_workspace_size(const rbx_bag_t* bags, int32_t n_bags, int64_t batch,
+                                                        int64_t long_threshold) {
+  rbx::LongPlan lp;
+  if (rbx::long_plan(bags, n_bags, batch, long_threshold, &lp) != RBX_OK) return 0;
+  return lp.bytes;
+}
+
+extern "C" int rbx_embed_csr_fwd_long(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, int64_t long_threshold, float* d_out,
+                                      int64_t out_stride_b, float* d_row_scale, void* d_workspace, size_t workspace_bytes,
+                                      int32_t* d_status, void* stream) {
+  return rbx::csr_fwd_long(bags, n_bags, batch, long_threshold, nullptr, false, d_out, out_stride_b, d_row_scale, d_workspace,
+                           workspace_bytes, d_status, rbx::as_stream(stream));
+}
+
+extern "C" int rbx_embed_csr_fwd_weighted_long(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, int64_t long_threshold,
+                                               const float* const* d_weights, float* d_out, int64_t out_stride_b,
+                                               void* d_workspace, size_t workspace_bytes, int32_t* d_status, void* stream) {
+  return rbx::csr_fwd_long(bags, n_bags, batch, long_threshold, d_weights, true, d_out, out_stride_b, nullptr, d_workspace,
+                           workspace_bytes, d_status, rbx::as_stream(stream));
+}
+
+extern "C" int rbx_embed_csr_weight_grad_long(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, int64_t long_threshold,
+                                              const float* d_dout, int64_t out_stride_b, float* const* d_dweights,
+                                              void* d_workspace, size_t workspace_bytes, int32_t* d_status, void* stream) {
+  using namespace rbx;
+  BagPack all;
+  int rc = pack_bags(bags, n_bags, batch, all.f);
+  if (rc != RBX_OK) return rc;
+  if (d_dweights == nullptr) return fail(RBX_ERR_INVALID, "d_dweights is NULL");
+  rc = check_weighted_pools(bags, n_bags, reinterpret_cast<const void* const*>(d_dweights), "a weight gradient");
+  if (rc != RBX_OK) return rc;
+  if (batch > 0 && d_dout == nullptr) return fail(RBX_ERR_INVALID, "d_dout is NULL");
+  BagPack pack[2];
+  BagWeightGrads dws[2], dwall = {};
+  int cnt[2] = {0, 0}, units[2] = {1, 1};
+  for (int i = 0; i < n_bags; ++i) {
+    if (d_dweights[i] == nullptr) continue;
+    const bool vec = bag_vec_ok(bags[i], d_dout, out_stride_b);
+    const int k = vec ? 0 : 1;
+    dws[k].dw[cnt[k]] = d_dweights[i];
+    dwall.dw[i] = d_dweights[i];
+    pack[k].f[cnt[k]++] = all.f[i];
+    const int u = vec ? bags[i].dim / 4 : bags[i].dim;
+    if (u > units[k]) units[k] = u;
+  }
+  for (int k = 0; k < 2; ++k)
+    if (cnt[k] > 0 && pow2_ceil(units[k]) > 256)
+      return fail(RBX_ERR_UNSUPPORTED, "embedding dim too large for one lane group (%s units=%d)", k == 0 ? "float4" : "scalar",
+                  units[k]);
+  hipStream_t s = as_stream(stream);
+  LongPlan lp;
+  bool on = false;
+  rc = long_begin(bags, n_bags, batch, long_threshold, d_workspace, workspace_bytes, s, &lp, &on);
+  if (rc != RBX_OK) return rc;
+  for (int i = 0; i < n_bags; ++i)                          // dw is fully defined after the call, as in rbx_embed_csr_weight_grad
+    if (d_dweights[i] != nullptr && bags[i].nnz > 0 &&
+        hipMemsetAsync(d_dweights[i], 0, static_cast<size_t>(bags[i].nnz) * 4, s) != hipSuccess)
+      return fail(RBX_ERR_LAUNCH, "clearing a weight gradient failed");
+  if (batch == 0) return RBX_OK;
+  LongArgs la = long_args(lp, d_workspace);
+  const BagWeights none = {};
+  for (int k = 0; k < 2; ++k) {
+    if (cnt[k] == 0) continue;
+    la.cls = k;
+    if (!on) rc = (k == 0) ? dispatch_csr_weighted<true, true>(units[k], pack[k], none, dws[k], cnt[k], batch, nullptr, d_dout, out_stride_b, d_status, s)
+                           : dispatch_csr_weighted<true, false>(units[k], pack[k], none, dws[k], cnt[k], batch, nullptr, d_dout, out_stride_b, d_status, s);
+    else rc = (k == 0) ? dispatch_csr_weighted<true, true, kHandOff>(units[k], pack[k], none, dws[k], cnt[k], batch, nullptr, d_dout, out_stride_b, d_status, s, la)
+                       : dispatch_csr_weighted<true, false, kHandOff>(units[k], pack[k], none, dws[k], cnt[k], batch, nullptr, d_dout, out_stride_b, d_status, s, la);
+    if (rc != RBX_OK) return rc;
+  }
+  for (int k = 0; on && k < 2; ++k) {                      // the same segment tasks, nothing to combine
+    if (cnt[k] == 0) continue;
+    la.cls = k;
+    rc = (k == 0) ? dispatch_csr_weighted<true, true, kSegments>(units[k], all, none, dwall, n_bags, batch, nullptr, d_dout, out_stride_b, d_status, s, la)
+                  : dispatch_csr_weighted<true, false, kSegments>(units[k], all, none, dwall, n_bags, batch, nullptr, d_dout, out_stride_b, d_status, s, la);
     if (rc != RBX_OK) return rc;
   }
   return RBX_OK;

@@ -489,6 +489,24 @@ def sort_chained(enable=None):
     return bool(lib.rbx_sort_chained(-1 if enable is None else int(bool(enable))))
 
 
+_bag_long = [1024]
+
+
+def bag_long_threshold(value=None):
+    """The bag length from which ``embed_bags`` hands a bag to whole waves in segments of ``_lib.CSR_SEGMENT`` ids
+    (csrc/rbx_embed_csr.hip, the ``_long`` entry points) instead of one lane group: read (``None``) or set; returns the previous
+    setting.  Default 1024; 0 = never (the lane-group calls for every bag).  Bags below the threshold are bit-equal to the
+    padded lookup over the same ids; bags at or above it are summed per segment, then over the segments in order --
+    deterministic, held to the float64 bound of the sum."""
+    old = _bag_long[0]
+    if value is not None:
+        value = int(value)
+        if value < 0:
+            raise ValueError("bag_long_threshold must be >= 0, got %d" % value)
+        _bag_long[0] = value
+    return old
+
+
 def check_deferred_ids():
     """Raise IndexError if any lookup since the last call met an id outside its table while ``config.check_ids`` was off
     (one device-to-host read per device; the words are cleared)."""
@@ -699,6 +717,7 @@ class BagPlan(object):
         self.width = int(width) if width is not None else max(s.out_off + s.dim for s in self.specs)
         self.arr = (_lib.rbx_bag_t * self.n)()
         self.needs_row_scale = any(s.pool in (POOL_MEAN_VALUE, POOL_MEAN_ID) for s in self.specs)
+        self._long_ws = None                               # workspace of the long-bag calls (long_workspace)
         for f, s in zip(self.arr, self.specs):
             if s.pool in (POOL_NONE, POOL_CONCAT):
                 raise NotImplementedError("feature '%s': ragged bags are pooled (sum / mean); pool mode %d keeps one slot "
@@ -744,6 +763,16 @@ class BagPlan(object):
             g = grads[s.param] if grads is not None else None
             f.grad = g.data_ptr() if g is not None else None
 
+    def long_workspace(self, B, threshold, dev):
+        """(tensor, bytes) for the ``_long`` calls over the bags bound now: owned by the plan, regrown when nnz or B asks for
+        more (warm a plan up before a capture, as the capture tests do: a replay then uses the buffer of the warm-up)."""
+        need = lib.rbx_embed_csr_fwd_long_workspace_size(self.arr, self.n, B, threshold)
+        need = max(need, 256)                              # (0: descriptors the call itself refuses, with its own message)
+        ws = self._long_ws
+        if ws is None or ws.device != dev or ws.numel() < need:
+            ws = self._long_ws = torch.empty(need + need // 4, dtype=torch.uint8, device=dev)
+        return ws, ws.numel()
+
 
 class _EmbedBags(torch.autograd.Function):
     """out[B, width] = pooled gather over ragged bags (rbx_embed_csr_fwd); backward = the sorted segmented scatter-add
@@ -768,16 +797,28 @@ class _EmbedBags(torch.autograd.Function):
         status = _status_word(dev)
         stride = out.stride(0) if B > 1 else plan.width
         ctx.warr = _ptr_array(weights) if any(w is not None for w in weights) else None
+        ctx.long_t = T = bag_long_threshold()              # the backward's weight gradient takes the forward's setting
+        lws, lws_bytes = plan.long_workspace(B, T, dev) if T > 0 else (None, 0)
         if ctx.warr is None:
             row_scale = torch.empty((plan.n, B), dtype=torch.float32, device=dev) if plan.needs_row_scale else None
-            check(_timed(("embed_csr_fwd", plan.n, plan.width, B),
-                         lambda: lib.rbx_embed_csr_fwd(plan.arr, plan.n, B, _ptr(out), stride, _ptr(row_scale), _ptr(status),
-                                                       _stream())))
+            if T > 0:
+                check(_timed(("embed_csr_fwd_long", plan.n, plan.width, B),
+                             lambda: lib.rbx_embed_csr_fwd_long(plan.arr, plan.n, B, T, _ptr(out), stride, _ptr(row_scale),
+                                                                _ptr(lws), lws_bytes, _ptr(status), _stream())))
+            else:
+                check(_timed(("embed_csr_fwd", plan.n, plan.width, B),
+                             lambda: lib.rbx_embed_csr_fwd(plan.arr, plan.n, B, _ptr(out), stride, _ptr(row_scale), _ptr(status),
+                                                           _stream())))
         else:
             row_scale = None
-            check(_timed(("embed_csr_fwd_weighted", plan.n, plan.width, B),
-                         lambda: lib.rbx_embed_csr_fwd_weighted(plan.arr, plan.n, B, ctx.warr, _ptr(out), stride, _ptr(status),
-                                                                _stream())))
+            if T > 0:
+                check(_timed(("embed_csr_fwd_weighted_long", plan.n, plan.width, B),
+                             lambda: lib.rbx_embed_csr_fwd_weighted_long(plan.arr, plan.n, B, T, ctx.warr, _ptr(out), stride,
+                                                                         _ptr(lws), lws_bytes, _ptr(status), _stream())))
+            else:
+                check(_timed(("embed_csr_fwd_weighted", plan.n, plan.width, B),
+                             lambda: lib.rbx_embed_csr_fwd_weighted(plan.arr, plan.n, B, ctx.warr, _ptr(out), stride,
+                                                                    _ptr(status), _stream())))
         _check_status(status)
         ctx.plan, ctx.inputs, ctx.row_scale, ctx.B, ctx.params, ctx.weights = plan, inputs, row_scale, B, params, weights
         ctx.ws, ctx.ws_bytes = None, 0
@@ -817,7 +858,12 @@ class _EmbedBags(torch.autograd.Function):
         if any(want_w):                                    # dw = <dY, row>: reads the tables, needs no sort
             plan.bind_params(params)
             dws = [torch.empty_like(w) if k else None for w, k in zip(ctx.weights, want_w)]
-            check(lib.rbx_embed_csr_weight_grad(plan.arr, plan.n, B, _ptr(dout), stride, _ptr_array(dws), None, _stream()))
+            if ctx.long_t > 0:
+                lws, lws_bytes = plan.long_workspace(B, ctx.long_t, dout.device)
+                check(lib.rbx_embed_csr_weight_grad_long(plan.arr, plan.n, B, ctx.long_t, _ptr(dout), stride, _ptr_array(dws),
+                                                         _ptr(lws), lws_bytes, None, _stream()))
+            else:
+                check(lib.rbx_embed_csr_weight_grad(plan.arr, plan.n, B, _ptr(dout), stride, _ptr_array(dws), None, _stream()))
         head = (None, None, None) + (None,) * len(ctx.inputs) + tuple(dws)
         if not any(want):                                  # frozen tables
             return head + (None,) * len(params)
