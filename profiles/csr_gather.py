@@ -237,7 +237,7 @@ def main():
     case("4. case 2's bags under SUM_ID, unweighted against random per-sample weights", ["unweighted", "weighted"],
          [plain, scored], a.repeats, lines)
     g = bracket([scored.wgrad], a.repeats)[0]
-    lines.append("\nweight gradient (memset of dw + csr_weight_grad_kernel): %.1f us (%.1f .. %.1f)" % g)
+    lines.append("\nweight gradient (memset of dw + bag_walk_kernel<WeightGradOp>): %.1f us (%.1f .. %.1f)" % g)
     text = "\n".join(lines) + "\n"
     print(text)
     if a.out:

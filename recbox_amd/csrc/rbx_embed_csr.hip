@@ -6,12 +6,20 @@
 // each exactly as rbx_pool_t defines it for padded ids (rbx_embed_fwd.hip, embed_seq_kernel) -- a bag is the history
 // without its padded tail, the layout of torch.nn.EmbeddingBag.
 //
-// Forward.  embed_seq_kernel's mapping with the id range taken from two offset loads per lane group instead of
-// (b * stride, seq_len): a lane group per bag, a wave task = (bag descriptor, block of 64 / SG bags) with the descriptor
-// in SGPRs, a coalesced sweep of the bag's ids in chunks of 4 * SG, classify + compact into the group's LDS list, U = 4
-// rows in flight, R sub-groups and a closing butterfly for narrow rows.  Chunk size, list order, U and R are the padded
-// kernel's, so a bag is summed in the order the padded call sums the same live ids: the outputs are bit-equal.  The
-// wave-uniform loop bound is the longest bag of the wave.
+// The bag walk.  Everything that reads table rows bag by bag is ONE kernel body, bag_walk_kernel<Op, G, R, NV, VEC, MODE>:
+// embed_seq_kernel's mapping with the id range taken from two offset loads per lane group instead of (b * stride,
+// seq_len) -- a lane group per bag, a wave task = (bag descriptor, block of 64 / SG bags) with the descriptor in SGPRs, a
+// coalesced sweep of the bag's ids in chunks of 4 * SG, classify + compact into the group's LDS list, U = 4 rows in
+// flight, R sub-groups for narrow rows.  The wave-uniform loop bound is the longest bag of the wave.  Chunk size, U and
+// the sub-group rule are the padded kernel's own constants (rbx_rowfrag.h), so a bag is walked in the order the padded
+// call walks the same live ids.  What happens to a row is the Op's business, and the three ops differ in nothing else:
+//   PoolOp          (forward)          acc += row, the mean pools count; butterfly, 1 / (count + eps), store.  Bit-equal
+//                                      to the padded call.  No second LDS list: 4 KB per workgroup.
+//   WeightedPoolOp  (weighted forward) a weight travels with the id (a second list, 8 KB); acc += w * row; butterfly,
+//                                      store.  x * 1.0f is x: all-ones weights give PoolOp's bits.
+//   WeightGradOp    (weight gradient)  the position travels with the id; dw[position] = <dY[bag, slot], row>; no close.
+// Sweep, compaction and batch order exist once, so the two bit-equalities hold by construction, not by keeping copies in
+// step.  check_launch still reports the ops under the names they had as separate kernels (Op::kName).
 // Backward.  The positions of a descriptor's index array are its lookups.  csr_bag_map_kernel (a lane group per bag,
 // coalesced stores) leaves an int32 lookup -> bag map; csr_keys_kernel builds, per sort tile, (global row, bag) pairs
 // for the in-range, unmasked, non-padding ids inside a bag -- every other position gets the sentinel key the sort puts
@@ -21,12 +29,13 @@
 // User-supplied offsets are clamped to 0 <= begin <= end <= nnz before any index is read (status bit 1 when that
 // changed anything): no input makes a kernel read outside indices[0, nnz).
 // Per-sample weights (sum pools only; torch's per_sample_weights).  A parallel array of fp32 [nnz] weight pointers, one
-// per descriptor, NULL = unweighted.  Forward: embed_csr_weighted_kernel, embed_csr_kernel's sweep with the weight loaded
-// beside the id and compacted beside it (a second LDS list), acc += w * row in the same chunk / list / U / R order: all
-// weights 1.0f give the unweighted call's bits.  Table gradient: the weighted sort's pair value names the lookup's POSITION
-// inside its descriptor's index array (csr_keys_kernel<RB, true>), and WeightedBagPolicy reads bag = map[position] and
-// w[position] -- rbx_embed_bwd_indexed's indirection plus one factor; passes, reduce and fix-ups unchanged.  Weight
-// gradient: csr_weight_grad_kernel, a lane group per bag, dw[j] = <dY[bag, slot], table[id_j]>; no sort involved.
+// per descriptor, NULL = unweighted.  Forward: WeightedPoolOp for the descriptors that have weights, PoolOp for the rest.
+// Table gradient: the weighted sort's pair value names the lookup's POSITION inside its descriptor's index array
+// (csr_keys_kernel<RB, true>), and WeightedBagPolicy reads bag = map[position] and w[position] -- rbx_embed_bwd_indexed's
+// indirection plus one factor; passes, reduce and fix-ups unchanged.  Weight gradient: WeightGradOp; no sort involved.
+// Host side.  classify_bags sorts a call's descriptors into (float4 | scalar) x (unweighted | weighted) launches and
+// refuses a dim no lane group holds before anything is written; csr_forward serves the four forward entry points and
+// csr_weight_grad the two weight-gradient ones, the long form being a parameter of both.
 #include "rbx_bwd_common.h"
 #include "rbx_rowfrag.h"
 #include "rbx_segreduce.h"
@@ -54,8 +63,10 @@ struct BagK {               // 64 B; RBX_MAX_BAGS of them (2 KiB) travel in the 
 static_assert(sizeof(BagK) == 64, "BagK must stay 64 bytes");
 struct BagPack { BagK f[RBX_MAX_BAGS]; };
 struct BagLookups { unsigned lk_off[RBX_MAX_BAGS]; };   // first lookup of every bag descriptor in the call's sort
-struct BagWeights { const float* w[RBX_MAX_BAGS]; };    // per-sample weights of the descriptors of a BagPack, same order
-struct BagWeightGrads { float* dw[RBX_MAX_BAGS]; };     // ... and where their gradients go
+template <class T>
+struct BagPtrs { T* p[RBX_MAX_BAGS]; };                 // one fp32 [nnz] array per descriptor of a BagPack, same order
+using BagWeights = BagPtrs<const float>;                // per-sample weights
+using BagWeightGrads = BagPtrs<float>;                  // ... and where their gradients go
 
 // [begin, end) of bag b, clamped into [0, nnz]; *bad: the clamp changed something
 __device__ __forceinline__ void bag_range(const BagK& fd, long long b, int* begin, int* end, bool* bad) {
@@ -76,7 +87,7 @@ __device__ __forceinline__ void bag_range(const BagK& fd, long long b, int* begi
 }
 
 // ---- the long-bag form: a bag of >= T ids is cut into segments of RBX_CSR_SEGMENT ids, a wave per segment ---------------
-// MODE of the three bag-walking kernels: kWalk = a lane group per bag whatever its length (the existing entry points);
+// MODE of bag_walk_kernel: kWalk = a lane group per bag whatever its length (the entry points without `_long`);
 // kHandOff = the same, but a group whose bag has L >= T appends a record to the workspace and neither sweeps nor stores;
 // kSegments = a wave task is one segment of a recorded bag: the wave's lane groups take consecutive S / (64 / G) ids each
 // and walk them exactly as a lane group walks a bag (chunk / list / U / R), the closing butterfly runs over the whole wave,
@@ -163,22 +174,168 @@ __device__ __forceinline__ void long_sub_range(const LongRec& r, long long s, in
   *end = static_cast<int>(ge);
 }
 
-// ---- forward -------------------------------------------------------------------------------------------------------
-// The constants below are embed_seq_kernel's (RBX_SEQ_WAVES, RBX_SEQ_U, RBX_SEQ_IPL16, RBX_SEQ_SG16 / _SG32): the
-// bit-equality of the two paths rests on equal chunks, batches and sub-group counts.
-constexpr int kCsrWaves = 4;
-constexpr int kCsrU = 4;               // rows in flight per lane
-constexpr int kCsrIpl = 4;             // ids per lane per chunk
+// ---- the bag walk: one kernel body, an op per use ----------------------------------------------------------------------
+// bag_walk_kernel is embed_seq_kernel's mapping over [begin, end) of a bag; kSeqWaves, kSeqU, kSeqIpl and seq_group_lanes
+// (rbx_rowfrag.h) are that kernel's own, so chunks, batches and sub-group counts are equal by construction.  An op says
+// what happens to a row once it is in registers:
+//   Args      what the op reads and writes, passed to the kernel by value;
+//   Payload   the value that travels with an id through the LDS list (kHasPayload = false: no second list at all);
+//   Bag       the state of one (lane group, bag): open() per bag, payload() in the id sweep, row() per loaded row,
+//             close() after the last chunk.  `owner` lanes store: the first sub-group of a live bag that was not handed
+//             over; in kSegments the first W lanes of the wave, and the row goes to partial slot t of the workspace.
+// Every lane of the wave reaches open(), row() and close() together (the loop bounds are wave-uniform), so they may shuffle.
+struct NoPayload {};
 
-template <int G, int R, int NV, bool VEC, int MODE = kWalk>
-__global__ __launch_bounds__(256, kCsrWaves) void embed_csr_kernel(const BagPack P, const int F, const long long B,
-                                                                   float* __restrict__ out, const long long stride_b,
-                                                                   float* __restrict__ row_scale,
-                                                                   int* __restrict__ status, const LongArgs LA) {
+// sum / mean pools: acc += row, the mean pools count as rbx_pool_t says; close = butterfly, 1 / (count + eps), store
+struct PoolOp {
+  static constexpr const char* kName = "embed_csr_kernel";
+  static constexpr bool kHasPayload = false;
+  using Payload = NoPayload;
+  struct Args {
+    float* out;
+    long long stride_b;
+    float* row_scale;       // NULL: not wanted
+  };
+  template <int W, int NV, bool VEC>
+  struct Bag {
+    using Frag = RowFrag<W, NV, VEC>;
+    Frag acc;
+    float count;
+    __device__ __forceinline__ void open(const Args&, const BagK&, int, long long, bool, int) {
+      acc.zero();
+      count = 0.f;
+    }
+    __device__ __forceinline__ void row(const BagK& fd, Frag& r, int id, Payload, int) {
+      acc.add(r);
+      if (fd.pool == RBX_POOL_MEAN_VALUE) {
+        const float sm = group_sum<W>(r.hsum());          // value mask: row sum != 0
+        count += (sm != 0.f) ? 1.f : 0.f;
+      } else if (fd.pool == RBX_POOL_MEAN_ID) {
+        count += (id >= 0) ? 1.f : 0.f;
+      }
+    }
+    template <int MODE, int G>
+    __device__ __forceinline__ void close(const Args& a, const LongArgs& la, const BagK& fd, long long t, long long b, long long B,
+                                          bool owner, int lane_w) {
+#pragma unroll
+      for (int o = W; o < (MODE == kSegments ? 64 : G); o <<= 1) {   // every lane joins the butterfly (segments: the whole wave)
+        acc.xor_add(o);
+        count += __shfl_xor(count, o, 64);
+      }
+      if (!owner) return;
+      if constexpr (MODE == kSegments) {                  // t < cap_segs (long_counts); the finish applies the mean scale
+        acc.store(la.part + t * la.pstride, fd.dim, lane_w);
+        if (lane_w == 0) la.pcnt[t] = count;
+      } else {
+        if (fd.pool == RBX_POOL_MEAN_VALUE || fd.pool == RBX_POOL_MEAN_ID) {
+          const float inv = 1.0f / (count + fd.eps);      // an empty bag: 0 * (1 / eps) = 0
+          acc.scale(inv);
+          if (a.row_scale != nullptr && lane_w == 0) a.row_scale[static_cast<long long>(fd.slot) * B + b] = inv;
+        }
+        acc.store(a.out + b * a.stride_b + fd.out_off, fd.dim, lane_w);
+      }
+    }
+  };
+};
+
+// sum pools with one factor per lookup: the weight is loaded beside the id, compacted beside it and multiplied into the
+// row before the add.  x * 1.0f is x: all-ones weights give PoolOp's bits.
+struct WeightedPoolOp {
+  static constexpr const char* kName = "embed_csr_weighted_kernel";
+  static constexpr bool kHasPayload = true;
+  using Payload = float;
+  struct Args {
+    BagWeights w;
+    float* out;
+    long long stride_b;
+  };
+  template <int W, int NV, bool VEC>
+  struct Bag {
+    using Frag = RowFrag<W, NV, VEC>;
+    Frag acc;
+    const float* __restrict__ wsrc;
+    __device__ __forceinline__ void open(const Args& a, const BagK&, int f, long long, bool, int) {
+      acc.zero();
+      wsrc = a.w.p[f];
+    }
+    __device__ __forceinline__ float payload(long long pos, bool live) const { return live ? wsrc[pos] : 0.f; }
+    __device__ __forceinline__ void row(const BagK&, Frag& r, int, float w, int) {
+      r.scale(w);
+      acc.add(r);
+    }
+    template <int MODE, int G>
+    __device__ __forceinline__ void close(const Args& a, const LongArgs& la, const BagK& fd, long long t, long long b, long long,
+                                          bool owner, int lane_w) {
+#pragma unroll
+      for (int o = W; o < (MODE == kSegments ? 64 : G); o <<= 1) acc.xor_add(o);   // every lane joins the butterfly
+      if (!owner) return;
+      if constexpr (MODE == kSegments) acc.store(la.part + t * la.pstride, fd.dim, lane_w);
+      else acc.store(a.out + b * a.stride_b + fd.out_off, fd.dim, lane_w);
+    }
+  };
+};
+
+// weight gradient: dw[j] = <dY[bag, slot], table[id_j]>.  The bag's dY fragment is loaded once, the ids travel with their
+// positions, the dot is reduced over the W lanes that hold a row and stored by the first of them; nothing to combine at the
+// end, so a handed-over bag is an empty one here.  Only usable positions are written: the host clears dw[0, nnz) in front
+// of the launch, so masked and out-of-range ids and the positions outside every bag read 0.
+template <int W, int NV>
+__device__ __forceinline__ float row_dot(const RowFrag<W, NV, true>& a, const RowFrag<W, NV, true>& b) {
+  float s = 0.f;
+#pragma unroll
+  for (int u = 0; u < NV; ++u)
+    s += (a.a[u].v.x * b.a[u].v.x + a.a[u].v.y * b.a[u].v.y) + (a.a[u].v.z * b.a[u].v.z + a.a[u].v.w * b.a[u].v.w);
+  return s;
+}
+template <int W, int NV>
+__device__ __forceinline__ float row_dot(const RowFrag<W, NV, false>& a, const RowFrag<W, NV, false>& b) {
+  float s = 0.f;
+#pragma unroll
+  for (int u = 0; u < NV; ++u) s += a.a[u].v * b.a[u].v;
+  return s;
+}
+
+struct WeightGradOp {
+  static constexpr const char* kName = "csr_weight_grad_kernel";
+  static constexpr bool kHasPayload = true;
+  using Payload = int;
+  struct Args {
+    BagWeightGrads dw;
+    const float* dout;
+    long long stride_b;
+  };
+  template <int W, int NV, bool VEC>
+  struct Bag {
+    using Frag = RowFrag<W, NV, VEC>;
+    Frag dy;
+    float* __restrict__ dw;
+    __device__ __forceinline__ void open(const Args& a, const BagK& fd, int f, long long b, bool alive, int lane_w) {
+      dw = a.dw.p[f];
+      dy.zero();
+      if (alive) dy.load(a.dout + b * a.stride_b + fd.out_off, fd.dim, lane_w);
+    }
+    __device__ __forceinline__ int payload(long long pos, bool) const { return static_cast<int>(pos); }   // < end <= nnz
+    __device__ __forceinline__ void row(const BagK&, Frag& r, int id, int pos, int lane_w) {
+      const float d = group_sum<W>(row_dot(r, dy));
+      if (id >= 0 && lane_w == 0) dw[pos] = d;
+    }
+    template <int MODE, int G>
+    __device__ __forceinline__ void close(const Args&, const LongArgs&, const BagK&, long long, long long, long long, bool, int) {}
+  };
+};
+
+// A lane group per bag, a wave task = (bag descriptor, block of 64 / G bags) with the descriptor in SGPRs; in kSegments a
+// wave task is one segment slot.  Per chunk of 4 * G ids: (1a) one coalesced sweep of the ids (and the op's payload),
+// (1b) classify + compact into the group's LDS list, (2) the list walked U rows at a time, R sub-groups side by side.
+template <class Op, int G, int R, int NV, bool VEC, int MODE>
+__global__ __launch_bounds__(256, kSeqWaves) void bag_walk_kernel(const BagPack P, const typename Op::Args A, const int F,
+                                                                  const long long B, int* __restrict__ status,
+                                                                  const LongArgs LA) {
   constexpr int W = G / R;                                // lanes that hold one row
   using Frag = RowFrag<W, NV, VEC>;
-  constexpr int U = kCsrU;
-  constexpr int IPL = kCsrIpl;
+  using Pay = typename Op::Payload;
+  constexpr int U = kSeqU;
+  constexpr int IPL = kSeqIpl;
   constexpr int C = G * IPL;                              // lookups per chunk
   constexpr int GPB = 256 / G;
   __shared__ int s_id[GPB][C];
@@ -190,6 +347,11 @@ __global__ __launch_bounds__(256, kCsrWaves) void embed_csr_kernel(const BagPack
   const unsigned long long gmask = (G == 64) ? ~0ull : ((1ull << G) - 1ull);
   const unsigned long long below = (1ull << lane_g) - 1ull;
   volatile int* my_id = s_id[gidx];
+  volatile Pay* my_pay = nullptr;
+  if constexpr (Op::kHasPayload) {                        // the second list exists only for an op that has something to put there
+    __shared__ Pay s_pay[GPB][C];
+    my_pay = s_pay[gidx];
+  }
   constexpr int GPW = 64 / G;
   const long long tasks_per_bag = (B + GPW - 1) / GPW;
   long long ntasks = tasks_per_bag * F;
@@ -220,6 +382,8 @@ __global__ __launch_bounds__(256, kCsrWaves) void embed_csr_kernel(const BagPack
       bag_range(fd, b, &begin, &end, &bad);
       if (bad && lane_g == 0 && status != nullptr) atomicOr(status, kStatusBadOffsets);
     }
+    typename Op::template Bag<W, NV, VEC> bag;
+    bag.open(A, fd, f, b, alive, lane_w);
     int L = end - begin;
     bool handed = false;                                  // the bag went to the segment kernel: no sweep, no store here
     if constexpr (MODE == kHandOff) {
@@ -228,10 +392,6 @@ __global__ __launch_bounds__(256, kCsrWaves) void embed_csr_kernel(const BagPack
       handed = __shfl(took, 0, G) != 0;
       if (handed) L = 0;
     }
-    float* dst = out + b * stride_b + fd.out_off;
-    Frag acc;
-    acc.zero();
-    float count = 0.f;
     int Lmax = L;                                         // wave-uniform number of chunks: the longest bag of the wave
 #pragma unroll
     for (int o = 32; o >= G && o > 0; o >>= 1) {
@@ -240,160 +400,12 @@ __global__ __launch_bounds__(256, kCsrWaves) void embed_csr_kernel(const BagPack
     }
     for (int c0 = 0; c0 < Lmax; c0 += C) {
       long long raw[IPL];
+      Pay pay[IPL];
 #pragma unroll
       for (int i = 0; i < IPL; ++i) {                     // (1a) one coalesced sweep of id loads; l < L <=> inside [begin, end)
         const int l = c0 + i * G + lane_g;
         raw[i] = (l < L) ? load_raw(fd.indices, (static_cast<long long>(begin) + l) * fd.idx_stride, dt) : 0;
-      }
-      int nvalid = 0;
-#pragma unroll
-      for (int i = 0; i < IPL; ++i) {                     // (1b) classify + compact
-        const int l = c0 + i * G + lane_g;
-        const long long id = decode_id(raw[i], dt);
-        const bool live = l < L;
-        const bool in_range = id >= 0 && id < fd.vocab;
-        if (live && !in_range && status != nullptr) atomicOr(status, kStatusBadId);
-        const bool use = live && in_range && !(id_pool && id == fd.mask_id);
-        const unsigned long long m = (__ballot(use) >> gshift) & gmask;
-        if (use) my_id[nvalid + __popcll(m & below)] = static_cast<int>(id);
-        nvalid += __popcll(m);
-      }
-      __builtin_amdgcn_wave_barrier();
-      int nmax = nvalid;                                   // wave-uniform batch count
-#pragma unroll
-      for (int o = 32; o >= G && o > 0; o >>= 1) {
-        const int other = __shfl_xor(nmax, o, 64);
-        nmax = other > nmax ? other : nmax;
-      }
-      for (int k0 = 0; k0 < nmax; k0 += U * R) {          // (2) dense row batches
-        int idu[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int k = k0 + u * R + sub;
-          idu[u] = (k < nvalid) ? my_id[k] : -1;
-        }
-        Frag r[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          r[u].zero();
-          if (idu[u] >= 0) r[u].load(fd.table + static_cast<long long>(idu[u]) * dim, dim, lane_w);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          acc.add(r[u]);
-          if (pool == RBX_POOL_MEAN_VALUE) {
-            const float sm = group_sum<W>(r[u].hsum());   // value mask: row sum != 0
-            count += (sm != 0.f) ? 1.f : 0.f;
-          } else if (pool == RBX_POOL_MEAN_ID) {
-            count += (idu[u] >= 0) ? 1.f : 0.f;
-          }
-        }
-      }
-      __builtin_amdgcn_wave_barrier();
-    }
-#pragma unroll
-    for (int o = W; o < (MODE == kSegments ? 64 : G); o <<= 1) {   // every lane joins the butterfly (segments: the whole wave)
-      acc.xor_add(o);
-      count += __shfl_xor(count, o, 64);
-    }
-    if constexpr (MODE == kSegments) {                    // t < cap_segs (long_counts); the finish applies the mean scale
-      if ((threadIdx.x & 63) < W) {
-        acc.store(LA.part + t * LA.pstride, dim, lane_w);
-        if (lane_w == 0) LA.pcnt[t] = count;
-      }
-      continue;
-    }
-    if (!alive || sub != 0 || handed) continue;
-    if (pool == RBX_POOL_MEAN_VALUE || pool == RBX_POOL_MEAN_ID) {
-      const float inv = 1.0f / (count + fd.eps);          // an empty bag: 0 * (1 / eps) = 0
-      acc.scale(inv);
-      if (row_scale != nullptr && lane_w == 0) row_scale[static_cast<long long>(fd.slot) * B + b] = inv;
-    }
-    acc.store(dst, dim, lane_w);
-  }
-}
-
-// ---- forward with per-sample weights --------------------------------------------------------------------------------
-// embed_csr_kernel for the sum pools with one factor per lookup: the weight is loaded in the id's coalesced sweep,
-// compacted beside the id (a second list: 8 KB of LDS per workgroup) and multiplied into the row before the add.  Chunk
-// size, list order, U and R are embed_csr_kernel's, and x * 1.0f is x: all-ones weights give that kernel's bits.
-template <int G, int R, int NV, bool VEC, int MODE = kWalk>
-__global__ __launch_bounds__(256, kCsrWaves) void embed_csr_weighted_kernel(const BagPack P, const BagWeights WP, const int F,
-                                                                            const long long B, float* __restrict__ out,
-                                                                            const long long stride_b,
-                                                                            int* __restrict__ status, const LongArgs LA) {
-  constexpr int W = G / R;                                // lanes that hold one row
-  using Frag = RowFrag<W, NV, VEC>;
-  constexpr int U = kCsrU;
-  constexpr int IPL = kCsrIpl;
-  constexpr int C = G * IPL;                              // lookups per chunk
-  constexpr int GPB = 256 / G;
-  __shared__ int s_id[GPB][C];
-  __shared__ float s_w[GPB][C];
-  const int lane_w = threadIdx.x % W;
-  const int sub = (threadIdx.x % G) / W;
-  const int lane_g = threadIdx.x % G;
-  const int gidx = threadIdx.x / G;
-  const int gshift = (threadIdx.x & 63) & ~(G - 1);       // first lane of the group inside its wave
-  const unsigned long long gmask = (G == 64) ? ~0ull : ((1ull << G) - 1ull);
-  const unsigned long long below = (1ull << lane_g) - 1ull;
-  volatile int* my_id = s_id[gidx];
-  volatile float* my_w = s_w[gidx];
-  constexpr int GPW = 64 / G;
-  const long long tasks_per_bag = (B + GPW - 1) / GPW;
-  long long ntasks = tasks_per_bag * F;
-  int n_long = 0;
-  if constexpr (MODE == kSegments) long_counts(LA, &n_long, &ntasks);    // a wave task = one segment slot
-  const long long nwaves = static_cast<long long>(gridDim.x) * 4;
-  for (long long t = static_cast<long long>(blockIdx.x) * 4 + threadIdx.x / 64; t < ntasks; t += nwaves) {
-    int f, begin = 0, end = 0;
-    long long b;
-    bool alive;
-    if constexpr (MODE == kSegments) {
-      const LongRec rec = long_find(LA, n_long, t);
-      if (rec.cls != LA.cls || static_cast<unsigned>(rec.desc) >= static_cast<unsigned>(F)) continue;
-      f = rec.desc;
-      b = rec.bag;
-      alive = true;
-      long_sub_range<GPW>(rec, t, (threadIdx.x & 63) / G, &begin, &end);
-    } else {
-      f = __builtin_amdgcn_readfirstlane(static_cast<int>(t / tasks_per_bag));
-      b = (t - f * tasks_per_bag) * GPW + (threadIdx.x & 63) / G;
-      alive = b < B;
-    }
-    const BagK& fd = P.f[f];
-    const float* __restrict__ wsrc = WP.w[f];
-    const int dim = fd.dim, dt = fd.idx_dtype;
-    const bool id_pool = fd.pool == RBX_POOL_SUM_ID;
-    if (MODE != kSegments && alive) {
-      bool bad;
-      bag_range(fd, b, &begin, &end, &bad);
-      if (bad && lane_g == 0 && status != nullptr) atomicOr(status, kStatusBadOffsets);
-    }
-    int L = end - begin;
-    bool handed = false;
-    if constexpr (MODE == kHandOff) {
-      int took = 0;
-      if (alive && lane_g == 0 && L >= LA.T) took = long_append(LA, fd.slot, b, begin, end);
-      handed = __shfl(took, 0, G) != 0;
-      if (handed) L = 0;
-    }
-    Frag acc;
-    acc.zero();
-    int Lmax = L;                                         // wave-uniform number of chunks: the longest bag of the wave
-#pragma unroll
-    for (int o = 32; o >= G && o > 0; o >>= 1) {
-      const int other = __shfl_xor(Lmax, o, 64);
-      Lmax = other > Lmax ? other : Lmax;
-    }
-    for (int c0 = 0; c0 < Lmax; c0 += C) {
-      long long raw[IPL];
-      float wraw[IPL];
-#pragma unroll
-      for (int i = 0; i < IPL; ++i) {                     // (1a) ids and weights, one coalesced sweep; l < L <=> inside [begin, end)
-        const int l = c0 + i * G + lane_g;
-        raw[i] = (l < L) ? load_raw(fd.indices, (static_cast<long long>(begin) + l) * fd.idx_stride, dt) : 0;
-        wraw[i] = (l < L) ? wsrc[static_cast<long long>(begin) + l] : 0.f;
+        if constexpr (Op::kHasPayload) pay[i] = bag.payload(static_cast<long long>(begin) + l, l < L);
       }
       int nvalid = 0;
 #pragma unroll
@@ -408,7 +420,7 @@ __global__ __launch_bounds__(256, kCsrWaves) void embed_csr_weighted_kernel(cons
         if (use) {
           const int at = nvalid + __popcll(m & below);
           my_id[at] = static_cast<int>(id);
-          my_w[at] = wraw[i];
+          if constexpr (Op::kHasPayload) my_pay[at] = pay[i];
         }
         nvalid += __popcll(m);
       }
@@ -421,12 +433,12 @@ __global__ __launch_bounds__(256, kCsrWaves) void embed_csr_weighted_kernel(cons
       }
       for (int k0 = 0; k0 < nmax; k0 += U * R) {          // (2) dense row batches
         int idu[U];
-        float wu[U];
+        Pay pu[U] = {};
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           const int k = k0 + u * R + sub;
           idu[u] = (k < nvalid) ? my_id[k] : -1;
-          wu[u] = (k < nvalid) ? my_w[k] : 0.f;
+          if constexpr (Op::kHasPayload) pu[u] = (k < nvalid) ? my_pay[k] : Pay(0);
         }
         Frag r[U];
 #pragma unroll
@@ -435,243 +447,60 @@ __global__ __launch_bounds__(256, kCsrWaves) void embed_csr_weighted_kernel(cons
           if (idu[u] >= 0) r[u].load(fd.table + static_cast<long long>(idu[u]) * dim, dim, lane_w);
         }
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-          r[u].scale(wu[u]);
-          acc.add(r[u]);
-        }
+        for (int u = 0; u < U; ++u) bag.row(fd, r[u], idu[u], pu[u], lane_w);
       }
       __builtin_amdgcn_wave_barrier();
     }
-#pragma unroll
-    for (int o = W; o < (MODE == kSegments ? 64 : G); o <<= 1) acc.xor_add(o);   // every lane joins the butterfly
-    if constexpr (MODE == kSegments) {
-      if ((threadIdx.x & 63) < W) acc.store(LA.part + t * LA.pstride, dim, lane_w);
-      continue;
-    }
-    if (!alive || sub != 0 || handed) continue;
-    acc.store(out + b * stride_b + fd.out_off, dim, lane_w);
+    const bool owner = (MODE == kSegments) ? (threadIdx.x & 63) < W : (alive && sub == 0 && !handed);
+    bag.template close<MODE, G>(A, LA, fd, t, b, B, owner, lane_w);
   }
 }
 
-// ---- weight gradient: dw[j] = <dY[bag, slot], table[id_j]> -----------------------------------------------------------
-// The forward's mapping once more: a lane group per bag, the bag's dY fragment loaded once, the ids swept and compacted
-// with their positions, U rows in flight, the dot reduced over the W lanes that hold a row and stored by the first of
-// them.  Only usable positions are written: the host clears dw[0, nnz) in front of the launch, so masked and
-// out-of-range ids and the positions outside every bag read 0.
-template <int W, int NV>
-__device__ __forceinline__ float row_dot(const RowFrag<W, NV, true>& a, const RowFrag<W, NV, true>& b) {
-  float s = 0.f;
-#pragma unroll
-  for (int u = 0; u < NV; ++u)
-    s += (a.a[u].v.x * b.a[u].v.x + a.a[u].v.y * b.a[u].v.y) + (a.a[u].v.z * b.a[u].v.z + a.a[u].v.w * b.a[u].v.w);
-  return s;
-}
-template <int W, int NV>
-__device__ __forceinline__ float row_dot(const RowFrag<W, NV, false>& a, const RowFrag<W, NV, false>& b) {
-  float s = 0.f;
-#pragma unroll
-  for (int u = 0; u < NV; ++u) s += a.a[u].v * b.a[u].v;
-  return s;
-}
-
-template <int G, int R, int NV, bool VEC, int MODE = kWalk>
-__global__ __launch_bounds__(256, kCsrWaves) void csr_weight_grad_kernel(const BagPack P, const BagWeightGrads DW, const int F,
-                                                                         const long long B, const float* __restrict__ dout,
-                                                                         const long long stride_b,
-                                                                         int* __restrict__ status, const LongArgs LA) {
-  constexpr int W = G / R;
-  using Frag = RowFrag<W, NV, VEC>;
-  constexpr int U = kCsrU;
-  constexpr int IPL = kCsrIpl;
-  constexpr int C = G * IPL;
-  constexpr int GPB = 256 / G;
-  __shared__ int s_id[GPB][C];
-  __shared__ int s_pos[GPB][C];
-  const int lane_w = threadIdx.x % W;
-  const int sub = (threadIdx.x % G) / W;
-  const int lane_g = threadIdx.x % G;
-  const int gidx = threadIdx.x / G;
-  const int gshift = (threadIdx.x & 63) & ~(G - 1);
-  const unsigned long long gmask = (G == 64) ? ~0ull : ((1ull << G) - 1ull);
-  const unsigned long long below = (1ull << lane_g) - 1ull;
-  volatile int* my_id = s_id[gidx];
-  volatile int* my_pos = s_pos[gidx];
-  constexpr int GPW = 64 / G;
-  const long long tasks_per_bag = (B + GPW - 1) / GPW;
-  long long ntasks = tasks_per_bag * F;
-  int n_long = 0;
-  if constexpr (MODE == kSegments) long_counts(LA, &n_long, &ntasks);    // a wave task = one segment slot
-  const long long nwaves = static_cast<long long>(gridDim.x) * 4;
-  for (long long t = static_cast<long long>(blockIdx.x) * 4 + threadIdx.x / 64; t < ntasks; t += nwaves) {
-    int f, begin = 0, end = 0;
-    long long b;
-    bool alive;
-    if constexpr (MODE == kSegments) {
-      const LongRec rec = long_find(LA, n_long, t);
-      if (rec.cls != LA.cls || static_cast<unsigned>(rec.desc) >= static_cast<unsigned>(F)) continue;
-      f = rec.desc;
-      b = rec.bag;
-      alive = true;
-      long_sub_range<GPW>(rec, t, (threadIdx.x & 63) / G, &begin, &end);
-    } else {
-      f = __builtin_amdgcn_readfirstlane(static_cast<int>(t / tasks_per_bag));
-      b = (t - f * tasks_per_bag) * GPW + (threadIdx.x & 63) / G;
-      alive = b < B;
-    }
-    const BagK& fd = P.f[f];
-    float* __restrict__ dw = DW.dw[f];
-    const int dim = fd.dim, dt = fd.idx_dtype;
-    const bool id_pool = fd.pool == RBX_POOL_SUM_ID;
-    Frag dy;
-    dy.zero();
-    if (alive) {
-      if constexpr (MODE != kSegments) {
-        bool bad;
-        bag_range(fd, b, &begin, &end, &bad);
-        if (bad && lane_g == 0 && status != nullptr) atomicOr(status, kStatusBadOffsets);
-      }
-      dy.load(dout + b * stride_b + fd.out_off, dim, lane_w);
-    }
-    int L = end - begin;
-    if constexpr (MODE == kHandOff) {                     // nothing to store at the end: a handed-over bag is an empty one here
-      int took = 0;
-      if (alive && lane_g == 0 && L >= LA.T) took = long_append(LA, fd.slot, b, begin, end);
-      if (__shfl(took, 0, G) != 0) L = 0;
-    }
-    int Lmax = L;
-#pragma unroll
-    for (int o = 32; o >= G && o > 0; o >>= 1) {
-      const int other = __shfl_xor(Lmax, o, 64);
-      Lmax = other > Lmax ? other : Lmax;
-    }
-    for (int c0 = 0; c0 < Lmax; c0 += C) {
-      long long raw[IPL];
-#pragma unroll
-      for (int i = 0; i < IPL; ++i) {
-        const int l = c0 + i * G + lane_g;
-        raw[i] = (l < L) ? load_raw(fd.indices, (static_cast<long long>(begin) + l) * fd.idx_stride, dt) : 0;
-      }
-      int nvalid = 0;
-#pragma unroll
-      for (int i = 0; i < IPL; ++i) {
-        const int l = c0 + i * G + lane_g;
-        const long long id = decode_id(raw[i], dt);
-        const bool live = l < L;
-        const bool in_range = id >= 0 && id < fd.vocab;
-        if (live && !in_range && status != nullptr) atomicOr(status, kStatusBadId);
-        const bool use = live && in_range && !(id_pool && id == fd.mask_id);
-        const unsigned long long m = (__ballot(use) >> gshift) & gmask;
-        if (use) {
-          const int at = nvalid + __popcll(m & below);
-          my_id[at] = static_cast<int>(id);
-          my_pos[at] = begin + l;                          // < end <= nnz
-        }
-        nvalid += __popcll(m);
-      }
-      __builtin_amdgcn_wave_barrier();
-      int nmax = nvalid;
-#pragma unroll
-      for (int o = 32; o >= G && o > 0; o >>= 1) {
-        const int other = __shfl_xor(nmax, o, 64);
-        nmax = other > nmax ? other : nmax;
-      }
-      for (int k0 = 0; k0 < nmax; k0 += U * R) {
-        int idu[U], pu[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int k = k0 + u * R + sub;
-          idu[u] = (k < nvalid) ? my_id[k] : -1;
-          pu[u] = (k < nvalid) ? my_pos[k] : 0;
-        }
-        Frag r[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          r[u].zero();
-          if (idu[u] >= 0) r[u].load(fd.table + static_cast<long long>(idu[u]) * dim, dim, lane_w);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const float d = group_sum<W>(row_dot(r[u], dy));  // (every lane of the wave is here: the loop bounds are wave-uniform)
-          if (idu[u] >= 0 && lane_w == 0) dw[pu[u]] = d;
-        }
-      }
-      __builtin_amdgcn_wave_barrier();
-    }
-  }
-}
-
-// the segment kernels' grid: fixed, grid-striding over the segment count in the workspace header
+// the segment launches' grid: fixed, grid-striding over the segment count in the workspace header
 constexpr int kSegBlocks = kCUs * 4;
 
-template <int G, int NV, bool VEC, int MODE = kWalk>
-static int launch_csr(const BagPack& pack, int F, int64_t B, float* out, int64_t stride_b, float* row_scale, int* status,
-                      hipStream_t s, const LongArgs& la = LongArgs{}) {
-  constexpr int SG = (G <= 8) ? 16 : ((G == 16) ? 32 : 64);    // lanes per bag: launch_fwd's rule for sequences
+template <class Op, int G, int NV, bool VEC, int MODE>
+static int launch_bag_walk(const BagPack& pack, int F, int64_t B, const typename Op::Args& args, int* status, hipStream_t s,
+                           const LongArgs& la) {
+  constexpr int SG = seq_group_lanes(G);                  // lanes per bag
   long long blocks = ((B + 64 / SG - 1) / (64 / SG) * F + 3) / 4;   // 4 wave tasks per workgroup
   const long long cap = static_cast<long long>(kCUs) * 64;
   if (blocks > cap) blocks = cap;
   if (blocks < 1) blocks = 1;
   if (MODE == kSegments) blocks = kSegBlocks;
-  hipLaunchKernelGGL((embed_csr_kernel<SG, SG / G, NV, VEC, MODE>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, pack,
-                     F, static_cast<long long>(B), out, static_cast<long long>(stride_b), row_scale, status, la);
-  return check_launch("embed_csr_kernel");
+  hipLaunchKernelGGL((bag_walk_kernel<Op, SG, SG / G, NV, VEC, MODE>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, pack,
+                     args, F, static_cast<long long>(B), status, la);
+  return check_launch(Op::kName);
 }
 
-template <bool VEC, int MODE = kWalk>
-static int dispatch_csr(int units, const BagPack& pack, int F, int64_t B, float* out, int64_t stride_b, float* row_scale,
-                        int* status, hipStream_t s, const LongArgs& la = LongArgs{}) {
+template <class Op, bool VEC, int MODE>
+static int dispatch_bag_walk(int units, const BagPack& pack, int F, int64_t B, const typename Op::Args& args, int* status,
+                             hipStream_t s, const LongArgs& la) {
   switch (pow2_ceil(units)) {
-    case 1: return launch_csr<1, 1, VEC, MODE>(pack, F, B, out, stride_b, row_scale, status, s, la);
-    case 2: return launch_csr<2, 1, VEC, MODE>(pack, F, B, out, stride_b, row_scale, status, s, la);
-    case 4: return launch_csr<4, 1, VEC, MODE>(pack, F, B, out, stride_b, row_scale, status, s, la);
-    case 8: return launch_csr<8, 1, VEC, MODE>(pack, F, B, out, stride_b, row_scale, status, s, la);
-    case 16: return launch_csr<16, 1, VEC, MODE>(pack, F, B, out, stride_b, row_scale, status, s, la);
-    case 32: return launch_csr<32, 1, VEC, MODE>(pack, F, B, out, stride_b, row_scale, status, s, la);
-    case 64: return launch_csr<64, 1, VEC, MODE>(pack, F, B, out, stride_b, row_scale, status, s, la);
-    case 128: return launch_csr<64, 2, VEC, MODE>(pack, F, B, out, stride_b, row_scale, status, s, la);
-    case 256: return launch_csr<64, 4, VEC, MODE>(pack, F, B, out, stride_b, row_scale, status, s, la);
+    case 1: return launch_bag_walk<Op, 1, 1, VEC, MODE>(pack, F, B, args, status, s, la);
+    case 2: return launch_bag_walk<Op, 2, 1, VEC, MODE>(pack, F, B, args, status, s, la);
+    case 4: return launch_bag_walk<Op, 4, 1, VEC, MODE>(pack, F, B, args, status, s, la);
+    case 8: return launch_bag_walk<Op, 8, 1, VEC, MODE>(pack, F, B, args, status, s, la);
+    case 16: return launch_bag_walk<Op, 16, 1, VEC, MODE>(pack, F, B, args, status, s, la);
+    case 32: return launch_bag_walk<Op, 32, 1, VEC, MODE>(pack, F, B, args, status, s, la);
+    case 64: return launch_bag_walk<Op, 64, 1, VEC, MODE>(pack, F, B, args, status, s, la);
+    case 128: return launch_bag_walk<Op, 64, 2, VEC, MODE>(pack, F, B, args, status, s, la);
+    case 256: return launch_bag_walk<Op, 64, 4, VEC, MODE>(pack, F, B, args, status, s, la);
     default: return fail(RBX_ERR_UNSUPPORTED, "embedding dim too large for one lane group (units=%d)", units);
   }
 }
 
-// launch_csr / dispatch_csr for the two kernels of the weighted path: GRAD = false the weighted forward (writes `out`),
-// GRAD = true the weight gradient (reads `dout`, writes through `dw`)
-template <bool GRAD, int G, int NV, bool VEC, int MODE = kWalk>
-static int launch_csr_weighted(const BagPack& pack, const BagWeights& w, const BagWeightGrads& dw, int F, int64_t B,
-                               float* out, const float* dout, int64_t stride_b, int* status, hipStream_t s,
-                               const LongArgs& la = LongArgs{}) {
-  constexpr int SG = (G <= 8) ? 16 : ((G == 16) ? 32 : 64);
-  long long blocks = ((B + 64 / SG - 1) / (64 / SG) * F + 3) / 4;
-  const long long cap = static_cast<long long>(kCUs) * 64;
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  if (MODE == kSegments) blocks = kSegBlocks;
-  if constexpr (GRAD) {
-    hipLaunchKernelGGL((csr_weight_grad_kernel<SG, SG / G, NV, VEC, MODE>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s,
-                       pack, dw, F, static_cast<long long>(B), dout, static_cast<long long>(stride_b), status, la);
-    return check_launch("csr_weight_grad_kernel");
-  } else {
-    hipLaunchKernelGGL((embed_csr_weighted_kernel<SG, SG / G, NV, VEC, MODE>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0,
-                       s, pack, w, F, static_cast<long long>(B), out, static_cast<long long>(stride_b), status, la);
-    return check_launch("embed_csr_weighted_kernel");
-  }
-}
-
-template <bool GRAD, bool VEC, int MODE = kWalk>
-static int dispatch_csr_weighted(int units, const BagPack& pack, const BagWeights& w, const BagWeightGrads& dw, int F, int64_t B,
-                                 float* out, const float* dout, int64_t stride_b, int* status, hipStream_t s,
-                                 const LongArgs& la = LongArgs{}) {
-  switch (pow2_ceil(units)) {
-    case 1: return launch_csr_weighted<GRAD, 1, 1, VEC, MODE>(pack, w, dw, F, B, out, dout, stride_b, status, s, la);
-    case 2: return launch_csr_weighted<GRAD, 2, 1, VEC, MODE>(pack, w, dw, F, B, out, dout, stride_b, status, s, la);
-    case 4: return launch_csr_weighted<GRAD, 4, 1, VEC, MODE>(pack, w, dw, F, B, out, dout, stride_b, status, s, la);
-    case 8: return launch_csr_weighted<GRAD, 8, 1, VEC, MODE>(pack, w, dw, F, B, out, dout, stride_b, status, s, la);
-    case 16: return launch_csr_weighted<GRAD, 16, 1, VEC, MODE>(pack, w, dw, F, B, out, dout, stride_b, status, s, la);
-    case 32: return launch_csr_weighted<GRAD, 32, 1, VEC, MODE>(pack, w, dw, F, B, out, dout, stride_b, status, s, la);
-    case 64: return launch_csr_weighted<GRAD, 64, 1, VEC, MODE>(pack, w, dw, F, B, out, dout, stride_b, status, s, la);
-    case 128: return launch_csr_weighted<GRAD, 64, 2, VEC, MODE>(pack, w, dw, F, B, out, dout, stride_b, status, s, la);
-    case 256: return launch_csr_weighted<GRAD, 64, 4, VEC, MODE>(pack, w, dw, F, B, out, dout, stride_b, status, s, la);
-    default: return fail(RBX_ERR_UNSUPPORTED, "embedding dim too large for one lane group (units=%d)", units);
+// the (float4 | scalar) x mode choice of a launch, made at run time
+template <class Op>
+static int bag_walk(bool vec, int mode, int units, const BagPack& pack, int F, int64_t B, const typename Op::Args& args,
+                    int* status, hipStream_t s, const LongArgs& la) {
+  switch (mode) {
+    case kWalk: return vec ? dispatch_bag_walk<Op, true, kWalk>(units, pack, F, B, args, status, s, la)
+                           : dispatch_bag_walk<Op, false, kWalk>(units, pack, F, B, args, status, s, la);
+    case kHandOff: return vec ? dispatch_bag_walk<Op, true, kHandOff>(units, pack, F, B, args, status, s, la)
+                              : dispatch_bag_walk<Op, false, kHandOff>(units, pack, F, B, args, status, s, la);
+    default: return vec ? dispatch_bag_walk<Op, true, kSegments>(units, pack, F, B, args, status, s, la)
+                        : dispatch_bag_walk<Op, false, kSegments>(units, pack, F, B, args, status, s, la);
   }
 }
 
@@ -686,21 +515,35 @@ static int check_weighted_pools(const rbx_bag_t* bags, int n, const void* const*
 
 static int compact(int64_t v) { return (v == RBX_NO_ID || v < INT_MIN || v > INT_MAX) ? kNoId : static_cast<int>(v); }
 
+// The size checks of pack_bags and long_plan (which also sees descriptors whose pointers are not set yet): i < 0 the
+// call's bags / n / batch, otherwise the dim / nnz of descriptor i.
+static int check_sizes(const rbx_bag_t* bags, int n, int64_t batch, int i) {
+  if (i < 0) {
+    if (bags == nullptr) return fail(RBX_ERR_INVALID, "bags is NULL");
+    if (n <= 0 || n > RBX_MAX_BAGS) return fail(RBX_ERR_INVALID, "n_bags=%d not in [1,%d]", n, RBX_MAX_BAGS);
+    if (batch < 0) return fail(RBX_ERR_INVALID, "negative batch");
+    if (batch > static_cast<int64_t>(kLocalMask)) return fail(RBX_ERR_UNSUPPORTED, "batch=%lld exceeds 2^26 bags per call", (long long)batch);
+    return RBX_OK;
+  }
+  const rbx_bag_t& g = bags[i];
+  if (g.dim <= 0 || g.dim > 1024) return fail(RBX_ERR_UNSUPPORTED, "bag %d: dim=%d not in [1,1024]", i, g.dim);
+  if (g.nnz < 0 || g.nnz > static_cast<int64_t>(kLocalMask))
+    return fail(RBX_ERR_UNSUPPORTED, "bag %d: nnz=%lld not in [0, 2^26]", i, (long long)g.nnz);
+  return RBX_OK;
+}
+
 // Validate the public descriptors; convert descriptor i into out[i] (slot = i).
 static int pack_bags(const rbx_bag_t* bags, int n, int64_t batch, BagK* out) {
-  if (bags == nullptr) return fail(RBX_ERR_INVALID, "bags is NULL");
-  if (n <= 0 || n > RBX_MAX_BAGS) return fail(RBX_ERR_INVALID, "n_bags=%d not in [1,%d]", n, RBX_MAX_BAGS);
-  if (batch < 0) return fail(RBX_ERR_INVALID, "negative batch");
-  if (batch > static_cast<int64_t>(kLocalMask)) return fail(RBX_ERR_UNSUPPORTED, "batch=%lld exceeds 2^26 bags per call", (long long)batch);
+  int rc = check_sizes(bags, n, batch, -1);
+  if (rc != RBX_OK) return rc;
   unsigned long long total = 0;
   for (int i = 0; i < n; ++i) {
     const rbx_bag_t& g = bags[i];
     if (g.pool == RBX_POOL_NONE || g.pool == RBX_POOL_CONCAT)
       return fail(RBX_ERR_UNSUPPORTED, "bag %d: pool mode %d keeps one slot per id; ragged bags are pooled (sum / mean)", i, g.pool);
     if (g.pool < RBX_POOL_NONE || g.pool > RBX_POOL_CONCAT) return fail(RBX_ERR_INVALID, "bag %d: bad pool mode %d", i, g.pool);
-    if (g.dim <= 0 || g.dim > 1024) return fail(RBX_ERR_UNSUPPORTED, "bag %d: dim=%d not in [1,1024]", i, g.dim);
-    if (g.nnz < 0 || g.nnz > static_cast<int64_t>(kLocalMask))
-      return fail(RBX_ERR_UNSUPPORTED, "bag %d: nnz=%lld not in [0, 2^26]", i, (long long)g.nnz);
+    rc = check_sizes(bags, n, batch, i);
+    if (rc != RBX_OK) return rc;
     if (g.nnz > 0 && g.indices == nullptr) return fail(RBX_ERR_INVALID, "bag %d: indices is NULL", i);
     if (g.offsets == nullptr) return fail(RBX_ERR_INVALID, "bag %d: offsets is NULL", i);
     if (g.table == nullptr) return fail(RBX_ERR_INVALID, "bag %d: table is NULL", i);
@@ -1029,18 +872,15 @@ struct LongPlan {
 constexpr size_t kLongHeader = 256;
 
 static int long_plan(const rbx_bag_t* bags, int n, int64_t batch, int64_t threshold, LongPlan* lp) {
-  if (bags == nullptr) return fail(RBX_ERR_INVALID, "bags is NULL");
-  if (n <= 0 || n > RBX_MAX_BAGS) return fail(RBX_ERR_INVALID, "n_bags=%d not in [1,%d]", n, RBX_MAX_BAGS);
-  if (batch < 0) return fail(RBX_ERR_INVALID, "negative batch");
-  if (batch > static_cast<int64_t>(kLocalMask)) return fail(RBX_ERR_UNSUPPORTED, "batch=%lld exceeds 2^26 bags per call", (long long)batch);
+  int rc = check_sizes(bags, n, batch, -1);
+  if (rc != RBX_OK) return rc;
   if (threshold < 0) return fail(RBX_ERR_INVALID, "negative long_threshold");
   long long cap_bags = 0, cap_segs = 0;
   int dim = 1;
   for (int i = 0; i < n; ++i) {
     const rbx_bag_t& g = bags[i];
-    if (g.dim <= 0 || g.dim > 1024) return fail(RBX_ERR_UNSUPPORTED, "bag %d: dim=%d not in [1,1024]", i, g.dim);
-    if (g.nnz < 0 || g.nnz > static_cast<int64_t>(kLocalMask))
-      return fail(RBX_ERR_UNSUPPORTED, "bag %d: nnz=%lld not in [0, 2^26]", i, (long long)g.nnz);
+    rc = check_sizes(bags, n, batch, i);
+    if (rc != RBX_OK) return rc;
     if (g.dim > dim) dim = g.dim;
     if (threshold == 0) continue;
     const long long most = g.nnz / threshold < batch ? g.nnz / threshold : batch;
@@ -1087,10 +927,44 @@ static int long_begin(const rbx_bag_t* bags, int n, int64_t batch, int64_t thres
   return RBX_OK;
 }
 
-// the forward of both long entry points: d_weights == NULL is rbx_embed_csr_fwd_long
-static int csr_fwd_long(const rbx_bag_t* bags, int n_bags, int64_t batch, int64_t threshold, const float* const* d_weights,
-                        bool weighted_call, float* d_out, int64_t out_stride_b, float* d_row_scale, void* d_workspace,
-                        size_t workspace_bytes, int* d_status, hipStream_t s) {
+// ---- host side of the bag walk: launch classes, the forward driver, the weight-gradient driver -------------------------
+// The descriptors of a call sorted into launch classes: class k = (float4 ? 0 : 1) + (2 when the descriptor walks with a
+// per-lookup array of the forward: its weights).  `per` is that array per descriptor (NULL: none); with `only_per` a
+// descriptor without one takes no part and the classes are 0 / 1 (the weight gradient).  Every dim is checked here, in
+// front of the first memset or launch, so a refused call writes nothing.
+template <class T>
+struct BagClasses {
+  BagPack pack[4];
+  BagPtrs<T> ptr[4], whole = {};    // the arrays of a class in pack order; of the whole call by descriptor index
+  int cnt[4] = {0, 0, 0, 0}, units[4] = {1, 1, 1, 1};
+};
+
+template <class T>
+static int classify_bags(const rbx_bag_t* bags, const BagPack& all, int n, const float* rows, int64_t stride_b, T* const* per,
+                         bool only_per, BagClasses<T>* c) {
+  for (int i = 0; i < n; ++i) {
+    T* const p = per != nullptr ? per[i] : nullptr;
+    if (only_per && p == nullptr) continue;
+    const bool vec = bag_vec_ok(bags[i], rows, stride_b);
+    const int k = (vec ? 0 : 1) + (p != nullptr && !only_per ? 2 : 0);
+    c->ptr[k].p[c->cnt[k]] = p;
+    c->whole.p[i] = p;
+    c->pack[k].f[c->cnt[k]++] = all.f[i];
+    const int u = vec ? bags[i].dim / 4 : bags[i].dim;
+    if (u > c->units[k]) c->units[k] = u;
+  }
+  for (int k = 0; k < 4; ++k)
+    if (c->cnt[k] > 0 && pow2_ceil(c->units[k]) > 256)
+      return fail(RBX_ERR_UNSUPPORTED, "embedding dim too large for one lane group (%s units=%d)", k % 2 == 0 ? "float4" : "scalar",
+                  c->units[k]);
+  return RBX_OK;
+}
+
+// The four forward entry points.  weighted_call: d_weights is looked at (NULL entries walk unweighted, without a row
+// scale: the caller passes none); has_long: the `_long` calls, whose bags of >= threshold ids go out in segments.
+static int csr_forward(const rbx_bag_t* bags, int n_bags, int64_t batch, bool has_long, int64_t threshold,
+                       const float* const* d_weights, bool weighted_call, float* d_out, int64_t out_stride_b, float* d_row_scale,
+                       void* d_workspace, size_t workspace_bytes, int* d_status, hipStream_t s) {
   BagPack all;
   int rc = pack_bags(bags, n_bags, batch, all.f);
   if (rc != RBX_OK) return rc;
@@ -1098,60 +972,39 @@ static int csr_fwd_long(const rbx_bag_t* bags, int n_bags, int64_t batch, int64_
     rc = check_weighted_pools(bags, n_bags, reinterpret_cast<const void* const*>(d_weights), "a weight array");
     if (rc != RBX_OK) return rc;
   }
+  if (!has_long && batch == 0) return RBX_OK;
   if (batch > 0 && d_out == nullptr) return fail(RBX_ERR_INVALID, "d_out is NULL");
-  BagPack pack[4];
-  BagWeights wts[2], wall = {};
-  int cnt[4] = {0, 0, 0, 0}, units[4] = {1, 1, 1, 1};
-  for (int i = 0; i < n_bags; ++i) {
-    const bool vec = bag_vec_ok(bags[i], d_out, out_stride_b);
-    const float* w = d_weights != nullptr ? d_weights[i] : nullptr;
-    const int k = (vec ? 0 : 1) + (w != nullptr ? 2 : 0);
-    if (w != nullptr) wts[k - 2].w[cnt[k]] = w;
-    wall.w[i] = w;
-    pack[k].f[cnt[k]++] = all.f[i];
-    const int u = vec ? bags[i].dim / 4 : bags[i].dim;
-    if (u > units[k]) units[k] = u;
-  }
-  for (int k = 0; k < 4; ++k)
-    if (cnt[k] > 0 && pow2_ceil(units[k]) > 256)
-      return fail(RBX_ERR_UNSUPPORTED, "embedding dim too large for one lane group (%s units=%d)", k % 2 == 0 ? "float4" : "scalar",
-                  units[k]);
-  LongPlan lp;
-  bool on = false;
-  rc = long_begin(bags, n_bags, batch, threshold, d_workspace, workspace_bytes, s, &lp, &on);
+  BagClasses<const float> c;
+  rc = classify_bags(bags, all, n_bags, d_out, out_stride_b, d_weights, false, &c);
   if (rc != RBX_OK) return rc;
-  if (batch == 0) return RBX_OK;
-  LongArgs la = long_args(lp, d_workspace);
-  const BagWeightGrads none = {};
-  // lane-group kernels of every class first (they fill the list), then the classes' segment kernels, then one finish
+  LongPlan lp;
+  LongArgs la = {};
+  bool on = false;
+  if (has_long) {
+    rc = long_begin(bags, n_bags, batch, threshold, d_workspace, workspace_bytes, s, &lp, &on);
+    if (rc != RBX_OK) return rc;
+    if (batch == 0) return RBX_OK;
+    la = long_args(lp, d_workspace);
+  }
+  // lane-group launches of every class first (they fill the list), then the classes' segment launches, then one finish
   for (int k = 0; k < 4; ++k) {
-    if (cnt[k] == 0) continue;
+    if (c.cnt[k] == 0) continue;
     la.cls = k;
-    const bool vec = k % 2 == 0;
-    if (k < 2) {
-      if (!on) rc = vec ? dispatch_csr<true>(units[k], pack[k], cnt[k], batch, d_out, out_stride_b, d_row_scale, d_status, s)
-                        : dispatch_csr<false>(units[k], pack[k], cnt[k], batch, d_out, out_stride_b, d_row_scale, d_status, s);
-      else rc = vec ? dispatch_csr<true, kHandOff>(units[k], pack[k], cnt[k], batch, d_out, out_stride_b, d_row_scale, d_status, s, la)
-                    : dispatch_csr<false, kHandOff>(units[k], pack[k], cnt[k], batch, d_out, out_stride_b, d_row_scale, d_status, s, la);
-    } else {
-      const BagWeights& w = wts[k - 2];
-      if (!on) rc = vec ? dispatch_csr_weighted<false, true>(units[k], pack[k], w, none, cnt[k], batch, d_out, nullptr, out_stride_b, d_status, s)
-                        : dispatch_csr_weighted<false, false>(units[k], pack[k], w, none, cnt[k], batch, d_out, nullptr, out_stride_b, d_status, s);
-      else rc = vec ? dispatch_csr_weighted<false, true, kHandOff>(units[k], pack[k], w, none, cnt[k], batch, d_out, nullptr, out_stride_b, d_status, s, la)
-                    : dispatch_csr_weighted<false, false, kHandOff>(units[k], pack[k], w, none, cnt[k], batch, d_out, nullptr, out_stride_b, d_status, s, la);
-    }
+    const int mode = on ? kHandOff : kWalk;
+    rc = k < 2 ? bag_walk<PoolOp>(k % 2 == 0, mode, c.units[k], c.pack[k], c.cnt[k], batch, {d_out, out_stride_b, d_row_scale},
+                                  d_status, s, la)
+               : bag_walk<WeightedPoolOp>(k % 2 == 0, mode, c.units[k], c.pack[k], c.cnt[k], batch,
+                                          {c.ptr[k], d_out, out_stride_b}, d_status, s, la);
     if (rc != RBX_OK) return rc;
   }
   if (!on) return RBX_OK;
-  for (int k = 0; k < 4; ++k) {
-    if (cnt[k] == 0) continue;
+  for (int k = 0; k < 4; ++k) {                             // every descriptor by index (LongRec::desc); the finish scales
+    if (c.cnt[k] == 0) continue;
     la.cls = k;
-    switch (k) {
-      case 0: rc = dispatch_csr<true, kSegments>(units[k], all, n_bags, batch, d_out, out_stride_b, nullptr, d_status, s, la); break;
-      case 1: rc = dispatch_csr<false, kSegments>(units[k], all, n_bags, batch, d_out, out_stride_b, nullptr, d_status, s, la); break;
-      case 2: rc = dispatch_csr_weighted<false, true, kSegments>(units[k], all, wall, none, n_bags, batch, d_out, nullptr, out_stride_b, d_status, s, la); break;
-      default: rc = dispatch_csr_weighted<false, false, kSegments>(units[k], all, wall, none, n_bags, batch, d_out, nullptr, out_stride_b, d_status, s, la); break;
-    }
+    rc = k < 2 ? bag_walk<PoolOp>(k % 2 == 0, kSegments, c.units[k], all, n_bags, batch, {d_out, out_stride_b, nullptr}, d_status,
+                                  s, la)
+               : bag_walk<WeightedPoolOp>(k % 2 == 0, kSegments, c.units[k], all, n_bags, batch, {c.whole, d_out, out_stride_b},
+                                          d_status, s, la);
     if (rc != RBX_OK) return rc;
   }
   long long fb = (static_cast<long long>(lp.cap_bags) + 3) / 4;
@@ -1161,39 +1014,58 @@ static int csr_fwd_long(const rbx_bag_t* bags, int n_bags, int64_t batch, int64_
   return check_launch("csr_long_finish_kernel");
 }
 
+// Both weight-gradient entry points; a descriptor takes part when it has somewhere to put its gradient.
+static int csr_weight_grad(const rbx_bag_t* bags, int n_bags, int64_t batch, bool has_long, int64_t threshold, const float* d_dout,
+                           int64_t out_stride_b, float* const* d_dweights, void* d_workspace, size_t workspace_bytes,
+                           int* d_status, hipStream_t s) {
+  BagPack all;
+  int rc = pack_bags(bags, n_bags, batch, all.f);
+  if (rc != RBX_OK) return rc;
+  if (d_dweights == nullptr) return fail(RBX_ERR_INVALID, "d_dweights is NULL");
+  rc = check_weighted_pools(bags, n_bags, reinterpret_cast<const void* const*>(d_dweights), "a weight gradient");
+  if (rc != RBX_OK) return rc;
+  if (batch > 0 && d_dout == nullptr) return fail(RBX_ERR_INVALID, "d_dout is NULL");
+  BagClasses<float> c;
+  rc = classify_bags(bags, all, n_bags, d_dout, out_stride_b, d_dweights, true, &c);
+  if (rc != RBX_OK) return rc;
+  LongPlan lp;
+  LongArgs la = {};
+  bool on = false;
+  if (has_long) {
+    rc = long_begin(bags, n_bags, batch, threshold, d_workspace, workspace_bytes, s, &lp, &on);
+    if (rc != RBX_OK) return rc;
+    la = long_args(lp, d_workspace);
+  }
+  // dw is fully defined after the call: everything the kernel does not write (masked and out-of-range ids, positions
+  // outside every bag, a batch of zero bags) is cleared here
+  for (int i = 0; i < n_bags; ++i)
+    if (d_dweights[i] != nullptr && bags[i].nnz > 0 &&
+        hipMemsetAsync(d_dweights[i], 0, static_cast<size_t>(bags[i].nnz) * 4, s) != hipSuccess)
+      return fail(RBX_ERR_LAUNCH, "clearing a weight gradient failed");
+  if (batch == 0) return RBX_OK;
+  for (int k = 0; k < 2; ++k) {
+    if (c.cnt[k] == 0) continue;
+    la.cls = k;
+    rc = bag_walk<WeightGradOp>(k == 0, on ? kHandOff : kWalk, c.units[k], c.pack[k], c.cnt[k], batch,
+                                {c.ptr[k], d_dout, out_stride_b}, d_status, s, la);
+    if (rc != RBX_OK) return rc;
+  }
+  for (int k = 0; on && k < 2; ++k) {                      // the same segment tasks, nothing to combine
+    if (c.cnt[k] == 0) continue;
+    la.cls = k;
+    rc = bag_walk<WeightGradOp>(k == 0, kSegments, c.units[k], all, n_bags, batch, {c.whole, d_dout, out_stride_b}, d_status, s,
+                                la);
+    if (rc != RBX_OK) return rc;
+  }
+  return RBX_OK;
+}
+
 }  // namespace rbx
 
 extern "C" int rbx_embed_csr_fwd(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, float* d_out, int64_t out_stride_b,
                                  float* d_row_scale, int32_t* d_status, void* stream) {
-  using namespace rbx;
-  BagK all[RBX_MAX_BAGS];
-  int rc = pack_bags(bags, n_bags, batch, all);
-  if (rc != RBX_OK) return rc;
-  if (batch == 0) return RBX_OK;
-  if (d_out == nullptr) return fail(RBX_ERR_INVALID, "d_out is NULL");
-  // (float4 | scalar) launches; every dim is checked before the first launch, so a refused call writes nothing
-  BagPack pack[2];
-  int cnt[2] = {0, 0}, units[2] = {1, 1};
-  for (int i = 0; i < n_bags; ++i) {
-    const bool vec = bag_vec_ok(bags[i], d_out, out_stride_b);
-    const int k = vec ? 0 : 1;
-    pack[k].f[cnt[k]++] = all[i];
-    const int u = vec ? bags[i].dim / 4 : bags[i].dim;
-    if (u > units[k]) units[k] = u;
-  }
-  for (int k = 0; k < 2; ++k)
-    if (cnt[k] > 0 && pow2_ceil(units[k]) > 256)
-      return fail(RBX_ERR_UNSUPPORTED, "embedding dim too large for one lane group (%s units=%d)", k == 0 ? "float4" : "scalar",
-                  units[k]);
-  for (int k = 0; k < 2; ++k) {
-    if (cnt[k] == 0) continue;
-    rc = (k == 0) ? dispatch_csr<true>(units[k], pack[k], cnt[k], batch, d_out, out_stride_b, d_row_scale, d_status,
-                                       as_stream(stream))
-                  : dispatch_csr<false>(units[k], pack[k], cnt[k], batch, d_out, out_stride_b, d_row_scale, d_status,
-                                        as_stream(stream));
-    if (rc != RBX_OK) return rc;
-  }
-  return RBX_OK;
+  return rbx::csr_forward(bags, n_bags, batch, false, 0, nullptr, false, d_out, out_stride_b, d_row_scale, nullptr, 0, d_status,
+                          rbx::as_stream(stream));
 }
 
 extern "C" size_t rbx_embed_csr_bwd_workspace_size(const rbx_bag_t* bags, int32_t n_bags, int64_t batch) {
@@ -1225,47 +1097,8 @@ extern "C" int rbx_embed_csr_bwd(const rbx_bag_t* bags, int32_t n_bags, int64_t 
 // ---- per-sample weights ----------------------------------------------------------------------------------------------
 extern "C" int rbx_embed_csr_fwd_weighted(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, const float* const* d_weights,
                                           float* d_out, int64_t out_stride_b, int32_t* d_status, void* stream) {
-  using namespace rbx;
-  BagK all[RBX_MAX_BAGS];
-  int rc = pack_bags(bags, n_bags, batch, all);
-  if (rc != RBX_OK) return rc;
-  rc = check_weighted_pools(bags, n_bags, reinterpret_cast<const void* const*>(d_weights), "a weight array");
-  if (rc != RBX_OK) return rc;
-  if (batch == 0) return RBX_OK;
-  if (d_out == nullptr) return fail(RBX_ERR_INVALID, "d_out is NULL");
-  // (float4 | scalar) x (unweighted | weighted) launches: a descriptor without weights takes embed_csr_kernel as it
-  // would in rbx_embed_csr_fwd.  Every dim is checked before the first launch, so a refused call writes nothing.
-  BagPack pack[4];
-  BagWeights wts[2];
-  int cnt[4] = {0, 0, 0, 0}, units[4] = {1, 1, 1, 1};
-  for (int i = 0; i < n_bags; ++i) {
-    const bool vec = bag_vec_ok(bags[i], d_out, out_stride_b);
-    const float* w = d_weights != nullptr ? d_weights[i] : nullptr;
-    const int k = (vec ? 0 : 1) + (w != nullptr ? 2 : 0);
-    if (w != nullptr) wts[k - 2].w[cnt[k]] = w;
-    pack[k].f[cnt[k]++] = all[i];
-    const int u = vec ? bags[i].dim / 4 : bags[i].dim;
-    if (u > units[k]) units[k] = u;
-  }
-  for (int k = 0; k < 4; ++k)
-    if (cnt[k] > 0 && pow2_ceil(units[k]) > 256)
-      return fail(RBX_ERR_UNSUPPORTED, "embedding dim too large for one lane group (%s units=%d)", k % 2 == 0 ? "float4" : "scalar",
-                  units[k]);
-  hipStream_t s = as_stream(stream);
-  const BagWeightGrads none = {};
-  for (int k = 0; k < 4; ++k) {
-    if (cnt[k] == 0) continue;
-    switch (k) {
-      case 0: rc = dispatch_csr<true>(units[k], pack[k], cnt[k], batch, d_out, out_stride_b, nullptr, d_status, s); break;
-      case 1: rc = dispatch_csr<false>(units[k], pack[k], cnt[k], batch, d_out, out_stride_b, nullptr, d_status, s); break;
-      case 2: rc = dispatch_csr_weighted<false, true>(units[k], pack[k], wts[0], none, cnt[k], batch, d_out, nullptr, out_stride_b,
-                                                      d_status, s); break;
-      default: rc = dispatch_csr_weighted<false, false>(units[k], pack[k], wts[1], none, cnt[k], batch, d_out, nullptr,
-                                                        out_stride_b, d_status, s); break;
-    }
-    if (rc != RBX_OK) return rc;
-  }
-  return RBX_OK;
+  return rbx::csr_forward(bags, n_bags, batch, false, 0, d_weights, true, d_out, out_stride_b, nullptr, nullptr, 0, d_status,
+                          rbx::as_stream(stream));
 }
 
 extern "C" int rbx_embed_csr_sort_weighted(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, void* d_workspace,
@@ -1311,48 +1144,8 @@ extern "C" int rbx_embed_csr_bwd_weighted(const rbx_bag_t* bags, int32_t n_bags,
 
 extern "C" int rbx_embed_csr_weight_grad(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, const float* d_dout,
                                          int64_t out_stride_b, float* const* d_dweights, int32_t* d_status, void* stream) {
-  using namespace rbx;
-  BagK all[RBX_MAX_BAGS];
-  int rc = pack_bags(bags, n_bags, batch, all);
-  if (rc != RBX_OK) return rc;
-  if (d_dweights == nullptr) return fail(RBX_ERR_INVALID, "d_dweights is NULL");
-  rc = check_weighted_pools(bags, n_bags, reinterpret_cast<const void* const*>(d_dweights), "a weight gradient");
-  if (rc != RBX_OK) return rc;
-  if (batch > 0 && d_dout == nullptr) return fail(RBX_ERR_INVALID, "d_dout is NULL");
-  BagPack pack[2];
-  BagWeightGrads dws[2];
-  int cnt[2] = {0, 0}, units[2] = {1, 1};
-  for (int i = 0; i < n_bags; ++i) {
-    if (d_dweights[i] == nullptr) continue;
-    const bool vec = bag_vec_ok(bags[i], d_dout, out_stride_b);
-    const int k = vec ? 0 : 1;
-    dws[k].dw[cnt[k]] = d_dweights[i];
-    pack[k].f[cnt[k]++] = all[i];
-    const int u = vec ? bags[i].dim / 4 : bags[i].dim;
-    if (u > units[k]) units[k] = u;
-  }
-  for (int k = 0; k < 2; ++k)
-    if (cnt[k] > 0 && pow2_ceil(units[k]) > 256)
-      return fail(RBX_ERR_UNSUPPORTED, "embedding dim too large for one lane group (%s units=%d)", k == 0 ? "float4" : "scalar",
-                  units[k]);
-  hipStream_t s = as_stream(stream);
-  // dw is fully defined after the call: everything the kernel does not write (masked and out-of-range ids, positions
-  // outside every bag, a batch of zero bags) is cleared here
-  for (int i = 0; i < n_bags; ++i)
-    if (d_dweights[i] != nullptr && bags[i].nnz > 0 &&
-        hipMemsetAsync(d_dweights[i], 0, static_cast<size_t>(bags[i].nnz) * 4, s) != hipSuccess)
-      return fail(RBX_ERR_LAUNCH, "clearing a weight gradient failed");
-  if (batch == 0) return RBX_OK;
-  const BagWeights none = {};
-  for (int k = 0; k < 2; ++k) {
-    if (cnt[k] == 0) continue;
-    rc = (k == 0) ? dispatch_csr_weighted<true, true>(units[k], pack[k], none, dws[k], cnt[k], batch, nullptr, d_dout, out_stride_b,
-                                                      d_status, s)
-                  : dispatch_csr_weighted<true, false>(units[k], pack[k], none, dws[k], cnt[k], batch, nullptr, d_dout,
-                                                       out_stride_b, d_status, s);
-    if (rc != RBX_OK) return rc;
-  }
-  return RBX_OK;
+  return rbx::csr_weight_grad(bags, n_bags, batch, false, 0, d_dout, out_stride_b, d_dweights, nullptr, 0, d_status,
+                              rbx::as_stream(stream));
 }
 
 // ---- the long-bag form (see LongArgs) ----------------------------------------------------------------------------------
@@ -1366,72 +1159,20 @@ extern "C" size_t rbx_embed_csr_fwd_long_workspace_size(const rbx_bag_t* bags, i
 extern "C" int rbx_embed_csr_fwd_long(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, int64_t long_threshold, float* d_out,
                                       int64_t out_stride_b, float* d_row_scale, void* d_workspace, size_t workspace_bytes,
                                       int32_t* d_status, void* stream) {
-  return rbx::csr_fwd_long(bags, n_bags, batch, long_threshold, nullptr, false, d_out, out_stride_b, d_row_scale, d_workspace,
-                           workspace_bytes, d_status, rbx::as_stream(stream));
+  return rbx::csr_forward(bags, n_bags, batch, true, long_threshold, nullptr, false, d_out, out_stride_b, d_row_scale, d_workspace,
+                          workspace_bytes, d_status, rbx::as_stream(stream));
 }
 
 extern "C" int rbx_embed_csr_fwd_weighted_long(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, int64_t long_threshold,
                                                const float* const* d_weights, float* d_out, int64_t out_stride_b,
                                                void* d_workspace, size_t workspace_bytes, int32_t* d_status, void* stream) {
-  return rbx::csr_fwd_long(bags, n_bags, batch, long_threshold, d_weights, true, d_out, out_stride_b, nullptr, d_workspace,
-                           workspace_bytes, d_status, rbx::as_stream(stream));
+  return rbx::csr_forward(bags, n_bags, batch, true, long_threshold, d_weights, true, d_out, out_stride_b, nullptr, d_workspace,
+                          workspace_bytes, d_status, rbx::as_stream(stream));
 }
 
 extern "C" int rbx_embed_csr_weight_grad_long(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, int64_t long_threshold,
                                               const float* d_dout, int64_t out_stride_b, float* const* d_dweights,
                                               void* d_workspace, size_t workspace_bytes, int32_t* d_status, void* stream) {
-  using namespace rbx;
-  BagPack all;
-  int rc = pack_bags(bags, n_bags, batch, all.f);
-  if (rc != RBX_OK) return rc;
-  if (d_dweights == nullptr) return fail(RBX_ERR_INVALID, "d_dweights is NULL");
-  rc = check_weighted_pools(bags, n_bags, reinterpret_cast<const void* const*>(d_dweights), "a weight gradient");
-  if (rc != RBX_OK) return rc;
-  if (batch > 0 && d_dout == nullptr) return fail(RBX_ERR_INVALID, "d_dout is NULL");
-  BagPack pack[2];
-  BagWeightGrads dws[2], dwall = {};
-  int cnt[2] = {0, 0}, units[2] = {1, 1};
-  for (int i = 0; i < n_bags; ++i) {
-    if (d_dweights[i] == nullptr) continue;
-    const bool vec = bag_vec_ok(bags[i], d_dout, out_stride_b);
-    const int k = vec ? 0 : 1;
-    dws[k].dw[cnt[k]] = d_dweights[i];
-    dwall.dw[i] = d_dweights[i];
-    pack[k].f[cnt[k]++] = all.f[i];
-    const int u = vec ? bags[i].dim / 4 : bags[i].dim;
-    if (u > units[k]) units[k] = u;
-  }
-  for (int k = 0; k < 2; ++k)
-    if (cnt[k] > 0 && pow2_ceil(units[k]) > 256)
-      return fail(RBX_ERR_UNSUPPORTED, "embedding dim too large for one lane group (%s units=%d)", k == 0 ? "float4" : "scalar",
-                  units[k]);
-  hipStream_t s = as_stream(stream);
-  LongPlan lp;
-  bool on = false;
-  rc = long_begin(bags, n_bags, batch, long_threshold, d_workspace, workspace_bytes, s, &lp, &on);
-  if (rc != RBX_OK) return rc;
-  for (int i = 0; i < n_bags; ++i)                          // dw is fully defined after the call, as in rbx_embed_csr_weight_grad
-    if (d_dweights[i] != nullptr && bags[i].nnz > 0 &&
-        hipMemsetAsync(d_dweights[i], 0, static_cast<size_t>(bags[i].nnz) * 4, s) != hipSuccess)
-      return fail(RBX_ERR_LAUNCH, "clearing a weight gradient failed");
-  if (batch == 0) return RBX_OK;
-  LongArgs la = long_args(lp, d_workspace);
-  const BagWeights none = {};
-  for (int k = 0; k < 2; ++k) {
-    if (cnt[k] == 0) continue;
-    la.cls = k;
-    if (!on) rc = (k == 0) ? dispatch_csr_weighted<true, true>(units[k], pack[k], none, dws[k], cnt[k], batch, nullptr, d_dout, out_stride_b, d_status, s)
-                           : dispatch_csr_weighted<true, false>(units[k], pack[k], none, dws[k], cnt[k], batch, nullptr, d_dout, out_stride_b, d_status, s);
-    else rc = (k == 0) ? dispatch_csr_weighted<true, true, kHandOff>(units[k], pack[k], none, dws[k], cnt[k], batch, nullptr, d_dout, out_stride_b, d_status, s, la)
-                       : dispatch_csr_weighted<true, false, kHandOff>(units[k], pack[k], none, dws[k], cnt[k], batch, nullptr, d_dout, out_stride_b, d_status, s, la);
-    if (rc != RBX_OK) return rc;
-  }
-  for (int k = 0; on && k < 2; ++k) {                      // the same segment tasks, nothing to combine
-    if (cnt[k] == 0) continue;
-    la.cls = k;
-    rc = (k == 0) ? dispatch_csr_weighted<true, true, kSegments>(units[k], all, none, dwall, n_bags, batch, nullptr, d_dout, out_stride_b, d_status, s, la)
-                  : dispatch_csr_weighted<true, false, kSegments>(units[k], all, none, dwall, n_bags, batch, nullptr, d_dout, out_stride_b, d_status, s, la);
-    if (rc != RBX_OK) return rc;
-  }
-  return RBX_OK;
+  return rbx::csr_weight_grad(bags, n_bags, batch, true, long_threshold, d_dout, out_stride_b, d_dweights, d_workspace,
+                              workspace_bytes, d_status, rbx::as_stream(stream));
 }

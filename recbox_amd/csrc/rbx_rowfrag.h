@@ -5,6 +5,15 @@
 
 namespace rbx {
 
+// The shape of the pooled gather, shared by embed_seq_kernel and bag_walk_kernel: the two are bit-equal on the same live
+// ids because chunks (G * kSeqIpl ids), row batches and sub-group counts are the same numbers, defined once.
+constexpr int kSeqWaves = 4;           // waves per SIMD the kernels are bounded for
+constexpr int kSeqU = 4;               // rows in flight per lane
+constexpr int kSeqIpl = 4;             // ids per lane per chunk (chunk = 64 .. 256 lookups)
+// lanes of the group that pools one (sample, sequence feature) or one bag, for rows of G lanes: narrow rows share a
+// wider group as R = seq_group_lanes(G) / G sub-groups
+constexpr int seq_group_lanes(int G) { return (G <= 8) ? 16 : ((G == 16) ? 32 : 64); }
+
 template <bool VEC>
 struct Acc;
 template <>

@@ -8,7 +8,7 @@ are restated in groups -- the few bags of several hundred ids at L = Lmax, the o
 and the groups' outputs, gradients and absolute sums are merged into one ``Oracle`` (gradients are sums over samples).
 The forward constant is max(C_BOUND, Lmax + 2) on every row.
 
-Forms: embed_csr_kernel<SG, R, NV, VEC> takes the instantiation embed_seq_kernel takes for the dim (the table in
+Forms: bag_walk_kernel<PoolOp, SG, R, NV, VEC> takes the instantiation embed_seq_kernel takes for the dim (the table in
 tests/test_gpu_embed_dims.py), and sums a bag in that kernel's order: the outputs of the id-masked pools are bit-equal
 to the padded call's at every dim and every bag length (there is no separate long-bag form; none is exempt)."""
 import pytest
