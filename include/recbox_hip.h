@@ -426,6 +426,15 @@ int rbx_fm_quad(int32_t enable);
 int rbx_sort_chained(int32_t enable);
 int rbx_fm_rezero(const rbx_field_t* emb, const rbx_field_t* lr, int32_t n_fields, int64_t batch,
                   void* d_workspace, size_t workspace_bytes, void* stream);
+/* rbx_fm_rezero(d_rezero_workspace) followed by rbx_fm_sort_phases(d_sort_workspace, phases = 1) -- the head of a step with
+ * persistent gradients, same fields, same batch for both -- as ONE launch whose workgroups are id-compaction tiles or re-zero
+ * blocks (the two share no data).  The two workspaces may be the same one (the previous sort's pairs and the compact id
+ * matrix lie in different regions of the layout) or differ (the previous step's ids were sorted ahead, into a workspace of
+ * the caller's).  A call without sorted tables only compacts, one without a compact matrix only clears, batch == 0 does
+ * nothing.  Same stores, same status word as the two calls. */
+int rbx_fm_head(const rbx_field_t* emb, const rbx_field_t* lr, int32_t n_fields, int64_t batch,
+                const void* d_rezero_workspace, size_t rezero_workspace_bytes, void* d_sort_workspace,
+                size_t sort_workspace_bytes, int32_t* d_status, void* stream);
 /* Two lookups over the SAME id tensors with the same table layout (the embedding tables of FeatureEmbedding and the dim-1
  * tables of LogisticRegression over one batch: feature_embedding.py + logistic_regression.py:30-35) sort identical
  * (row, sample) pairs.  Given the descriptors of a sort that is already in d_src_workspace (src_is_fm = 0: src_a is an

@@ -156,6 +156,7 @@ SIGNATURES = {
     "rbx_fm_quad": (ctypes.c_int, [_i32]),
     "rbx_sort_chained": (ctypes.c_int, [_i32]),
     "rbx_fm_rezero": (ctypes.c_int, [_FP, _FP, _i32, _i64, _P, _sz, _P]),
+    "rbx_fm_head": (ctypes.c_int, [_FP, _FP, _i32, _i64, _P, _sz, _P, _sz, _P, _P]),
     "rbx_fm_bwd": (ctypes.c_int, [_FP, _FP, _i32, _i64, _P, _P, _P, _i32, _i32, _P, _sz, _P]),
     "rbx_gatherdot_fwd": (ctypes.c_int, [_FP, _i32, _i64, _P, _i64, _f32, _P, _P, _P]),
     "rbx_gatherdot_bwd_workspace_size": (_sz, [_FP, _i32, _i64]),

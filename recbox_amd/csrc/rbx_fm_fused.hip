@@ -833,8 +833,96 @@ static void fm_bind_cid(FmFull* f, char* ws, int64_t B) {
   }
 }
 
+// ---- the head of a step with persistent gradients as ONE launch: id compaction tiles | re-zero blocks ---------------------
+// rezero_rows_kernel (reads the PREVIOUS step's sorted pairs, clears gradient rows) and compact_ids_kernel (reads the id
+// columns, writes the compact matrix) share no data, yet ran one behind the other in front of BOTH chains of the step: the
+// forward and the large tables' pair construction wait for the compaction only, the first reader of a cleared row is the
+// segmented reduce ~100 us later.  One grid, the role chosen by blockIdx.x; the compaction tiles -- the short part, which
+// everything downstream waits for -- are dispatched first.  Both bodies are the ones of the two kernels (rezero_rows_block,
+// compact_ids_tile).  The two full descriptor packs (3072 + 1536 B) do not fit one kernarg segment together: the call's LIVE
+// entries travel packed, [n_cat RedField | n_cid CidField]; a call whose entries do not fit keeps the two launches.
+constexpr int kFmHeadPackBytes = 3840;
+struct FmHeadPack { long long w[kFmHeadPackBytes / 8]; };
+static_assert(sizeof(FmHeadPack) + 128 <= 4096, "fm_head_kernel's arguments (the pack + 12 scalars) must fit the kernarg segment");
+
+template <bool VEC, bool FIELD_FAST>
+__global__ __launch_bounds__(256) void fm_head_kernel(const FmHeadPack P, const unsigned n_tiles, const int n_cid,
+                                                      const long long B, const int ts, int* __restrict__ cid,
+                                                      int* __restrict__ status, const int n_cat,
+                                                      const unsigned* __restrict__ keys, const unsigned* __restrict__ vals,
+                                                      const unsigned n_lookups, const unsigned sentinel, const int lanes) {
+  extern __shared__ __attribute__((aligned(16))) int head_lds[];
+  const int red_words = n_cat * static_cast<int>(sizeof(RedField) / 4);
+  const int* src = reinterpret_cast<const int*>(&P);
+  if (blockIdx.x < n_tiles) {
+    const int words = n_cid * static_cast<int>(sizeof(CidField) / 4);
+    for (int i = threadIdx.x; i < words; i += 256) head_lds[i] = src[red_words + i];
+    __syncthreads();
+    compact_ids_tile<FIELD_FAST>(reinterpret_cast<const CidField*>(head_lds),
+                                 head_lds + (RBX_MAX_FIELDS * sizeof(CidField)) / sizeof(int), blockIdx.x, n_cid, B, ts, cid,
+                                 status);
+  } else {
+    for (int i = threadIdx.x; i < red_words; i += 256) head_lds[i] = src[i];
+    __syncthreads();
+    rezero_rows_block<VEC>(reinterpret_cast<const RedField*>(head_lds), blockIdx.x - n_tiles, keys, vals, n_lookups, sentinel,
+                           lanes);
+  }
+}
+
+// rz: the plan whose sorted pairs (in rz_ws) name the rows to clear; ta: the compaction's plan, writing into `region`
+static int launch_fm_head(const BwdPlan& rz, const char* rz_ws, const TaPlan& ta, int64_t B, char* region, int* d_status,
+                          hipStream_t s) {
+  const size_t red_bytes = static_cast<size_t>(rz.n_cat) * sizeof(RedField);
+  const size_t cid_bytes = static_cast<size_t>(ta.n_cid) * sizeof(CidField);
+  if (red_bytes + cid_bytes > sizeof(FmHeadPack)) {
+    const int rc = launch_rezero(rz, rz_ws, s);
+    return rc != RBX_OK ? rc : ta_launch_compact(ta, B, region, d_status, s);
+  }
+  FmHeadPack pk;
+  memcpy(pk.w, rz.red.f, red_bytes);
+  memcpy(reinterpret_cast<char*>(pk.w) + red_bytes, ta.cid.f, cid_bytes);
+  const int cur = rz.passes & 1;
+  const unsigned* keys = reinterpret_cast<const unsigned*>(rz_ws + rz.off_keys[cur]);
+  const unsigned* vals = reinterpret_cast<const unsigned*>(rz_ws + rz.off_vals[cur]);
+  const int lanes = rezero_lanes(rz);
+  const int ts = ta.cid_ts;
+  const unsigned n_tiles = static_cast<unsigned>((B + ts - 1) / ts);
+  const unsigned rz_blocks = (rz.n_lookups + 255) / 256;
+  size_t lds = RBX_MAX_FIELDS * sizeof(CidField) + static_cast<size_t>(ta.n_cid) * (ts + 1) * 4;   // (as ta_launch_compact)
+  if (lds < red_bytes) lds = red_bytes;
+  int* cid = reinterpret_cast<int*>(region + ta.off_cid);
+#define RBX_FM_HEAD(V, FF)                                                                                                   \
+  hipLaunchKernelGGL((fm_head_kernel<V, FF>), dim3(n_tiles + rz_blocks), dim3(256), lds, s, pk, n_tiles, ta.n_cid,           \
+                     static_cast<long long>(B), ts, cid, d_status, rz.n_cat, keys, vals, rz.n_lookups, rz.total_rows, lanes)
+  if (rz.vec) { if (ta.field_fast) RBX_FM_HEAD(true, true); else RBX_FM_HEAD(true, false); }
+  else { if (ta.field_fast) RBX_FM_HEAD(false, true); else RBX_FM_HEAD(false, false); }
+#undef RBX_FM_HEAD
+  return check_launch("fm_head_kernel");
+}
 
 }  // namespace rbx
+
+extern "C" int rbx_fm_head(const rbx_field_t* emb, const rbx_field_t* lr, int32_t n_fields, int64_t batch,
+                           const void* d_rezero_workspace, size_t rezero_workspace_bytes, void* d_sort_workspace,
+                           size_t sort_workspace_bytes, int32_t* d_status, void* stream) {
+  using namespace rbx;
+  if (batch <= 0) return RBX_OK;
+  FmFull f;
+  int rc = fm_full_plan(emb, lr, n_fields, batch, &f);
+  if (rc != RBX_OK) return rc;
+  const bool clear = f.p.n_lookups > 0;            // (tier-A tables are written in full by every backward: nothing to clear)
+  const bool compact = f.ta.n_cid > 0;
+  if (clear && (d_rezero_workspace == nullptr || rezero_workspace_bytes < f.bytes))
+    return fail(RBX_ERR_WORKSPACE, "fm_head: re-zero workspace too small");
+  if (compact && (d_sort_workspace == nullptr || sort_workspace_bytes < f.bytes))
+    return fail(RBX_ERR_WORKSPACE, "fm_head: sort workspace too small");
+  const char* rws = static_cast<const char*>(d_rezero_workspace);
+  char* sws = static_cast<char*>(d_sort_workspace);
+  hipStream_t s = as_stream(stream);
+  if (!clear) return compact ? ta_launch_compact(f.ta, batch, sws + f.off_ta, d_status, s) : RBX_OK;
+  if (!compact) return launch_rezero(f.p, rws, s);
+  return launch_fm_head(f.p, rws, f.ta, batch, sws + f.off_ta, d_status, s);
+}
 
 extern "C" int rbx_fm_rezero(const rbx_field_t* emb, const rbx_field_t* lr, int32_t n_fields, int64_t batch,
                              void* d_workspace, size_t workspace_bytes, void* stream) {

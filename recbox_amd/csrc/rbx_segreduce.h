@@ -480,6 +480,10 @@ static int launch_reduce(const BwdPlan& p, const typename Policy::Args& args, co
   hipLaunchKernelGGL((segment_fixup_short_kernel<Policy, G, NV, VEC>), dim3(short_blocks), dim3(256), 0, s, p.red, args,
                      keys, vals, head, tail, flags, fin, p.max_dim, p.sum_stride, p.n_chunks,
                      static_cast<unsigned>(p.chunk));
+  // (Two launches, not two workgroup roles of one: the long pass CONSUMES what the short pass writes -- fin[1], the list of
+  //  long chains behind it and their zeroed arrival counters are filled by the short pass's lane groups as they find chains
+  //  of more than kShortHops chunks, and the long pass sizes its work by fin[1].  One launch would have its long-chain
+  //  workgroups wait for every short-pass workgroup: an inter-workgroup wait without guaranteed co-residency.)
   unsigned long_blocks = p.n_chunks;                        // one workgroup per long chain, grid-stride
   if (long_blocks > p.long_cap) long_blocks = p.long_cap;
   hipLaunchKernelGGL((segment_fixup_long_kernel<Policy, G, NV, VEC>), dim3(long_blocks), dim3(256), 0, s, p.red, args,
@@ -510,25 +514,19 @@ static int dispatch_reduce(const BwdPlan& p, const typename Policy::Args& args, 
 // The sorted (key, val) pairs of the PREVIOUS sort on this workspace name every gradient row that step's
 // backward stored to: one lane group per pair, the head of each run of equal keys clears its row (dim floats of
 // dW, one float of the LR gradient).  36 MB of stores at the Criteo shape instead of a 379 MB fill of the dense grads.
+// (The body is a __device__ function of the workgroup number so that fm_head_kernel, rbx_fm_fused.hip, can run it as one
+//  of two workgroup roles of ONE launch; `sf` is the plan's RedFields in LDS, filled by the caller.)
 template <bool VEC>
-__global__ __launch_bounds__(256) void rezero_rows_kernel(const RedPack P, const int n_cat, const unsigned* __restrict__ keys,
-                                                        const unsigned* __restrict__ vals, const unsigned n,
-                                                        const unsigned sentinel, const int lanes) {
-  __shared__ RedField sf[RBX_MAX_FIELDS];
-  {
-    const int words = n_cat * static_cast<int>(sizeof(RedField) / 4);
-    const int* src = reinterpret_cast<const int*>(&P);
-    int* dst = reinterpret_cast<int*>(sf);
-    for (int i = threadIdx.x; i < words; i += blockDim.x) dst[i] = src[i];
-  }
-  __syncthreads();
+__device__ __forceinline__ void rezero_rows_block(const RedField* sf, const unsigned block, const unsigned* __restrict__ keys,
+                                                  const unsigned* __restrict__ vals, const unsigned n,
+                                                  const unsigned sentinel, const int lanes) {
   typedef float v4f __attribute__((ext_vector_type(4)));
   constexpr int W = VEC ? 4 : 1;
   // Phase 1, a thread per sorted pair: three independent coalesced loads decide whether the pair starts a run and
   // where its row lives.  Phase 2, a lane group per pair: the wave walks its 64 pairs `64 / lanes` at a time and a
   // row is cleared by ONE coalesced store of its group.  (One lane group per pair from the start, with the loads
   // chained behind each other, was latency-bound at 41 us; a thread per pair storing 4 x 16 B took 83 us.)
-  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+  const unsigned i = block * blockDim.x + threadIdx.x;
   float* row_ptr = nullptr;
   int dim = 0;
   if (i < n) {
@@ -562,15 +560,35 @@ __global__ __launch_bounds__(256) void rezero_rows_kernel(const RedPack P, const
   }
 }
 
+template <bool VEC>
+__global__ __launch_bounds__(256) void rezero_rows_kernel(const RedPack P, const int n_cat, const unsigned* __restrict__ keys,
+                                                        const unsigned* __restrict__ vals, const unsigned n,
+                                                        const unsigned sentinel, const int lanes) {
+  __shared__ RedField sf[RBX_MAX_FIELDS];
+  {
+    const int words = n_cat * static_cast<int>(sizeof(RedField) / 4);
+    const int* src = reinterpret_cast<const int*>(&P);
+    int* dst = reinterpret_cast<int*>(sf);
+    for (int i = threadIdx.x; i < words; i += blockDim.x) dst[i] = src[i];
+  }
+  __syncthreads();
+  rezero_rows_block<VEC>(sf, blockIdx.x, keys, vals, n, sentinel, lanes);
+}
+
+
+static inline int rezero_lanes(const BwdPlan& p) {        // lanes that clear one row: a power of two
+  const int width = p.vec ? (p.max_dim + 3) / 4 : p.max_dim;
+  int lanes = 1;
+  while (lanes < width && lanes < 64) lanes *= 2;
+  return lanes;
+}
 
 // launch helper of rbx_fm_rezero / rbx_embed_rezero (any plan built by make_plan / fm_plan: the kernel reads the RedPack only)
 static inline int launch_rezero(const BwdPlan& p, const char* ws, hipStream_t s) {
   const int cur = p.passes & 1;
   const unsigned* keys = reinterpret_cast<const unsigned*>(ws + p.off_keys[cur]);
   const unsigned* vals = reinterpret_cast<const unsigned*>(ws + p.off_vals[cur]);
-  const int width = p.vec ? (p.max_dim + 3) / 4 : p.max_dim;
-  int lanes = 1;
-  while (lanes < width && lanes < 64) lanes *= 2;
+  const int lanes = rezero_lanes(p);
   const unsigned blocks = (p.n_lookups + 255) / 256;
   if (p.vec)
     hipLaunchKernelGGL(rezero_rows_kernel<true>, dim3(blocks), dim3(256), 0, s, p.red, p.n_cat, keys, vals, p.n_lookups,

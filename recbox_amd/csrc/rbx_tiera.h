@@ -23,6 +23,7 @@
 // inside a table): gradients are bit-identical run to run, no float atomics.  The two ids-only kernels run on the side
 // stream beside the forward (rbx_fm_sort), the other two after the loss (rbx_fm_bwd).
 #pragma once
+#include <string.h>
 #include "rbx_bwd_common.h"
 
 namespace rbx {
@@ -103,20 +104,14 @@ __device__ __forceinline__ bool ta_decode_id(long long raw, int dt, int vocab, i
 // memory); otherwise consecutive samples of one column (separate contiguous id tensors).  Either way the stores are `ts`
 // consecutive ints per column.  Out-of-range ids become -1 and raise the status word.
 constexpr int kCidPerThread = 8;
+// The tile's work as a __device__ function of the tile number (`sf`: the n CidFields in LDS, filled by the caller; `tile`:
+// n * (ts + 1) ints of LDS): compact_ids_kernel below and fm_head_kernel (rbx_fm_fused.hip: one launch whose workgroups
+// are compaction tiles or re-zero blocks) both run it.
 template <bool FIELD_FAST>
-__global__ __launch_bounds__(256) void compact_ids_kernel(const CidPack P, const int n, const long long B, const int ts,
-                                                          int* __restrict__ cid, int* __restrict__ status) {
-  extern __shared__ int ta_lds[];
-  CidField* sf = reinterpret_cast<CidField*>(ta_lds);                       // [n]
-  int* tile = ta_lds + (RBX_MAX_FIELDS * sizeof(CidField)) / sizeof(int);   // [n][ts + 1]
-  {
-    const int words = n * static_cast<int>(sizeof(CidField) / 4);
-    const int* src = reinterpret_cast<const int*>(&P);
-    int* dst = reinterpret_cast<int*>(sf);
-    for (int i = threadIdx.x; i < words; i += blockDim.x) dst[i] = src[i];
-  }
-  __syncthreads();
-  const long long b0 = static_cast<long long>(blockIdx.x) * ts;
+__device__ __forceinline__ void compact_ids_tile(const CidField* sf, int* tile, const unsigned tile_no, const int n,
+                                                 const long long B, const int ts, int* __restrict__ cid,
+                                                 int* __restrict__ status) {
+  const long long b0 = static_cast<long long>(tile_no) * ts;
   const int live = static_cast<int>((B - b0 < ts) ? (B - b0) : ts);
   const int pitch = ts + 1;
   const int total = n * ts;                             // <= 256 * kCidPerThread
@@ -152,6 +147,22 @@ __global__ __launch_bounds__(256) void compact_ids_kernel(const CidPack P, const
     const int c = idx / ts, s = idx - c * ts;
     if (s < live) cid[static_cast<size_t>(c) * B + b0 + s] = tile[c * pitch + s];
   }
+}
+
+template <bool FIELD_FAST>
+__global__ __launch_bounds__(256) void compact_ids_kernel(const CidPack P, const int n, const long long B, const int ts,
+                                                          int* __restrict__ cid, int* __restrict__ status) {
+  extern __shared__ int ta_lds[];
+  CidField* sf = reinterpret_cast<CidField*>(ta_lds);                       // [n]
+  int* tile = ta_lds + (RBX_MAX_FIELDS * sizeof(CidField)) / sizeof(int);   // [n][ts + 1]
+  {
+    const int words = n * static_cast<int>(sizeof(CidField) / 4);
+    const int* src = reinterpret_cast<const int*>(&P);
+    int* dst = reinterpret_cast<int*>(sf);
+    for (int i = threadIdx.x; i < words; i += blockDim.x) dst[i] = src[i];
+  }
+  __syncthreads();
+  compact_ids_tile<FIELD_FAST>(sf, tile, blockIdx.x, n, B, ts, cid, status);
 }
 
 // ---- one stable 8-bit LSD pass over the 2048 keys of a workgroup, in LDS -------------------------------------------

@@ -81,6 +81,10 @@ class config(object):
     fuse_deepfm_input = os.environ.get("RECBOX_AMD_FUSE_DEEPFM_INPUT", "1") != "0"
     # ... and inside it the first-order Linear in the FM term's pass over the block (rbx_fm_sum_lr_fwd)
     fuse_deepfm_lr = True
+    # fused FM, persistent gradients: the step's head (re-zero of the previous step's rows | id compaction) as ONE launch
+    # (rbx_fm_head) -- one dependent launch less at the head of both chains of the step.  Off: the separate entry points
+    # (rbx_fm_rezero, then rbx_fm_sort_phases), which leave the same bits (tests/test_gpu_fm_launch_fusion.py).
+    fm_fuse_launches = os.environ.get("RECBOX_AMD_FM_FUSE_LAUNCHES", "1") != "0"
     reuse_grad_buffers = {"0": False, "": False, "all": "all"}.get(os.environ.get("RECBOX_AMD_REUSE_GRADS", "0"), True)
     # keep, after every embedding backward, a record of what names the rows it touched (the sorted ids in its workspace, the
     # descriptors, the gradient tensors): what recbox_amd.optim's sparse-row optimisers step over.  Switched on by them.
@@ -1209,7 +1213,7 @@ class _GradPool(object):
             return None
         return pool
 
-    def early_sort(self, ctx, device, ws_bytes, rezero, sort, first=None, pre=None):
+    def early_sort(self, ctx, device, ws_bytes, rezero, sort, first=None, pre=None, head=None):
         """Launch, on the side stream: ``rezero(stream)`` -- clear the rows the previous backward stored, its sorted ids
         are still in ``self.ws`` -- when there are any, then ``sort(ws, ws_bytes, stream)`` of this batch's ids over
         them.  Both return a C-ABI code.  (Clearing on a third stream beside the sort was measured slower -- 0.344 vs
@@ -1223,6 +1227,11 @@ class _GradPool(object):
         # With ``pre`` (the tiered FM step) the re-zero runs HERE, on the current stream in front of the forward kernel:
         # beside the forward its 0.5 M random row stores slowed that kernel from 43 to 55 us for a step only 1.3 % shorter
         # (0.2355 vs 0.2386 ms; profiles/r03), and inside a partition pass beside it they cost more than they saved (r04).
+        # ``head(ws, ws_bytes)``: that re-zero and ``pre`` as ONE launch, where the caller has one (same batch size as the
+        # previous step, so that the two parts work on different regions of the workspace) and the workspace stays.
+        if dirty and pre is not None and head is not None and self.ws is not None and self.ws_bytes >= ws_bytes:
+            check(head(self.ws, self.ws_bytes))
+            dirty, pre = 0, None
         if dirty and (self.ws_bytes < ws_bytes or pre is not None):
             check(rezero(_stream()))
             dirty = 0
@@ -1498,8 +1507,12 @@ class _FmFused(torch.autograd.Function):
             def rezero(st):                            # ... and back to the sort's descriptors
                 return _FmFused._rezero(pool, tb, st, then=_FmTables.PLACEHOLDERS)
 
+            def head(ws, nbytes):                      # re-zero | id compaction, one launch on the current stream
+                return _FmFused._head(pool, tb, B, ws, nbytes, then=_FmTables.PLACEHOLDERS)
+
             if split:
-                pool.early_sort(step, dev, ws_bytes, rezero, rest, pre=compact)
+                fuse = config.fm_fuse_launches and pool.dirty_batch == B
+                pool.early_sort(step, dev, ws_bytes, rezero, rest, pre=compact, head=head if fuse else None)
                 step.blocksort_pending = True
             else:
                 pool.early_sort(step, dev, ws_bytes, rezero, rest, first=first)
@@ -1526,6 +1539,17 @@ class _FmFused(torch.autograd.Function):
         if previous is not None:
             dws, dbytes = previous.ws, previous.ws_bytes
         rc = lib.rbx_fm_rezero(tb.ea, tb.la, tb.n, pool.dirty_batch, _ptr(dws), dbytes, st)
+        pool.dirty_batch = 0
+        tb.bind(then)
+        return rc
+
+    @staticmethod
+    def _head(pool, tb, B, ws, nbytes, then):
+        """``_rezero`` and the id compaction of this step's batch into ``ws`` (rbx_fm_sort_phases, FM_SORT_IDS) as one launch
+        on the current stream; both for batch size ``B``.  Then bind ``then``."""
+        tb.bind(pool.bind_views(tb.params))
+        dws, dbytes = pool.dirty_ws if pool.dirty_ws is not None else (pool.ws, pool.ws_bytes)
+        rc = lib.rbx_fm_head(tb.ea, tb.la, tb.n, B, _ptr(dws), dbytes, _ptr(ws), nbytes, None, _stream())
         pool.dirty_batch = 0
         tb.bind(then)
         return rc
