@@ -186,7 +186,26 @@ int rbx_embed_bwd_indexed(const rbx_field_t* fields, int32_t n_fields, int64_t b
  *                                needs the row scale of the unweighted path.
  *   rbx_embed_csr_weight_grad    d_dweights: host array of n_bags device pointers, entry i an fp32 [nnz] array or NULL (no
  *                                gradient wanted).  Every element of a non-NULL array is defined after the call (cleared
- *                                by a memset node, then the usable positions are written).  Needs no sort. */
+ *                                by a memset node, then the usable positions are written).  Needs no sort.
+ *
+ * Training a large table (persistent gradients, sparse-row optimiser step).  After rbx_embed_csr_sort[_weighted] +
+ * rbx_embed_csr_bwd[_weighted] the workspace still holds the sorted pairs: the head of each run of equal keys names one
+ * touched row.  Both calls below read keys and plan slots only, so they take the workspace of either sort; descriptor
+ * rules and refusals are those of the calls above, made before anything is launched; a workspace smaller than
+ * rbx_embed_csr_bwd_workspace_size returns RBX_ERR_WORKSPACE; batch == 0 or no lookups: RBX_OK, nothing launched.
+ *   rbx_embed_csr_rezero         the contract of rbx_embed_rezero: zeros to exactly the rows of bags[i].grad that the
+ *                                previous rbx_embed_csr_bwd[_weighted] on this workspace stored (bags[i].nnz as in that
+ *                                call: it fixes the workspace layout).  Only for tables that get their gradient from that
+ *                                call alone.
+ *   rbx_embed_csr_sparse_update  the contract of rbx_embed_sparse_update (rules and rbx_opt_t below): one SGD / Adagrad /
+ *                                lazy-Adam step on exactly the touched rows of bags[i].table and of d_state1[i] /
+ *                                d_state2[i] -- indexed by DESCRIPTOR i (entries of frozen descriptors are not looked at;
+ *                                descriptors that share a table pass the same pointers and the row is stepped once).
+ *                                Untouched rows, padding_idx rows, mask_id ids of the _ID pools, ids outside [0, vocab)
+ *                                and positions outside every bag are neither read nor written.  A rule without its state
+ *                                array returns RBX_ERR_INVALID.  clear_grad != 0: the lane group that steps a row writes
+ *                                zeros over that gradient row once it holds it in registers (non-temporal stores): the
+ *                                step and the re-zero in one launch, table and state bit-equal to clear_grad = 0. */
 #define RBX_MAX_BAGS 32
 typedef struct rbx_bag {
   const void*  indices;          /* [nnz] ids */
@@ -223,6 +242,12 @@ int rbx_embed_csr_bwd_weighted(const rbx_bag_t* bags, int32_t n_bags, int64_t ba
                                size_t workspace_bytes, void* stream);
 int rbx_embed_csr_weight_grad(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, const float* d_dout,
                               int64_t out_stride_b, float* const* d_dweights, int32_t* d_status, void* stream);
+int rbx_embed_csr_rezero(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, void* d_workspace, size_t workspace_bytes,
+                         void* stream);
+struct rbx_opt;                  /* rbx_opt_t, declared with rbx_embed_sparse_update below */
+int rbx_embed_csr_sparse_update(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, const void* d_workspace,
+                                size_t workspace_bytes, const struct rbx_opt* opt, float* const* d_state1,
+                                float* const* d_state2, int32_t clear_grad, void* stream);
 
 /* The long-bag form of the three bag-walking calls above.  They map one lane group to one bag whatever its length, so a
  * few bags of thousands of ids keep a wave (and the launch) waiting for one group.  The `_long` calls take a

@@ -117,6 +117,8 @@ SIGNATURES = {
     "rbx_embed_csr_sort_weighted": (ctypes.c_int, [_BP, _i32, _i64, _P, _sz, _P, _P]),
     "rbx_embed_csr_bwd_weighted": (ctypes.c_int, [_BP, _i32, _i64, _PP, _P, _i64, _i32, _P, _sz, _P]),
     "rbx_embed_csr_weight_grad": (ctypes.c_int, [_BP, _i32, _i64, _P, _i64, _PP, _P, _P]),
+    "rbx_embed_csr_rezero": (ctypes.c_int, [_BP, _i32, _i64, _P, _sz, _P]),
+    "rbx_embed_csr_sparse_update": (ctypes.c_int, [_BP, _i32, _i64, _P, _sz, _OP, _PP, _PP, _i32, _P]),
     "rbx_embed_csr_fwd_long_workspace_size": (_sz, [_BP, _i32, _i64, _i64]),
     "rbx_embed_csr_fwd_long": (ctypes.c_int, [_BP, _i32, _i64, _i64, _P, _i64, _P, _P, _sz, _P, _P]),
     "rbx_embed_csr_fwd_weighted_long": (ctypes.c_int, [_BP, _i32, _i64, _i64, _PP, _P, _i64, _P, _sz, _P, _P]),

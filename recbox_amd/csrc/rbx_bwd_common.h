@@ -150,6 +150,10 @@ int run_sort_passes(const BwdPlan& p, char* ws, hipStream_t s);
 int generic_reduce(const BwdPlan& p, const float* dout, int64_t stride_b, const int32_t* index, const float* row_scale,
                    int64_t B, int accumulate, char* ws, hipStream_t s);
 
+// The plan of a ragged-bag call (definition in rbx_embed_csr.hip: csr_plan's, after the descriptor checks of every
+// rbx_embed_csr_* entry point) for a caller outside that file; *bytes: the workspace rbx_embed_csr_sort needs for it.
+int csr_bwd_plan(const rbx_bag_t* bags, int n, int64_t batch, BwdPlan* p, size_t* bytes);
+
 // ---- segment reduce ------------------------------------------------------------------
 template <int G, int NV, bool VEC>
 struct Frag {

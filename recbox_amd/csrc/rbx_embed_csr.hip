@@ -738,6 +738,15 @@ static int csr_plan(const rbx_bag_t* bags, int n, int64_t batch, const float* do
   return RBX_OK;
 }
 
+int csr_bwd_plan(const rbx_bag_t* bags, int n, int64_t batch, BwdPlan* p, size_t* bytes) {
+  CsrPlan c;
+  const int rc = csr_plan(bags, n, batch, nullptr, 0, &c);
+  if (rc != RBX_OK) return rc;
+  *p = c.p;
+  *bytes = c.bytes;
+  return RBX_OK;
+}
+
 template <int RB, bool POS = false>
 static int launch_csr_keys(const CsrPlan& c, char* ws, int* status, hipStream_t s) {
   const BwdPlan& p = c.p;
@@ -1092,6 +1101,20 @@ extern "C" int rbx_embed_csr_bwd(const rbx_bag_t* bags, int32_t n_bags, int64_t 
     return fail(RBX_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, c.bytes);
   return generic_reduce(c.p, d_dout, out_stride_b, nullptr, d_row_scale, batch, accumulate, static_cast<char*>(d_workspace),
                         as_stream(stream));
+}
+
+// The rows the previous rbx_embed_csr_bwd[_weighted] over this workspace stored: the run heads of its sorted pairs (either
+// sort: keys and plan slots only are read).
+extern "C" int rbx_embed_csr_rezero(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, void* d_workspace,
+                                    size_t workspace_bytes, void* stream) {
+  using namespace rbx;
+  CsrPlan c;
+  int rc = csr_plan(bags, n_bags, batch, nullptr, 0, &c);
+  if (rc != RBX_OK) return rc;
+  if (c.p.n_lookups == 0 || batch == 0) return RBX_OK;
+  if (d_workspace == nullptr || workspace_bytes < c.bytes)
+    return fail(RBX_ERR_WORKSPACE, "workspace %zu B < required %zu B", d_workspace == nullptr ? size_t(0) : workspace_bytes, c.bytes);
+  return launch_rezero(c.p, static_cast<const char*>(d_workspace), as_stream(stream));
 }
 
 // ---- per-sample weights ----------------------------------------------------------------------------------------------

@@ -69,9 +69,13 @@ struct UpdField {            // 80 B
 constexpr int kUpdFields = 32;                       // plan slots one launch serves (kernarg budget)
 struct UpdPack { UpdField f[kUpdFields]; };
 
-// one row: the G lanes of a group sweep its dim floats (float4 when VEC)
-template <bool VEC>
+// one row: the G lanes of a group sweep its dim floats (float4 when VEC).  CLEAR (rbx_embed_csr_sparse_update with
+// clear_grad): the lane that holds a piece of the gradient row in registers writes zeros back over it -- the row is
+// streamed through once more per step anyway, so the persistent gradient buffer is clean for the next backward without a
+// re-zero launch of its own.  Non-temporal: nothing reads those zeros before the next backward overwrites them.
+template <bool VEC, bool CLEAR = false>
 __device__ __forceinline__ void update_row(const OptArgs& o, const UpdField& fd, size_t row, int lane_g, int G) {
+  typedef float v4f __attribute__((ext_vector_type(4)));
   constexpr int W = VEC ? 4 : 1;
   if (fd.w != nullptr && fd.g != nullptr) {
     float* wrow = fd.w + row * fd.w_stride;
@@ -81,6 +85,10 @@ __device__ __forceinline__ void update_row(const OptArgs& o, const UpdField& fd,
     for (int e = lane_g * W; e < fd.dim; e += G * W) {
       if constexpr (VEC) {
         const float4 g = *reinterpret_cast<const float4*>(grow + e);
+        if constexpr (CLEAR) {
+          const v4f z = {0.f, 0.f, 0.f, 0.f};
+          __builtin_nontemporal_store(z, reinterpret_cast<v4f*>(const_cast<float*>(grow) + e));
+        }
         float4 w = *reinterpret_cast<const float4*>(wrow + e);
         float4 a = s1row ? *reinterpret_cast<const float4*>(s1row + e) : make_float4(0.f, 0.f, 0.f, 0.f);
         float4 b = s2row ? *reinterpret_cast<const float4*>(s2row + e) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -93,7 +101,9 @@ __device__ __forceinline__ void update_row(const OptArgs& o, const UpdField& fd,
         if (s2row) *reinterpret_cast<float4*>(s2row + e) = b;
       } else {
         float w = wrow[e], a = s1row ? s1row[e] : 0.f, b = s2row ? s2row[e] : 0.f;
-        opt_apply(o, grow[e], w, a, b);
+        const float g = grow[e];
+        if constexpr (CLEAR) __builtin_nontemporal_store(0.f, const_cast<float*>(grow) + e);
+        opt_apply(o, g, w, a, b);
         wrow[e] = w;
         if (s1row) s1row[e] = a;
         if (s2row) s2row[e] = b;
@@ -102,7 +112,9 @@ __device__ __forceinline__ void update_row(const OptArgs& o, const UpdField& fd,
   }
   if (fd.w2 != nullptr && fd.g2 != nullptr && lane_g == 0) {
     float w = fd.w2[row], a = fd.t1 ? fd.t1[row] : 0.f, b = fd.t2 ? fd.t2[row] : 0.f;
-    opt_apply(o, fd.g2[row], w, a, b);
+    const float g = fd.g2[row];
+    if constexpr (CLEAR) const_cast<float*>(fd.g2)[row] = 0.f;
+    opt_apply(o, g, w, a, b);
     fd.w2[row] = w;
     if (fd.t1) fd.t1[row] = a;
     if (fd.t2) fd.t2[row] = b;
@@ -110,7 +122,7 @@ __device__ __forceinline__ void update_row(const OptArgs& o, const UpdField& fd,
 }
 
 // sorted pairs -> run heads -> rows.  One lane group per pair; plan slots [slot_lo, slot_lo + n_slots) only.
-template <bool VEC>
+template <bool VEC, bool CLEAR = false>
 __global__ __launch_bounds__(256) void sparse_update_kernel(const UpdPack P, const int slot_lo, const int n_slots,
                                                             const OptArgs o, const unsigned* __restrict__ keys,
                                                             const unsigned* __restrict__ vals, const unsigned n,
@@ -124,7 +136,7 @@ __global__ __launch_bounds__(256) void sparse_update_kernel(const UpdPack P, con
     const int slot = static_cast<int>(vals[i] >> kLocalBits) - slot_lo;
     if (slot < 0 || slot >= n_slots) continue;
     const UpdField& fd = P.f[slot];
-    update_row<VEC>(o, fd, static_cast<size_t>(key - fd.row_base), lane_g, G);
+    update_row<VEC, CLEAR>(o, fd, static_cast<size_t>(key - fd.row_base), lane_g, G);
   }
 }
 
@@ -201,8 +213,9 @@ static int lanes_for(int dim, bool vec) {
   return g;
 }
 
-// launch the pair walk over the plan's sorted keys, kUpdFields plan slots at a time
-static int launch_pairs(const BwdPlan& p, const UpdField* upd, const OptArgs& o, const char* ws, hipStream_t s) {
+// launch the pair walk over the plan's sorted keys, kUpdFields plan slots at a time; clear: the CLEAR form of update_row
+static int launch_pairs(const BwdPlan& p, const UpdField* upd, const OptArgs& o, const char* ws, hipStream_t s,
+                        bool clear = false) {
   if (p.n_lookups == 0) return RBX_OK;
   const int cur = p.passes & 1;
   const unsigned* keys = reinterpret_cast<const unsigned*>(ws + p.off_keys[cur]);
@@ -222,7 +235,13 @@ static int launch_pairs(const BwdPlan& p, const UpdField* upd, const OptArgs& o,
     const int G = lanes_for(dim, vec);
     unsigned long long blocks = (static_cast<unsigned long long>(p.n_lookups) + (256 / G) - 1) / (256 / G);
     if (blocks > static_cast<unsigned long long>(kCUs) * 64) blocks = kCUs * 64;
-    if (vec)
+    if (vec && clear)
+      hipLaunchKernelGGL((sparse_update_kernel<true, true>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, pack, lo, cnt,
+                         o, keys, vals, p.n_lookups, p.total_rows, G);
+    else if (clear)
+      hipLaunchKernelGGL((sparse_update_kernel<false, true>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, pack, lo, cnt,
+                         o, keys, vals, p.n_lookups, p.total_rows, G);
+    else if (vec)
       hipLaunchKernelGGL(sparse_update_kernel<true>, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, pack, lo, cnt, o,
                          keys, vals, p.n_lookups, p.total_rows, G);
     else
@@ -267,6 +286,44 @@ extern "C" int rbx_embed_sparse_update(const rbx_field_t* fields, int32_t n_fiel
     if (o.kind == RBX_OPT_ADAM && u.s2 == nullptr) return fail(RBX_ERR_INVALID, "sparse_update: feature %d has no second moment", i);
   }
   return launch_pairs(p, upd, o, static_cast<const char*>(d_workspace), as_stream(stream));
+}
+
+// Ragged bags (rbx_embed_csr.hip): the same step over the sorted pairs of rbx_embed_csr_sort / _sort_weighted -- both
+// keep the plan slot in vals >> kLocalBits and give dropped pairs the sentinel key, which is all the pair walk reads.
+// d_state* are indexed by descriptor (RedField::slot), not by plan slot: frozen descriptors take no slot.
+extern "C" int rbx_embed_csr_sparse_update(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, const void* d_workspace,
+                                           size_t workspace_bytes, const rbx_opt_t* opt, float* const* d_state1,
+                                           float* const* d_state2, int32_t clear_grad, void* stream) {
+  using namespace rbx;
+  OptArgs o;
+  int rc = opt_validate(opt, &o);
+  if (rc != RBX_OK) return rc;
+  if (batch <= 0) return RBX_OK;
+  BwdPlan p;
+  size_t bytes = 0;
+  rc = csr_bwd_plan(bags, n_bags, batch, &p, &bytes);
+  if (rc != RBX_OK) return rc;
+  if (p.n_lookups == 0) return RBX_OK;
+  UpdField upd[RBX_MAX_FIELDS];
+  for (int c = 0; c < p.n_cat; ++c) {
+    const RedField& rf = p.red.f[c];
+    const int i = rf.slot;                              // index of the descriptor in `bags`
+    UpdField& u = upd[c];
+    u.w = const_cast<float*>(bags[i].table);
+    u.g = bags[i].grad;
+    u.w2 = nullptr; u.g2 = nullptr; u.t1 = nullptr; u.t2 = nullptr;
+    u.s1 = d_state1 != nullptr ? d_state1[i] : nullptr;
+    u.s2 = d_state2 != nullptr ? d_state2[i] : nullptr;
+    u.row_base = rf.row_base;
+    u.dim = rf.dim;
+    u.w_stride = rf.dim;
+    u.reserved = 0;
+    if (o.kind != RBX_OPT_SGD && u.s1 == nullptr) return fail(RBX_ERR_INVALID, "csr_sparse_update: bag %d has no state tensor", i);
+    if (o.kind == RBX_OPT_ADAM && u.s2 == nullptr) return fail(RBX_ERR_INVALID, "csr_sparse_update: bag %d has no second moment", i);
+  }
+  if (d_workspace == nullptr || workspace_bytes < bytes)
+    return fail(RBX_ERR_WORKSPACE, "csr_sparse_update: workspace %zu B < required %zu B", d_workspace == nullptr ? size_t(0) : workspace_bytes, bytes);
+  return launch_pairs(p, upd, o, static_cast<const char*>(d_workspace), as_stream(stream), clear_grad != 0);
 }
 
 // defined in rbx_fm_fused.hip: the plan of a fused FM call (tier B sort plan + tier A description) and where its pieces live

@@ -354,23 +354,24 @@ def _enqueue_sort(desc, keep, B, ws, nbytes, st, sort_call):
 
 class TouchedRows(object):
     """What one embedding backward left behind for a sparse-row optimiser step (recbox_amd.optim): ``kind`` "embed"
-    (rbx_embed_*) or "fm" (rbx_fm_*), the plan(s) and id tensors of the call, its parameter and gradient lists, and the
-    workspace whose sorted ids name every touched row; "fm": also ``tables``, the call's _FmTables (what binds its two
-    plans).  Valid until the next sort on that workspace."""
-    __slots__ = ("kind", "plans", "inputs", "params", "grads", "ws", "ws_bytes", "B", "serial", "tables")
+    (rbx_embed_*), "fm" (rbx_fm_*) or "bags" (rbx_embed_csr_*: ``inputs`` are the indices / offsets tensors of every bag in
+    turn), the plan(s) and id tensors of the call, its parameter and gradient lists, and the workspace whose sorted ids name
+    every touched row; "fm": also ``tables``, the call's _FmTables (what binds its two plans); "bags": also ``pool``, the
+    _GradPool the gradients alias (None: fresh gradients).  Valid until the next sort on that workspace."""
+    __slots__ = ("kind", "plans", "inputs", "params", "grads", "ws", "ws_bytes", "B", "serial", "tables", "pool")
 
 
 touched = {}                 # id(parameter) -> TouchedRows of the last backward that produced its gradient
 _touched_serial = [0]
 
 
-def _note_touched(kind, plans, inputs, params, grads, ws, ws_bytes, B, tables=None):
+def _note_touched(kind, plans, inputs, params, grads, ws, ws_bytes, B, tables=None, pool=None):
     rec = TouchedRows()
     # (aliases of the gradient tensors, not the objects handed to autograd: AccumulateGrad takes a gradient over as
     #  ``p.grad`` only while nobody else holds the tensor object -- otherwise it clones it, 5 GB for cfg 3's table)
     grads = tuple([g.detach() if g is not None else None for g in group] for group in grads)
     rec.kind, rec.plans, rec.inputs, rec.params, rec.grads = kind, plans, list(inputs), params, grads
-    rec.ws, rec.ws_bytes, rec.B, rec.tables = ws, int(ws_bytes), int(B), tables
+    rec.ws, rec.ws_bytes, rec.B, rec.tables, rec.pool = ws, int(ws_bytes), int(B), tables, pool
     _touched_serial[0] += 1
     rec.serial = _touched_serial[0]
     for group in params:
@@ -387,14 +388,15 @@ def _ids_pass_over():
     _ids_pass[1] = False
 
 
-def _note_ids(plan, inputs, params, grads, want):
+def _note_ids(plan, inputs, params, grads, want, ids_of=None):
     """A lookup over ``plan`` has written rows into ``grads`` (its own, or -- adopted -- the gradient another node of this
     backward pass published): remember the id tensors per table, so that a sparse-row optimiser can step a table that
     several lookups of one step feed (SASRec's item table: the sequence lookup and the pos / neg candidates of gather_dot)
     over the union of their rows instead of scanning the dense gradient for non-zero rows.  A list grows only within ONE
     backward pass: the first lookup of the next pass starts it afresh even when the gradient sits at the same address
     (``zero_grad(set_to_none=False)``, the caching allocator) and nobody stepped the table in between -- a table that some
-    other optimiser steps, or a frozen one, would otherwise pin every step's id tensors."""
+    other optimiser steps, or a frozen one, would otherwise pin every step's id tensors.
+    ``ids_of(k)``: the id tensors that address parameter ``k``, for a plan whose specs are not FieldSpecs (ragged bags)."""
     now = _pass_id()
     if _ids_pass[1] and now >= 0 and _ids_pass[2] != now:
         _ids_pass_over()               # the pass that armed this ended in an exception: its callback never ran
@@ -404,7 +406,8 @@ def _note_ids(plan, inputs, params, grads, want):
     for k, (p, g, w) in enumerate(zip(params, grads, want)):
         if not w or g is None:
             continue
-        ids = [t for sp, t in zip(plan.specs, inputs) if sp.kind == _lib.FIELD_CATEGORICAL and sp.param == k]
+        ids = ids_of(k) if ids_of is not None else \
+            [t for sp, t in zip(plan.specs, inputs) if sp.kind == _lib.FIELD_CATEGORICAL and sp.param == k]
         ent = touched_ids.get(id(p))
         if ent is not None and ent[0] == g.data_ptr() and ent[2] == _ids_pass[0]:
             ent[1].extend(ids)
@@ -783,6 +786,10 @@ class _EmbedBags(torch.autograd.Function):
     over the lookups that exist (rbx_embed_csr_sort in the forward, on the current stream; rbx_embed_csr_bwd).  Plain
     autograd semantics: freshly zeroed dense gradients (or, for a table another lookup of the pass has already written,
     that node's gradient: config.share_table_grads).  No host sync beyond the id check config.check_ids asks for.
+    With ``config.reuse_grad_buffers == "all"`` the node works as _EmbedLookup does: a _GradPool kept on the plan holds ONE
+    persistent dense gradient per table, the sort runs on the side stream behind rbx_embed_csr_rezero of the rows the
+    previous step stored, and the backward stores into the pool's views (every guard of the pool applies).  With
+    ``config.track_touched_rows`` a backward leaves a TouchedRows record of kind "bags" for recbox_amd.optim.
     ``weights``: one entry per bag, a float32 [nnz] tensor or None.  With any of them set the three calls are the
     ``_weighted`` ones, and rbx_embed_csr_weight_grad runs in the backward for the weights that want a gradient."""
 
@@ -825,22 +832,61 @@ class _EmbedBags(torch.autograd.Function):
                                                                     _ptr(status), _stream())))
         _check_status(status)
         ctx.plan, ctx.inputs, ctx.row_scale, ctx.B, ctx.params, ctx.weights = plan, inputs, row_scale, B, params, weights
-        ctx.ws, ctx.ws_bytes = None, 0
+        ctx.ws, ctx.ws_bytes, ctx.sort = None, 0, None
         if train:
             _note_readers(ctx, params)
         if B > 0 and train:
-            ctx.ws, ctx.ws_bytes = _EmbedBags._sort(plan, params, [p if p.requires_grad else None for p in params], B, dev,
-                                                    ctx.warr is not None)
+            placeholders = [p if p.requires_grad else None for p in params]
+            weighted = ctx.warr is not None
+            pool = _GradPool.claim(_EmbedBags._pool_for(plan, params, dev, weighted)
+                                   if config.reuse_grad_buffers == "all" else None)
+            if pool is None:
+                ctx.ws, ctx.ws_bytes = _EmbedBags._sort(plan, params, placeholders, B, dev, weighted)
+            else:
+                plan.bind_params(params, placeholders)
+                ws_bytes = _EmbedBags._workspace_size(plan, B)
+                sort_call = lib.rbx_embed_csr_sort_weighted if weighted else lib.rbx_embed_csr_sort
+
+                def sort(ws, nbytes, st):
+                    return sort_call(plan.arr, plan.n, B, _ptr(ws), nbytes, None, st)
+
+                def rezero(st):
+                    # the descriptors of the step whose rows are dirty: its nnz fix the layout of the pairs in the workspace
+                    rc = lib.rbx_embed_csr_rezero(pool.dirty_bags, plan.n, pool.dirty_batch, _ptr(pool.ws), pool.ws_bytes, st)
+                    pool.dirty_batch = 0
+                    return rc
+
+                if ws_bytes > 0:
+                    # (the size follows nnz, which differs from batch to batch: regrow with headroom, not at every new maximum)
+                    pool.early_sort(ctx, dev, ws_bytes if pool.ws_bytes >= ws_bytes else ws_bytes + ws_bytes // 4, rezero, sort)
         return out
 
     @staticmethod
-    def _sort(plan, params, grads, B, dev, weighted=False):
-        plan.bind_params(params, grads)
+    def _pool_for(plan, params, dev, weighted):
+        """The plan's _GradPool, keyed like _EmbedLookup._pool_for -- and by the weighted flag: the two sorts leave pairs
+        of different kinds, and nothing keeps a caller from alternating weighted and unweighted calls of one plan."""
+        params = list(params)
+        pools = plan.__dict__.setdefault("_grad_pools", {})
+        pool = pools.get(weighted)
+        if pool is None or not pool.matches(params):
+            named = set(sp.param for sp in plan.specs)
+            pool = pools[weighted] = _GradPool(params, [i in named for i in range(len(params))], dev)
+            pool.dirty_bags = None            # copy of the descriptor array of the backward whose rows are still in ``flat``
+        return pool
+
+    @staticmethod
+    def _workspace_size(plan, B):
         ws_bytes = lib.rbx_embed_csr_bwd_workspace_size(plan.arr, plan.n, B)
         if ws_bytes == 0:
             msg = _lib.last_error()
             if "too large" in msg or "exceeds" in msg or "limit" in msg:
                 raise NotImplementedError(msg)
+        return ws_bytes
+
+    @staticmethod
+    def _sort(plan, params, grads, B, dev, weighted=False):
+        plan.bind_params(params, grads)
+        ws_bytes = _EmbedBags._workspace_size(plan, B)
         ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
         if weighted:                                   # pairs that name the lookup's position: rbx_embed_csr_bwd_weighted's
             check(lib.rbx_embed_csr_sort_weighted(plan.arr, plan.n, B, _ptr(ws), ws_bytes, None, _stream()))
@@ -871,12 +917,21 @@ class _EmbedBags(torch.autograd.Function):
         head = (None, None, None) + (None,) * len(ctx.inputs) + tuple(dws)
         if not any(want):                                  # frozen tables
             return head + (None,) * len(params)
+        want_now = [p.requires_grad for p in params]
         adopted = _adopt_grads(ctx, params, want) if B > 0 else None
-        grads = adopted if adopted is not None else _flat_zero_grads(params, want, dout.device)
+        pool, grads = None, adopted
+        if adopted is None and getattr(ctx, "pool", None) is not None:
+            pool, grads = ctx.pool.backward_grads(ctx, params, want, want_now == list(want) and B > 0)
+        if grads is None:
+            grads = _flat_zero_grads(params, want, dout.device)
         if B == 0:
             return head + tuple(grads)
         weighted = ctx.warr is not None
-        if ctx.ws is not None and [p.requires_grad for p in params] == list(want):
+        if ctx.sort is not None and want_now == list(want):        # the pool's sort, on the side stream
+            ctx.sort.join()
+            plan.bind_params(params, grads)
+            ws, ws_bytes = ctx.sort.ws, ctx.sort.ws_bytes
+        elif ctx.ws is not None and want_now == list(want):
             plan.bind_params(params, grads)
             ws, ws_bytes = ctx.ws, ctx.ws_bytes
         else:                                          # e.g. torch.autograd.grad on a subset: sort now
@@ -888,11 +943,21 @@ class _EmbedBags(torch.autograd.Function):
         else:
             check(lib.rbx_embed_csr_bwd(plan.arr, plan.n, B, _ptr(dout), stride, _ptr(ctx.row_scale), accumulate, _ptr(ws),
                                         ws_bytes, _stream()))
+        if pool is not None:
+            pool.done(B)
+            pool.dirty_bags = type(plan.arr).from_buffer_copy(plan.arr)
+        _forget_sort(ws)
+        if config.track_touched_rows:
+            ids = ctx.inputs[0::2]
+            _note_ids(plan, ctx.inputs, params, grads, want,
+                      ids_of=lambda k: [t for sp, t in zip(plan.specs, ids) if sp.param == k])
         if adopted is not None:                        # the rows went into the gradient another node of this pass returned
             for p, w in zip(params, want):
                 if w:
                     touched.pop(id(p), None)           # (its touched-row record names that node's rows only)
             return head + (None,) * len(params)
+        if config.track_touched_rows:
+            _note_touched("bags", (plan,), ctx.inputs, (list(params),), (list(grads),), ws, ws_bytes, B, pool=pool)
         _publish_grads(ctx, params, grads)
         return head + tuple(grads)
 

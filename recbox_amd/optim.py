@@ -21,8 +21,8 @@ Rules (the sparse branches of torch.optim, so that results can be checked agains
 Dense stays the default and the parity surface of the layers; nothing here changes what ``p.grad`` is after a backward.
 A table that several lookups of one step feed (SASRec's item table: the sequence lookup and gather_dot's candidates) is
 stepped with the same rule over the union of their rows (the lookups leave their id tensors: ``ops.touched_ids``); a
-parameter that got its gradient from something else than ``embed_lookup`` / ``gather_dot`` / ``fm_fused`` is stepped over
-the non-zero rows of its dense gradient.
+parameter that got its gradient from something else than ``embed_lookup`` / ``embed_bags`` / ``gather_dot`` / ``fm_fused`` is
+stepped over the non-zero rows of its dense gradient.
 """
 import ctypes
 import math
@@ -50,7 +50,7 @@ def split_parameters(model):
 class _SparseRows(object):
     kind = None
 
-    def __init__(self, params, lr, weight_decay=0.0, capturable=False):
+    def __init__(self, params, lr, weight_decay=0.0, capturable=False, clear_grads=False):
         self.params = [p for p in params]
         if not self.params:
             raise ValueError("optimizer got an empty parameter list")
@@ -64,6 +64,13 @@ class _SparseRows(object):
         # capture without it.  One counter per optimiser: every table of it is then on the same step (torch.optim keeps one
         # per parameter; the two agree whenever every table receives a gradient in every step, as in a captured step).
         self.capturable = bool(capturable)
+        # clear_grads: a step over a ragged-bag lookup (``ops.embed_bags``) whose gradients alias the persistent buffer of
+        # ``ops.config.reuse_grad_buffers == "all"`` writes zeros back over every gradient row it has stepped
+        # (rbx_embed_csr_sparse_update, clear_grad = 1): the buffer is clean for the next backward and the next forward
+        # launches no re-zero.  ``p.grad`` of such a table then reads ALL-ZERO after ``step()``: nothing may read the
+        # gradient afterwards (clipping, logging and an all-reduce belong in front of the step).  Ignored everywhere else:
+        # fresh gradients, ``embed_lookup`` / ``fm_fused`` records, the dense fallback.
+        self.clear_grads = bool(clear_grads)
         self._dev = None                              # {"t": float32[1], "step_size": float32[1]} on the tables' device
         ops.config.track_touched_rows = True
 
@@ -178,7 +185,8 @@ class _SparseRows(object):
             sel = {}
             if plan is not None:
                 for i, sp in enumerate(plan.specs):
-                    if sp.kind != _lib.FIELD_CATEGORICAL or sp.param < 0:
+                    # (a BagSpec has no ``kind``: every spec of a "bags" record is a table lookup)
+                    if rec.kind != "bags" and (sp.kind != _lib.FIELD_CATEGORICAL or sp.param < 0):
                         continue
                     p, g = plist[sp.param], glist[sp.param]
                     if g is None:
@@ -213,6 +221,18 @@ class _SparseRows(object):
             plan.bind_params(rec.params[0], rec.grads[0])
             check(lib.rbx_embed_sparse_update(plan.arr, plan.n, rec.B, ops._ptr(rec.ws), rec.ws_bytes, ctypes.byref(opt),
                                               st_arrays[0][0], st_arrays[0][1], st))
+        elif rec.kind == "bags":
+            plan, pool = rec.plans[0], rec.pool
+            plan.bind_tensors(rec.inputs)
+            plan.bind_params(rec.params[0], rec.grads[0])
+            # the re-zero rides along only while the pool's dirty rows are exactly this record's (a polluted pool is
+            # cleared in full before its next step: rows somebody else wrote are not named by these sorted ids)
+            clear = (self.clear_grads and pool is not None and not pool.polluted and not pool.pending
+                     and pool.dirty_batch == rec.B and pool.dirty_ws[0] is rec.ws)
+            check(lib.rbx_embed_csr_sparse_update(plan.arr, plan.n, rec.B, ops._ptr(rec.ws), rec.ws_bytes, ctypes.byref(opt),
+                                                  st_arrays[0][0], st_arrays[0][1], 1 if clear else 0, st))
+            if clear:
+                pool.dirty_batch = 0
         else:
             tb = rec.tables
             tb.bind_inputs(rec.inputs)
@@ -228,8 +248,8 @@ class SparseSGD(_SparseRows):
     kind = _lib.OPT_SGD
     n_state = 0
 
-    def __init__(self, params, lr=1e-2, weight_decay=0.0, capturable=False):
-        super().__init__(params, lr, weight_decay, capturable)
+    def __init__(self, params, lr=1e-2, weight_decay=0.0, capturable=False, clear_grads=False):
+        super().__init__(params, lr, weight_decay, capturable, clear_grads)
 
     def _dense_rows(self, p, g, st, rows, t):
         g = g + self.weight_decay * p if self.weight_decay else g
@@ -244,8 +264,8 @@ class SparseAdagrad(_SparseRows):
     n_state = 1
 
     def __init__(self, params, lr=1e-2, lr_decay=0.0, eps=1e-10, weight_decay=0.0, initial_accumulator_value=0.0,
-                 capturable=False):
-        super().__init__(params, lr, weight_decay, capturable)
+                 capturable=False, clear_grads=False):
+        super().__init__(params, lr, weight_decay, capturable, clear_grads)
         self.lr_decay, self.eps, self.init_acc = float(lr_decay), float(eps), float(initial_accumulator_value)
 
     def _lr_decay(self):
@@ -282,8 +302,8 @@ class SparseAdam(_SparseRows):
     kind = _lib.OPT_ADAM
     n_state = 2
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False):
-        super().__init__(params, lr, weight_decay, capturable)
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False, clear_grads=False):
+        super().__init__(params, lr, weight_decay, capturable, clear_grads)
         self.b1, self.b2, self.eps = float(betas[0]), float(betas[1]), float(eps)
 
     def _step_size(self, t):
