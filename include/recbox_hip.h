@@ -61,7 +61,9 @@ typedef enum {
   RBX_POOL_MEAN_VALUE = 2,       /* recbox MaskedAveragePooling: sum / (#rows with sum_d != 0 + eps) */
   RBX_POOL_MEAN_ID = 3,          /* rechub AveragePooling: sum_{id != mask_id} / (count + eps) */
   RBX_POOL_SUM_ID = 4,           /* rechub SumPooling with InputMask */
-  RBX_POOL_CONCAT = 5            /* rechub ConcatPooling: keep [L, dim] */
+  RBX_POOL_CONCAT = 5,           /* rechub ConcatPooling: keep [L, dim] */
+  RBX_POOL_MAX = 6               /* ragged bags only (rbx_embed_csr_fwd_max): elementwise max, torch's EmbeddingBag mode="max";
+                                  * honours mask_id when one is set, ignores eps; the padded lookup refuses it */
 } rbx_pool_t;
 
 /* One feature of a multi-table lookup.  Output slot of sample b:
@@ -145,8 +147,8 @@ int rbx_embed_bwd_indexed(const rbx_field_t* fields, int32_t n_fields, int64_t b
  *   offsets  [batch + 1], RBX_I32 or RBX_I64, contiguous: bag b = indices[offsets[b] : offsets[b + 1]).  offsets[0] may be
  *            > 0 and offsets[batch] < nnz (ids outside every bag are never looked up); a bag may be empty: a zero output
  *            row, and for the mean pools a scale of 1 / (0 + eps) times a zero sum = 0.
- *   pool     RBX_POOL_SUM, RBX_POOL_SUM_ID, RBX_POOL_MEAN_ID or RBX_POOL_MEAN_VALUE; RBX_POOL_NONE / RBX_POOL_CONCAT return
- *            RBX_ERR_UNSUPPORTED.
+ *   pool     RBX_POOL_SUM, RBX_POOL_SUM_ID, RBX_POOL_MEAN_ID or RBX_POOL_MEAN_VALUE, or RBX_POOL_MAX through the calls of its
+ *            own below; RBX_POOL_NONE / RBX_POOL_CONCAT return RBX_ERR_UNSUPPORTED.
  * Malformed offsets cannot make a kernel read outside indices[0, nnz): every bag is clamped to 0 <= begin <= end <= nnz
  * before an index is read, and bit 1 (value 2) of *d_status is set when the clamp changed anything (a decreasing pair, a
  * negative value, a value above nnz).  Ids outside [0, vocab) set bit 0 and read as zero rows, as in rbx_embed_fwd.
@@ -205,7 +207,30 @@ int rbx_embed_bwd_indexed(const rbx_field_t* fields, int32_t n_fields, int64_t b
  *                                and positions outside every bag are neither read nor written.  A rule without its state
  *                                array returns RBX_ERR_INVALID.  clear_grad != 0: the lane group that steps a row writes
  *                                zeros over that gradient row once it holds it in registers (non-temporal stores): the
- *                                step and the re-zero in one launch, table and state bit-equal to clear_grad = 0. */
+ *                                step and the re-zero in one launch, table and state bit-equal to clear_grad = 0.
+ *
+ * Max pool (RBX_POOL_MAX; torch.nn.EmbeddingBag(mode="max"), whose CPU result is the reference).  "usable" as above, with
+ * mask_id honoured whenever it is set (torch excludes padding_idx from the max: pass it as mask_id).
+ *   out[b, out_off + d]    = max over the usable j of bag b of table[id_j][d]; a bag without a usable id (empty, all masked,
+ *                            all out of range) gives a row of zeros, never -inf, and no table gradient
+ *   argpos[b, out_off + d] = the position j in [0, nnz) of the winner in the descriptor's index array, -1 where the bag
+ *                            had no usable id.  Ties: the LOWEST position wins (torch: strict >, first occurrence)
+ *   dTable[id_argpos[b, c]][d] += dY[b, c], summed through the sorted pairs: no float atomics, the same bits from run to
+ *                            run; the padding_idx row is read in the forward and keeps a zero gradient row
+ * Table values are finite: NaN and +-inf in a table are outside the contract.  Status bits and the offset clamp as above.
+ *   rbx_embed_csr_fwd_max  every descriptor must be RBX_POOL_MAX (else RBX_ERR_UNSUPPORTED).  d_argpos: int32 [batch,
+ *                          arg_stride_b], a descriptor's columns at out_off .. out_off + dim as in d_out.  long_threshold as in
+ *                          the `_long` calls below; 0 = no hand-off and no workspace.  A max selects and never rounds, so the
+ *                          long form is BIT-EQUAL to the lane-group walk at every threshold, d_out and d_argpos alike.
+ *   rbx_embed_csr_fwd_max_workspace_size  rbx_embed_csr_fwd_long_workspace_size plus one int32 partial argpos row per
+ *                          segment slot; the same guarantees (no pointer read, never shrinks when an nnz grows).
+ *   rbx_embed_csr_bwd_max  over the workspace rbx_embed_csr_sort_weighted leaves (position-valued pairs); every descriptor
+ *                          RBX_POOL_MAX.  d_argpos is only compared with positions, never used as an address: no content
+ *                          of it makes a kernel read out of bounds.  accumulate as rbx_embed_csr_bwd.
+ * The calls that never pool -- rbx_embed_csr_bwd_workspace_size, _sort, _sort_weighted, _rezero, _sparse_update -- take
+ * RBX_POOL_MAX descriptors like any other; every call that pools a sum or a mean, or takes weights (rbx_embed_csr_fwd,
+ * _fwd_long, _fwd_weighted, _fwd_weighted_long, _bwd, _bwd_weighted, _weight_grad, _weight_grad_long), returns
+ * RBX_ERR_UNSUPPORTED for one before anything is cleared or launched. */
 #define RBX_MAX_BAGS 32
 typedef struct rbx_bag {
   const void*  indices;          /* [nnz] ids */
@@ -248,6 +273,13 @@ struct rbx_opt;                  /* rbx_opt_t, declared with rbx_embed_sparse_up
 int rbx_embed_csr_sparse_update(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, const void* d_workspace,
                                 size_t workspace_bytes, const struct rbx_opt* opt, float* const* d_state1,
                                 float* const* d_state2, int32_t clear_grad, void* stream);
+size_t rbx_embed_csr_fwd_max_workspace_size(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, int64_t long_threshold);
+int rbx_embed_csr_fwd_max(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, int64_t long_threshold, float* d_out,
+                          int64_t out_stride_b, int32_t* d_argpos, int64_t arg_stride_b, void* d_workspace,
+                          size_t workspace_bytes, int32_t* d_status, void* stream);
+int rbx_embed_csr_bwd_max(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, const float* d_dout, int64_t out_stride_b,
+                          const int32_t* d_argpos, int64_t arg_stride_b, int32_t accumulate, void* d_workspace,
+                          size_t workspace_bytes, void* stream);
 
 /* The long-bag form of the three bag-walking calls above.  They map one lane group to one bag whatever its length, so a
  * few bags of thousands of ids keep a wave (and the launch) waiting for one group.  The `_long` calls take a

@@ -8,8 +8,10 @@ gradient, so that no zero fill is inside the bracket) with HIP events on torch's
 Cases: (1) every bag 50 ids = the padded L = 50 call's lookups; (2) lengths uniform in 1 .. 50 against the same ids padded
 to 50; (3) skewed lengths (bags of 1 .. 9 ids, 0.1 % of them 1 000 .. 5 000) against the same nnz spread evenly, the skewed
 batch with the long-bag form off (threshold 0: a lane group per bag) and on (``--threshold``, default the one in force)
-alternating; (4) case 2's bags under SUM_ID with and without per-sample weights, and the weight-gradient call.  Every CSR
-variant calls what ``ops.embed_bags`` calls: the ``_long`` entry points with the threshold, the plain ones at 0."""
+alternating; (4) case 2's bags under SUM_ID with and without per-sample weights, and the weight-gradient call; (5) case
+2's bags under SUM_ID against POOL_MAX (rbx_embed_csr_fwd_max, the position-valued sort, rbx_embed_csr_bwd_max), and the
+ATen routes to a max over the same ids.  Every CSR variant calls what ``ops.embed_bags`` calls: the ``_long`` entry points
+with the threshold, the plain ones at 0.  ``--cases 5`` runs a subset."""
 import argparse
 import os
 import statistics
@@ -162,6 +164,73 @@ class Weighted(object):
             _lib.check(lib.rbx_embed_csr_weight_grad(self.plan.arr, 1, B, self.out.data_ptr(), D, self.dwarr, None, ops._stream()))
 
 
+class MaxPool(object):
+    """Case 2's bags under POOL_MAX: the forward also stores argpos, the backward reads it beside dY."""
+
+    def __init__(self, emb, grad, bags):
+        self.plan = ops.BagPlan([ops.BagSpec("h", D, 0, 0, _lib.POOL_MAX, emb.num_embeddings, mask_id=0)])
+        self.w, self.g = emb.weight, grad
+        self.out = torch.empty(B, D, device="cuda")
+        self.argpos = torch.empty(B, D, dtype=torch.int32, device="cuda")
+        self.plan.bind_inputs([bags])
+        self.plan.bind_params([self.w], [self.g])
+        self.nbytes = lib.rbx_embed_csr_bwd_workspace_size(self.plan.arr, 1, B)
+        self.ws = torch.empty(self.nbytes, dtype=torch.uint8, device="cuda")
+        self.lookups = bags.nnz
+        self.threshold = ops.bag_long_threshold()
+        self.lbytes = lib.rbx_embed_csr_fwd_max_workspace_size(self.plan.arr, 1, B, self.threshold)
+        self.lws = torch.empty(max(self.lbytes, 1), dtype=torch.uint8, device="cuda")
+
+    def fwd(self):
+        _lib.check(lib.rbx_embed_csr_fwd_max(self.plan.arr, 1, B, self.threshold, self.out.data_ptr(), D, self.argpos.data_ptr(), D,
+                                             self.lws.data_ptr(), self.lbytes, None, ops._stream()))
+
+    def sort(self):
+        _lib.check(lib.rbx_embed_csr_sort_weighted(self.plan.arr, 1, B, self.ws.data_ptr(), self.nbytes, None, ops._stream()))
+
+    def bwd(self):
+        _lib.check(lib.rbx_embed_csr_bwd_max(self.plan.arr, 1, B, self.out.data_ptr(), D, self.argpos.data_ptr(), D, 1,
+                                             self.ws.data_ptr(), self.nbytes, ops._stream()))
+
+
+def aten_max(emb, bags, repeats, lines):
+    """The routes to a max over the same ids a caller has without this library: forward only, and torch's own
+    ``F.embedding_bag(mode="max")`` with its autograd backward (a fresh dense gradient per call)."""
+    w, idx, off = emb.weight, bags.indices, bags.offsets
+    pad = padded_of(bags)
+    lengths = (off[1:] - off[:-1])
+    live = (torch.arange(L, device="cuda")[None, :] < lengths[:, None])[:, :, None]
+    neg = torch.finfo(torch.float32).min
+
+    def gather_segment():
+        with torch.no_grad():
+            return torch.segment_reduce(w[idx], "max", offsets=off, axis=0)
+
+    def gather_padded():
+        with torch.no_grad():
+            return torch.where(live, w[pad], neg).max(dim=1).values
+
+    def bag_fwd():
+        with torch.no_grad():
+            return torch.nn.functional.embedding_bag(idx, w, off, mode="max", include_last_offset=True)
+
+    dy = torch.rand(B, D, device="cuda")
+
+    def bag_fwd_bwd():
+        out = torch.nn.functional.embedding_bag(idx, w, off, mode="max", include_last_offset=True)
+        return torch.autograd.grad(out, w, dy)
+
+    names = ["gather + segment_reduce(max)", "padded gather + max(dim=1)", "F.embedding_bag(max) forward",
+             "F.embedding_bag(max) forward + autograd backward"]
+    res = bracket([gather_segment, gather_padded, bag_fwd, bag_fwd_bwd], repeats)
+    lines.append("\nATen over the same ids:\n")
+    lines.append("| route | us (min .. max) |")
+    lines.append("|---|---|")
+    for n, r in zip(names, res):
+        lines.append("| %s | %.1f (%.1f .. %.1f) |" % ((n,) + r))
+    return res
+
+
 def bags_of(lengths, rows, gen):
     offsets = torch.zeros(B + 1, dtype=torch.int64)
     torch.cumsum(lengths, 0, out=offsets[1:])
@@ -195,6 +264,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--rows", type=int, default=10000000)
     ap.add_argument("--out", default="", help="also write the markdown report to this file")
+    ap.add_argument("--cases", default="1,2,3,4,5", help="comma-separated case numbers to run")
     ap.add_argument("--threshold", type=int, default=None, help="ops.bag_long_threshold for the run (default: the one in force)")
     a = ap.parse_args()
     if a.threshold is not None:
@@ -209,35 +279,45 @@ def main():
         commit = "working tree"
     lines = ["box: %s, torch %s; commit: %s; B = %d, table %d x %d, MEAN_ID, %d repeats, variants alternating; long-bag threshold %d"
              % (torch.cuda.get_device_name(0), torch.__version__, commit, B, a.rows, D, a.repeats, ops.bag_long_threshold())]
+    want = set(int(c) for c in a.cases.split(","))
     full = bags_of(torch.full((B,), L, dtype=torch.int64), a.rows, gen)
-    pad = Padded(emb, grad, full.indices.view(B, L))
-    case("1. every bag %d ids (the padded call's lookups; `padded again` = its run-to-run spread)" % L,
-         ["padded", "CSR", "padded again"], [pad, Ragged(emb, grad, full), Padded(emb, grad, full.indices.view(B, L))],
-         a.repeats, lines)
     uni = bags_of(torch.randint(1, L + 1, (B,), generator=gen), a.rows, gen)
-    case("2. lengths uniform in 1 .. %d against the same ids padded to %d" % (L, L), ["padded", "CSR"],
-         [Padded(emb, grad, padded_of(uni)), Ragged(emb, grad, uni)], a.repeats, lines)
-    skew = torch.randint(1, 10, (B,), generator=gen)
-    where = torch.randperm(B, generator=gen)[:B // 1000]
-    skew[where] = torch.randint(1000, 5001, (where.numel(),), generator=gen)
-    total = int(skew.sum())
-    even = torch.full((B,), total // B, dtype=torch.int64)
-    even[:total - int(even.sum())] += 1
-    skewed = bags_of(skew, a.rows, gen)
-    walked, handed = Ragged(emb, grad, skewed, threshold=0), Ragged(emb, grad, skewed)
-    case("3. skewed lengths (1 .. 9, 0.1 pct of the bags 1 000 .. 5 000) against the same nnz spread evenly",
-         ["even", "skewed, threshold 0", "skewed, threshold %d" % handed.threshold],
-         [Ragged(emb, grad, bags_of(even, a.rows, gen)), walked, handed], a.repeats, lines)
-    torch.cuda.synchronize()
-    same = torch.equal(walked.out[(skew < max(handed.threshold, 1)).cuda()], handed.out[(skew < max(handed.threshold, 1)).cuda()])
-    err = float((walked.out - handed.out).abs().max())
-    lines.append("\nlong form on the skewed batch: %d bags in %d segments; bags below the threshold bit-equal to threshold 0: %s; "
-                 "max |difference| over all bags %.3g" % (long_counts(handed.lws) + (same, err)))
-    plain, scored = Weighted(emb, grad, uni, False), Weighted(emb, grad, uni, True)
-    case("4. case 2's bags under SUM_ID, unweighted against random per-sample weights", ["unweighted", "weighted"],
-         [plain, scored], a.repeats, lines)
-    g = bracket([scored.wgrad], a.repeats)[0]
-    lines.append("\nweight gradient (memset of dw + bag_walk_kernel<WeightGradOp>): %.1f us (%.1f .. %.1f)" % g)
+    if 1 in want:
+        pad = Padded(emb, grad, full.indices.view(B, L))
+        case("1. every bag %d ids (the padded call's lookups; `padded again` = its run-to-run spread)" % L,
+             ["padded", "CSR", "padded again"], [pad, Ragged(emb, grad, full), Padded(emb, grad, full.indices.view(B, L))],
+             a.repeats, lines)
+    if 2 in want:
+        case("2. lengths uniform in 1 .. %d against the same ids padded to %d" % (L, L), ["padded", "CSR"],
+             [Padded(emb, grad, padded_of(uni)), Ragged(emb, grad, uni)], a.repeats, lines)
+    if 3 in want:
+        skew = torch.randint(1, 10, (B,), generator=gen)
+        where = torch.randperm(B, generator=gen)[:B // 1000]
+        skew[where] = torch.randint(1000, 5001, (where.numel(),), generator=gen)
+        total = int(skew.sum())
+        even = torch.full((B,), total // B, dtype=torch.int64)
+        even[:total - int(even.sum())] += 1
+        skewed = bags_of(skew, a.rows, gen)
+        walked, handed = Ragged(emb, grad, skewed, threshold=0), Ragged(emb, grad, skewed)
+        case("3. skewed lengths (1 .. 9, 0.1 pct of the bags 1 000 .. 5 000) against the same nnz spread evenly",
+             ["even", "skewed, threshold 0", "skewed, threshold %d" % handed.threshold],
+             [Ragged(emb, grad, bags_of(even, a.rows, gen)), walked, handed], a.repeats, lines)
+        torch.cuda.synchronize()
+        short = (skew < max(handed.threshold, 1)).cuda()
+        same = torch.equal(walked.out[short], handed.out[short])
+        err = float((walked.out - handed.out).abs().max())
+        lines.append("\nlong form on the skewed batch: %d bags in %d segments; bags below the threshold bit-equal to threshold 0: "
+                     "%s; max |difference| over all bags %.3g" % (long_counts(handed.lws) + (same, err)))
+    if 4 in want:
+        plain, scored = Weighted(emb, grad, uni, False), Weighted(emb, grad, uni, True)
+        case("4. case 2's bags under SUM_ID, unweighted against random per-sample weights", ["unweighted", "weighted"],
+             [plain, scored], a.repeats, lines)
+        g = bracket([scored.wgrad], a.repeats)[0]
+        lines.append("\nweight gradient (memset of dw + bag_walk_kernel<WeightGradOp>): %.1f us (%.1f .. %.1f)" % g)
+    if 5 in want:
+        case("5. case 2's bags under SUM_ID against POOL_MAX (forward + argpos; position-valued sort; masked reduce)",
+             ["sum", "max"], [Weighted(emb, grad, uni, False), MaxPool(emb, grad, uni)], a.repeats, lines)
+        aten_max(emb, uni, a.repeats, lines)
     text = "\n".join(lines) + "\n"
     print(text)
     if a.out:

@@ -17,7 +17,7 @@ RBX_NO_ID = -(1 << 63)
 RBX_OK, RBX_ERR_INVALID, RBX_ERR_LAUNCH, RBX_ERR_WORKSPACE, RBX_ERR_UNSUPPORTED = 0, -1, -2, -3, -4
 RBX_I32, RBX_I64, RBX_F32, RBX_F64 = 0, 1, 2, 3
 FIELD_CATEGORICAL, FIELD_NUMERIC, FIELD_DENSE = 0, 1, 2
-POOL_NONE, POOL_SUM, POOL_MEAN_VALUE, POOL_MEAN_ID, POOL_SUM_ID, POOL_CONCAT = 0, 1, 2, 3, 4, 5
+POOL_NONE, POOL_SUM, POOL_MEAN_VALUE, POOL_MEAN_ID, POOL_SUM_ID, POOL_CONCAT, POOL_MAX = 0, 1, 2, 3, 4, 5, 6
 INTERACTION_MODES = {"product_sum": 0, "bi_interaction": 1, "inner_product": 2, "elementwise_product": 3}
 # ``phases`` of rbx_fm_sort_phases: ids -> the workspace's compact int32 matrix (both tiers need it done); tier B: (row,
 # sample) pairs + radix sort; tier A: the per-block sorts
@@ -123,6 +123,9 @@ SIGNATURES = {
     "rbx_embed_csr_fwd_long": (ctypes.c_int, [_BP, _i32, _i64, _i64, _P, _i64, _P, _P, _sz, _P, _P]),
     "rbx_embed_csr_fwd_weighted_long": (ctypes.c_int, [_BP, _i32, _i64, _i64, _PP, _P, _i64, _P, _sz, _P, _P]),
     "rbx_embed_csr_weight_grad_long": (ctypes.c_int, [_BP, _i32, _i64, _i64, _P, _i64, _PP, _P, _sz, _P, _P]),
+    "rbx_embed_csr_fwd_max_workspace_size": (_sz, [_BP, _i32, _i64, _i64]),
+    "rbx_embed_csr_fwd_max": (ctypes.c_int, [_BP, _i32, _i64, _i64, _P, _i64, _P, _i64, _P, _sz, _P, _P]),
+    "rbx_embed_csr_bwd_max": (ctypes.c_int, [_BP, _i32, _i64, _P, _i64, _P, _i64, _i32, _P, _sz, _P]),
     "rbx_shard_int_chunk": (_sz, [_GP]),
     "rbx_shard_float_rows": (_sz, [_GP]),
     "rbx_shard_route_workspace_size": (_sz, [_GP, _i32]),

@@ -12,12 +12,15 @@
 // coalesced sweep of the bag's ids in chunks of 4 * SG, classify + compact into the group's LDS list, U = 4 rows in
 // flight, R sub-groups for narrow rows.  The wave-uniform loop bound is the longest bag of the wave.  Chunk size, U and
 // the sub-group rule are the padded kernel's own constants (rbx_rowfrag.h), so a bag is walked in the order the padded
-// call walks the same live ids.  What happens to a row is the Op's business, and the three ops differ in nothing else:
+// call walks the same live ids.  What happens to a row is the Op's business, and the four ops differ in nothing else:
 //   PoolOp          (forward)          acc += row, the mean pools count; butterfly, 1 / (count + eps), store.  Bit-equal
 //                                      to the padded call.  No second LDS list: 4 KB per workgroup.
 //   WeightedPoolOp  (weighted forward) a weight travels with the id (a second list, 8 KB); acc += w * row; butterfly,
 //                                      store.  x * 1.0f is x: all-ones weights give PoolOp's bits.
 //   WeightGradOp    (weight gradient)  the position travels with the id; dw[position] = <dY[bag, slot], row>; no close.
+//   MaxPoolOp       (max forward)      the position travels with the id; a row is taken elementwise where it is greater;
+//                                      butterfly over (value, position) pairs, store the row and argpos.  Exact, so its
+//                                      long form is bit-equal to the walk.
 // Sweep, compaction and batch order exist once, so the two bit-equalities hold by construction, not by keeping copies in
 // step.  check_launch still reports the ops under the names they had as separate kernels (Op::kName).
 // Backward.  The positions of a descriptor's index array are its lookups.  csr_bag_map_kernel (a lane group per bag,
@@ -33,6 +36,10 @@
 // Table gradient: the weighted sort's pair value names the lookup's POSITION inside its descriptor's index array
 // (csr_keys_kernel<RB, true>), and WeightedBagPolicy reads bag = map[position] and w[position] -- rbx_embed_bwd_indexed's
 // indirection plus one factor; passes, reduce and fix-ups unchanged.  Weight gradient: WeightGradOp; no sort involved.
+// Max pool (RBX_POOL_MAX; torch's mode="max").  Forward: MaxPoolOp, which also leaves argpos, the winner's position per output
+// element (-1: the bag had no usable id, the row is zeros).  Table gradient: the position-valued sort again, and MaxBagPolicy
+// reads bag = map[position] and keeps dY[bag, c] where argpos[bag, c] names that position -- WeightedBagPolicy with a mask
+// instead of a factor.  argpos is only ever compared, never used as an address.
 // Host side.  classify_bags sorts a call's descriptors into (float4 | scalar) x (unweighted | weighted) launches and
 // refuses a dim no lane group holds before anything is written; csr_forward serves the four forward entry points and
 // csr_weight_grad the two weight-gradient ones, the long form being a parameter of both.
@@ -189,6 +196,7 @@ struct NoPayload {};
 // sum / mean pools: acc += row, the mean pools count as rbx_pool_t says; close = butterfly, 1 / (count + eps), store
 struct PoolOp {
   static constexpr const char* kName = "embed_csr_kernel";
+  static constexpr bool kMasksIds = false;   // mask_id counts for the _ID pools only (true: whenever it is set)
   static constexpr bool kHasPayload = false;
   using Payload = NoPayload;
   struct Args {
@@ -242,6 +250,7 @@ struct PoolOp {
 // row before the add.  x * 1.0f is x: all-ones weights give PoolOp's bits.
 struct WeightedPoolOp {
   static constexpr const char* kName = "embed_csr_weighted_kernel";
+  static constexpr bool kMasksIds = false;
   static constexpr bool kHasPayload = true;
   using Payload = float;
   struct Args {
@@ -297,6 +306,7 @@ __device__ __forceinline__ float row_dot(const RowFrag<W, NV, false>& a, const R
 
 struct WeightGradOp {
   static constexpr const char* kName = "csr_weight_grad_kernel";
+  static constexpr bool kMasksIds = false;
   static constexpr bool kHasPayload = true;
   using Payload = int;
   struct Args {
@@ -321,6 +331,98 @@ struct WeightGradOp {
     }
     template <int MODE, int G>
     __device__ __forceinline__ void close(const Args&, const LongArgs&, const BagK&, long long, long long, long long, bool, int) {}
+  };
+};
+
+
+// max pool: a row is taken elementwise where nothing has been taken yet or where it is strictly greater, and the position of
+// the id it came with is kept per element.  A lane group meets its own ids in ascending position, so within a sub-group
+// strict > alone is "first occurrence wins".  close() combines (value, position) pairs across the R sub-groups -- in
+// kSegments across the whole wave -- by an xor butterfly under one lexicographic rule: the greater value wins, on equal
+// values the lower position, and "nothing taken" (position -1) loses to anything.  That rule is a total order on the pairs
+// of a bag (positions are distinct), so its maximum does not depend on the order of the combination: the result is "the
+// lowest position among the maxima" by construction, whatever R, the mode or the threshold.  Table values are finite
+// (NaN / +-inf are outside the contract).  mask_id is honoured whenever it is set: kNoId equals no in-range id.
+struct MaxPoolOp {
+  static constexpr const char* kName = "embed_csr_max_kernel";
+  static constexpr bool kMasksIds = true;
+  static constexpr bool kHasPayload = true;
+  using Payload = int;
+  struct Args {
+    float* out;
+    long long stride_b;
+    int* argpos;            // [batch, arg_stride]: the winner's position per output element, -1 where there is none
+    long long arg_stride;
+    int* parg;              // kSegments: [cap_segs][pstride] partial argpos rows beside LongArgs::part
+    int arg_vec;            // argpos rows take 16-byte stores
+  };
+  template <int W, int NV, bool VEC>
+  struct Bag {
+    using Frag = RowFrag<W, NV, VEC>;
+    static constexpr int E = Frag::kElems;
+    Frag val;
+    int pos[E];
+    bool any;
+    __device__ __forceinline__ void open(const Args&, const BagK&, int, long long, bool, int) {
+      val.zero();
+#pragma unroll
+      for (int q = 0; q < E; ++q) pos[q] = -1;
+      any = false;
+    }
+    __device__ __forceinline__ int payload(long long p, bool) const { return static_cast<int>(p); }   // < end <= nnz
+    __device__ __forceinline__ void row(const BagK&, Frag& r, int id, int p, int) {
+      if (id < 0) return;                                   // (an empty slot of the batch)
+#pragma unroll
+      for (int q = 0; q < E; ++q) {
+        const bool take = !any || r.at(q) > val.at(q);
+        val.at(q) = take ? r.at(q) : val.at(q);
+        pos[q] = take ? p : pos[q];
+      }
+      any = true;
+    }
+    static __device__ __forceinline__ void store_pos(const int (&pos)[E], int* row, int dim, int lane_w, bool vec) {
+      constexpr int WD = Frag::W;
+#pragma unroll
+      for (int u = 0; u < NV; ++u) {
+        const int e = (lane_w + u * W) * WD;
+        if (e >= dim) continue;
+        if constexpr (VEC) {
+          if (vec) {
+            *reinterpret_cast<int4*>(row + e) = make_int4(pos[u * 4], pos[u * 4 + 1], pos[u * 4 + 2], pos[u * 4 + 3]);
+          } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) row[e + k] = pos[u * 4 + k];
+          }
+        } else {
+          row[e] = pos[u];
+        }
+      }
+    }
+    template <int MODE, int G>
+    __device__ __forceinline__ void close(const Args& a, const LongArgs& la, const BagK& fd, long long t, long long b, long long,
+                                          bool owner, int lane_w) {
+#pragma unroll
+      for (int o = W; o < (MODE == kSegments ? 64 : G); o <<= 1) {   // every lane joins the butterfly (segments: the whole wave)
+        Frag ov = val.xor_get(o);
+#pragma unroll
+        for (int q = 0; q < E; ++q) {
+          const int op = __shfl_xor(pos[q], o, 64);
+          const float x = ov.at(q), v = val.at(q);
+          const bool take = op >= 0 && (pos[q] < 0 || x > v || (x == v && op < pos[q]));
+          val.at(q) = take ? x : v;
+          pos[q] = take ? op : pos[q];
+        }
+      }
+      if (!owner) return;
+      // an element nothing was taken for still holds the 0 of open(): the zero row of a bag without a usable id
+      if constexpr (MODE == kSegments) {                  // t < cap_segs (long_counts); pstride is a multiple of 4
+        val.store(la.part + t * la.pstride, fd.dim, lane_w);
+        store_pos(pos, a.parg + t * la.pstride, fd.dim, lane_w, true);
+      } else {
+        val.store(a.out + b * a.stride_b + fd.out_off, fd.dim, lane_w);
+        store_pos(pos, a.argpos + b * a.arg_stride + fd.out_off, fd.dim, lane_w, a.arg_vec != 0);
+      }
+    }
   };
 };
 
@@ -376,7 +478,7 @@ __global__ __launch_bounds__(256, kSeqWaves) void bag_walk_kernel(const BagPack 
     }
     const BagK& fd = P.f[f];
     const int pool = fd.pool, dim = fd.dim, dt = fd.idx_dtype;
-    const bool id_pool = (pool == RBX_POOL_MEAN_ID || pool == RBX_POOL_SUM_ID);
+    const bool id_pool = Op::kMasksIds || (pool == RBX_POOL_MEAN_ID || pool == RBX_POOL_SUM_ID);
     if (MODE != kSegments && alive) {
       bool bad;
       bag_range(fd, b, &begin, &end, &bad);
@@ -513,6 +615,22 @@ static int check_weighted_pools(const rbx_bag_t* bags, int n, const void* const*
   return RBX_OK;
 }
 
+// the sum / mean entry points and everything with weights: a max pool has calls of its own (rbx_embed_csr_fwd_max / _bwd_max)
+static int check_no_max(const rbx_bag_t* bags, int n, const char* who) {
+  for (int i = 0; bags != nullptr && i < n; ++i)
+    if (bags[i].pool == RBX_POOL_MAX)
+      return fail(RBX_ERR_UNSUPPORTED, "%s: bag %d is a max pool; it goes through rbx_embed_csr_fwd_max / rbx_embed_csr_bwd_max "
+                  "(and takes no per-sample weights)", who, i);
+  return RBX_OK;
+}
+static int check_all_max(const rbx_bag_t* bags, int n, const char* who) {
+  for (int i = 0; bags != nullptr && i < n; ++i)
+    if (bags[i].pool != RBX_POOL_MAX)
+      return fail(RBX_ERR_UNSUPPORTED, "%s: bag %d has pool mode %d; every descriptor of the call must be RBX_POOL_MAX", who, i,
+                  bags[i].pool);
+  return RBX_OK;
+}
+
 static int compact(int64_t v) { return (v == RBX_NO_ID || v < INT_MIN || v > INT_MAX) ? kNoId : static_cast<int>(v); }
 
 // The size checks of pack_bags and long_plan (which also sees descriptors whose pointers are not set yet): i < 0 the
@@ -540,8 +658,8 @@ static int pack_bags(const rbx_bag_t* bags, int n, int64_t batch, BagK* out) {
   for (int i = 0; i < n; ++i) {
     const rbx_bag_t& g = bags[i];
     if (g.pool == RBX_POOL_NONE || g.pool == RBX_POOL_CONCAT)
-      return fail(RBX_ERR_UNSUPPORTED, "bag %d: pool mode %d keeps one slot per id; ragged bags are pooled (sum / mean)", i, g.pool);
-    if (g.pool < RBX_POOL_NONE || g.pool > RBX_POOL_CONCAT) return fail(RBX_ERR_INVALID, "bag %d: bad pool mode %d", i, g.pool);
+      return fail(RBX_ERR_UNSUPPORTED, "bag %d: pool mode %d keeps one slot per id; ragged bags are pooled (sum / mean / max)", i, g.pool);
+    if (g.pool < RBX_POOL_NONE || g.pool > RBX_POOL_MAX) return fail(RBX_ERR_INVALID, "bag %d: bad pool mode %d", i, g.pool);
     rc = check_sizes(bags, n, batch, i);
     if (rc != RBX_OK) return rc;
     if (g.nnz > 0 && g.indices == nullptr) return fail(RBX_ERR_INVALID, "bag %d: indices is NULL", i);
@@ -719,7 +837,9 @@ static int csr_plan(const rbx_bag_t* bags, int n, int64_t batch, const float* do
     f.seq_len = 1;
     f.ids_dtype = g.indices_dtype;
     f.kind = RBX_FIELD_CATEGORICAL;
-    f.pool = g.pool;
+    // the sort of a max pool drops what the sort of RBX_POOL_SUM_ID drops (padding_idx, mask_id when set, ids out of range):
+    // the padded path's plan is handed that pool and learns no new one
+    f.pool = g.pool == RBX_POOL_MAX ? RBX_POOL_SUM_ID : g.pool;
     f.eps = g.eps;
     f.table_stride = 0;
     lookups_of[i] = static_cast<unsigned long long>(g.nnz);
@@ -797,6 +917,74 @@ struct WeightedBagPolicy {
   }
 };
 
+// ---- max reduce: a lookup contributes dY[map[position], c] where argpos[that bag, c] names its position -------------------
+// WeightedBagPolicy with a mask instead of a factor.  The mask is applied in place, right behind the two loads: a second
+// per-lookup fragment for the argpos slice would hold U * NV * 4 more registers than RBX_REDUCE_WAVES leaves at the wide
+// forms, and this reduce is on no measured step.  argpos is compared with the position and never used as an address: no
+// content of that buffer makes a kernel read out of bounds.
+struct MaxBagPolicy {
+  static constexpr bool kHasCount = false;
+  struct Args {
+    const float* dout;
+    long long stride_b;
+    const int* argpos;
+    long long arg_stride;
+    const int* map;
+    int accumulate;
+    unsigned lk_off[RBX_MAX_BAGS];        // by descriptor index (RedField::slot)
+  };
+  template <int G, int NV, bool VEC>
+  static __device__ __forceinline__ void fetch(const Args& a, const RedField& fd, unsigned pos, int lane_g, Frag<G, NV, VEC>& frag,
+                                               float& w) {
+    const int bag = a.map[a.lk_off[fd.slot] + pos];
+    w = 1.0f;
+    frag.load_from(a.dout + static_cast<long long>(bag) * a.stride_b + fd.out_off, fd.dim, lane_g);
+    const int* __restrict__ arg = a.argpos + static_cast<long long>(bag) * a.arg_stride + fd.out_off;
+    const int me = static_cast<int>(pos);
+    constexpr int W = VEC ? 4 : 1;
+#pragma unroll
+    for (int u = 0; u < NV; ++u) {
+      int e = (lane_g + u * G) * W;
+      e = e < fd.dim ? e : fd.dim - W;                     // load_from's rule: lanes beyond dim re-read the last vector
+      if constexpr (VEC) {
+        const int4 t = *reinterpret_cast<const int4*>(arg + e);
+        frag.a[u * 4 + 0] = t.x == me ? frag.a[u * 4 + 0] : 0.f;
+        frag.a[u * 4 + 1] = t.y == me ? frag.a[u * 4 + 1] : 0.f;
+        frag.a[u * 4 + 2] = t.z == me ? frag.a[u * 4 + 2] : 0.f;
+        frag.a[u * 4 + 3] = t.w == me ? frag.a[u * 4 + 3] : 0.f;
+      } else {
+        frag.a[u] = arg[e] == me ? frag.a[u] : 0.f;
+      }
+    }
+  }
+  static __device__ __forceinline__ float weight(const Args&, float w) { return w; }
+  template <class F>
+  static __device__ __forceinline__ void prefetch(const Args& a, const RedField& fd, unsigned row, int lane_g, F& pre) {
+    if (a.accumulate) pre.add_from(fd.grad + static_cast<size_t>(row) * fd.dim, fd.dim, lane_g);
+  }
+  template <class F>
+  static __device__ __forceinline__ void prefetch_raw(const Args& a, const RedField& fd, unsigned row, int lane_g, F& pre) {
+    if (a.accumulate) pre.load_from(fd.grad + static_cast<size_t>(row) * fd.dim, fd.dim, lane_g);
+  }
+  template <class F>
+  static __device__ __forceinline__ void flush(const Args&, const RedField& fd, unsigned row, const F& acc, float, const F& pre,
+                                               int lane_g) {
+    F out = acc;
+    frag_add(out, pre);
+    out.store_nt(fd.grad + static_cast<size_t>(row) * fd.dim, fd.dim, lane_g);
+  }
+};
+// 16 floats per lane (D > 512): with 4 lookups in flight the masked fetch spilled 264 B per lane at RBX_REDUCE_WAVES; 2 fit
+template <>
+struct ReduceWideBatch<MaxBagPolicy> {
+  static constexpr int of(int per_lane) { return per_lane > 8 ? 2 : 4; }
+};
+// the mask zeroes single elements: the lanes of a group disagree on whether a chunk's tail is zero
+template <>
+struct ReduceLaneZeros<MaxBagPolicy> {
+  static constexpr bool value = true;
+};
+
 // the sort of both paths: map, pairs (POS: position-valued), radix passes
 static int csr_sort(const rbx_bag_t* bags, int n_bags, int64_t batch, void* d_workspace, size_t workspace_bytes,
                     int* d_status, hipStream_t s, bool pos) {
@@ -867,6 +1055,45 @@ __global__ __launch_bounds__(256) void csr_long_finish_kernel(const BagPack P, c
       float a = 0.f;
       for (long long j = 0; j < nseg; ++j) a += src[j * LA.pstride + d];
       dst[d] = mean ? a * inv : a;
+    }
+  }
+}
+
+// The max pool's finish, a wave per recorded bag: the maximum over the partial rows of its segments in ascending slot order
+// under strict > -- a later segment holds higher positions, so on equal values the earlier one keeps the element -- and a
+// partial with position -1 (no usable id in that segment) is skipped.  Exact: the bits of the lane-group walk.
+__global__ __launch_bounds__(256) void csr_long_max_finish_kernel(const BagPack P, const int F, const long long B,
+                                                                  float* __restrict__ out, const long long stride_b,
+                                                                  int* __restrict__ argpos, const long long arg_stride,
+                                                                  const int* __restrict__ parg, const LongArgs LA) {
+  int n_long;
+  long long n_segs;
+  long_counts(LA, &n_long, &n_segs);
+  const int lane = threadIdx.x & 63;
+  for (long long r = static_cast<long long>(blockIdx.x) * 4 + threadIdx.x / 64; r < n_long;
+       r += static_cast<long long>(gridDim.x) * 4) {
+    const LongRec rec = LA.recs[r];
+    if (rec.end <= rec.begin || static_cast<unsigned>(rec.desc) >= static_cast<unsigned>(F)) continue;   // refused: walked in place
+    const long long nseg = (static_cast<long long>(rec.end) - rec.begin + kSeg - 1) / kSeg;
+    if (rec.seg0 < 0 || rec.seg0 + nseg > n_segs || rec.bag < 0 || rec.bag >= B) continue;              // (long_append checked)
+    const BagK& fd = P.f[rec.desc];
+    float* dst = out + rec.bag * stride_b + fd.out_off;
+    int* adst = argpos + rec.bag * arg_stride + fd.out_off;
+    const float* src = LA.part + static_cast<long long>(rec.seg0) * LA.pstride;
+    const int* asrc = parg + static_cast<long long>(rec.seg0) * LA.pstride;
+    for (int d = lane; d < fd.dim; d += 64) {
+      float best = 0.f;
+      int at = -1;
+      for (long long j = 0; j < nseg; ++j) {
+        const int p = asrc[j * LA.pstride + d];
+        const float v = src[j * LA.pstride + d];
+        if (p >= 0 && (at < 0 || v > best)) {
+          best = v;
+          at = p;
+        }
+      }
+      dst[d] = best;
+      adst[d] = at;
     }
   }
 }
@@ -977,6 +1204,8 @@ static int csr_forward(const rbx_bag_t* bags, int n_bags, int64_t batch, bool ha
   BagPack all;
   int rc = pack_bags(bags, n_bags, batch, all.f);
   if (rc != RBX_OK) return rc;
+  rc = check_no_max(bags, n_bags, "the sum / mean forward");
+  if (rc != RBX_OK) return rc;
   if (weighted_call) {
     rc = check_weighted_pools(bags, n_bags, reinterpret_cast<const void* const*>(d_weights), "a weight array");
     if (rc != RBX_OK) return rc;
@@ -1030,6 +1259,8 @@ static int csr_weight_grad(const rbx_bag_t* bags, int n_bags, int64_t batch, boo
   BagPack all;
   int rc = pack_bags(bags, n_bags, batch, all.f);
   if (rc != RBX_OK) return rc;
+  rc = check_no_max(bags, n_bags, "the weight gradient");
+  if (rc != RBX_OK) return rc;
   if (d_dweights == nullptr) return fail(RBX_ERR_INVALID, "d_dweights is NULL");
   rc = check_weighted_pools(bags, n_bags, reinterpret_cast<const void* const*>(d_dweights), "a weight gradient");
   if (rc != RBX_OK) return rc;
@@ -1069,6 +1300,63 @@ static int csr_weight_grad(const rbx_bag_t* bags, int n_bags, int64_t batch, boo
   return RBX_OK;
 }
 
+// The max forward.  Its workspace is the long workspace with one int32 partial argpos row per segment slot behind it.
+static size_t max_workspace_bytes(const LongPlan& lp) {
+  return lp.bytes + (static_cast<size_t>(lp.cap_segs) * lp.pstride * 4 + 255) / 256 * 256;
+}
+
+static int csr_forward_max(const rbx_bag_t* bags, int n_bags, int64_t batch, int64_t threshold, float* d_out, int64_t out_stride_b,
+                           int* d_argpos, int64_t arg_stride_b, void* d_workspace, size_t workspace_bytes, int* d_status,
+                           hipStream_t s) {
+  BagPack all;
+  int rc = pack_bags(bags, n_bags, batch, all.f);
+  if (rc != RBX_OK) return rc;
+  rc = check_all_max(bags, n_bags, "rbx_embed_csr_fwd_max");
+  if (rc != RBX_OK) return rc;
+  LongPlan lp;
+  rc = long_plan(bags, n_bags, batch, threshold, &lp);
+  if (rc != RBX_OK) return rc;
+  if (batch == 0) return RBX_OK;
+  if (d_out == nullptr) return fail(RBX_ERR_INVALID, "d_out is NULL");
+  if (d_argpos == nullptr) return fail(RBX_ERR_INVALID, "d_argpos is NULL");
+  BagClasses<const float> c;
+  rc = classify_bags<const float>(bags, all, n_bags, d_out, out_stride_b, nullptr, false, &c);
+  if (rc != RBX_OK) return rc;
+  LongArgs la = {};
+  bool on = false;
+  int* parg = nullptr;
+  if (threshold > 0) {                                    // 0: no hand-off and no workspace
+    const size_t need = max_workspace_bytes(lp);
+    if (d_workspace == nullptr || workspace_bytes < need)
+      return fail(RBX_ERR_WORKSPACE, "workspace %zu B < required %zu B", d_workspace == nullptr ? size_t(0) : workspace_bytes, need);
+    rc = long_begin(bags, n_bags, batch, threshold, d_workspace, workspace_bytes, s, &lp, &on);
+    if (rc != RBX_OK) return rc;
+    la = long_args(lp, d_workspace);
+    parg = reinterpret_cast<int*>(static_cast<char*>(d_workspace) + lp.bytes);
+  }
+  const int arg_vec = (arg_stride_b % 4 == 0 && (reinterpret_cast<uintptr_t>(d_argpos) & 15) == 0) ? 1 : 0;
+  const MaxPoolOp::Args args = {d_out, out_stride_b, d_argpos, arg_stride_b, parg, arg_vec};
+  for (int k = 0; k < 2; ++k) {                            // two launch classes here: float4 and scalar
+    if (c.cnt[k] == 0) continue;
+    la.cls = k;
+    rc = bag_walk<MaxPoolOp>(k == 0, on ? kHandOff : kWalk, c.units[k], c.pack[k], c.cnt[k], batch, args, d_status, s, la);
+    if (rc != RBX_OK) return rc;
+  }
+  if (!on) return RBX_OK;
+  for (int k = 0; k < 2; ++k) {
+    if (c.cnt[k] == 0) continue;
+    la.cls = k;
+    rc = bag_walk<MaxPoolOp>(k == 0, kSegments, c.units[k], all, n_bags, batch, args, d_status, s, la);
+    if (rc != RBX_OK) return rc;
+  }
+  long long fb = (static_cast<long long>(lp.cap_bags) + 3) / 4;
+  if (fb > kCUs * 2) fb = kCUs * 2;
+  hipLaunchKernelGGL(csr_long_max_finish_kernel, dim3(static_cast<unsigned>(fb)), dim3(256), 0, s, all, n_bags,
+                     static_cast<long long>(batch), d_out, static_cast<long long>(out_stride_b), d_argpos,
+                     static_cast<long long>(arg_stride_b), parg, la);
+  return check_launch("csr_long_max_finish_kernel");
+}
+
 }  // namespace rbx
 
 extern "C" int rbx_embed_csr_fwd(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, float* d_out, int64_t out_stride_b,
@@ -1095,6 +1383,8 @@ extern "C" int rbx_embed_csr_bwd(const rbx_bag_t* bags, int32_t n_bags, int64_t 
   if (d_dout == nullptr) return fail(RBX_ERR_INVALID, "d_dout is NULL");
   CsrPlan c;
   int rc = csr_plan(bags, n_bags, batch, d_dout, out_stride_b, &c);
+  if (rc != RBX_OK) return rc;
+  rc = check_no_max(bags, n_bags, "rbx_embed_csr_bwd");
   if (rc != RBX_OK) return rc;
   if (c.p.n_lookups == 0 || batch == 0) return RBX_OK;
   if (d_workspace == nullptr || workspace_bytes < c.bytes)
@@ -1140,6 +1430,8 @@ extern "C" int rbx_embed_csr_bwd_weighted(const rbx_bag_t* bags, int32_t n_bags,
   if (rc != RBX_OK) return rc;
   CsrPlan c;
   rc = csr_plan(bags, n_bags, batch, d_dout, out_stride_b, &c);
+  if (rc != RBX_OK) return rc;
+  rc = check_no_max(bags, n_bags, "rbx_embed_csr_bwd_weighted");
   if (rc != RBX_OK) return rc;
   rc = check_weighted_pools(bags, n_bags, reinterpret_cast<const void* const*>(d_weights), "a weight array");
   if (rc != RBX_OK) return rc;
@@ -1198,4 +1490,55 @@ extern "C" int rbx_embed_csr_weight_grad_long(const rbx_bag_t* bags, int32_t n_b
                                               void* d_workspace, size_t workspace_bytes, int32_t* d_status, void* stream) {
   return rbx::csr_weight_grad(bags, n_bags, batch, true, long_threshold, d_dout, out_stride_b, d_dweights, d_workspace,
                               workspace_bytes, d_status, rbx::as_stream(stream));
+}
+
+// ---- the max pool (see MaxPoolOp, MaxBagPolicy) --------------------------------------------------------------------------
+extern "C" size_t rbx_embed_csr_fwd_max_workspace_size(const rbx_bag_t* bags, int32_t n_bags, int64_t batch,
+                                                       int64_t long_threshold) {
+  rbx::LongPlan lp;
+  if (rbx::long_plan(bags, n_bags, batch, long_threshold, &lp) != RBX_OK) return 0;
+  return rbx::max_workspace_bytes(lp);
+}
+
+extern "C" int rbx_embed_csr_fwd_max(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, int64_t long_threshold, float* d_out,
+                                     int64_t out_stride_b, int32_t* d_argpos, int64_t arg_stride_b, void* d_workspace,
+                                     size_t workspace_bytes, int32_t* d_status, void* stream) {
+  return rbx::csr_forward_max(bags, n_bags, batch, long_threshold, d_out, out_stride_b, d_argpos, arg_stride_b, d_workspace,
+                              workspace_bytes, d_status, rbx::as_stream(stream));
+}
+
+extern "C" int rbx_embed_csr_bwd_max(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, const float* d_dout,
+                                     int64_t out_stride_b, const int32_t* d_argpos, int64_t arg_stride_b, int32_t accumulate,
+                                     void* d_workspace, size_t workspace_bytes, void* stream) {
+  using namespace rbx;
+  if (d_dout == nullptr) return fail(RBX_ERR_INVALID, "d_dout is NULL");
+  if (d_argpos == nullptr) return fail(RBX_ERR_INVALID, "d_argpos is NULL");
+  CsrPlan c;
+  int rc = csr_plan(bags, n_bags, batch, d_dout, out_stride_b, &c);
+  if (rc != RBX_OK) return rc;
+  rc = check_all_max(bags, n_bags, "rbx_embed_csr_bwd_max");
+  if (rc != RBX_OK) return rc;
+  const BwdPlan& p = c.p;
+  if (p.n_lookups == 0 || batch == 0) return RBX_OK;
+  if (d_workspace == nullptr || workspace_bytes < c.bytes)
+    return fail(RBX_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, c.bytes);
+  char* ws = static_cast<char*>(d_workspace);
+  MaxBagPolicy::Args args = {};
+  args.dout = d_dout;
+  args.stride_b = out_stride_b;
+  args.argpos = d_argpos;
+  args.arg_stride = arg_stride_b;
+  args.map = reinterpret_cast<const int*>(ws + c.off_map);
+  args.accumulate = accumulate;
+  for (int k = 0; k < p.n_cat; ++k) args.lk_off[p.red.f[k].slot] = p.keys.f[k].lk_off;   // by the descriptor's index in `bags`
+  const int cur = p.passes & 1;
+  const unsigned* keys = reinterpret_cast<const unsigned*>(ws + p.off_keys[cur]);
+  const unsigned* vals = reinterpret_cast<const unsigned*>(ws + p.off_vals[cur]);
+  // the float4 form reads argpos in 16-byte vectors as well
+  const bool vec = p.vec && arg_stride_b % 4 == 0 && (reinterpret_cast<uintptr_t>(d_argpos) & 15) == 0;
+  if (!vec && pow2_ceil(p.max_dim) > 256)
+    return fail(RBX_ERR_UNSUPPORTED, "embedding dim %d too large for one lane group (scalar units: d_argpos is not 16-byte aligned "
+                "or arg_stride_b no multiple of 4)", p.max_dim);
+  return vec ? dispatch_reduce<MaxBagPolicy, true>(p, args, keys, vals, ws, as_stream(stream))
+             : dispatch_reduce<MaxBagPolicy, false>(p, args, keys, vals, ws, as_stream(stream));
 }

@@ -29,6 +29,12 @@ struct Acc<true> {
     v.x += __shfl_xor(v.x, o, 64); v.y += __shfl_xor(v.y, o, 64);
     v.z += __shfl_xor(v.z, o, 64); v.w += __shfl_xor(v.w, o, 64);
   }
+  __device__ __forceinline__ float& at(int k) { return k == 0 ? v.x : (k == 1 ? v.y : (k == 2 ? v.z : v.w)); }
+  __device__ __forceinline__ Acc xor_get(int o) const {
+    Acc r;
+    r.v = make_float4(__shfl_xor(v.x, o, 64), __shfl_xor(v.y, o, 64), __shfl_xor(v.z, o, 64), __shfl_xor(v.w, o, 64));
+    return r;
+  }
 };
 template <>
 struct Acc<false> {
@@ -40,6 +46,12 @@ struct Acc<false> {
   __device__ __forceinline__ void load(const float* p) { v = *p; }
   __device__ __forceinline__ void store(float* p) const { *p = v; }
   __device__ __forceinline__ void xor_add(int o) { v += __shfl_xor(v, o, 64); }
+  __device__ __forceinline__ float& at(int) { return v; }
+  __device__ __forceinline__ Acc xor_get(int o) const {
+    Acc r;
+    r.v = __shfl_xor(v, o, 64);
+    return r;
+  }
 };
 
 // One lane's share of a row: NV units, unit u covers elements [(lane_g + u*G)*W, +W).
@@ -82,6 +94,16 @@ struct RowFrag {
   __device__ __forceinline__ void xor_add(int o) {
 #pragma unroll
     for (int u = 0; u < NV; ++u) a[u].xor_add(o);
+  }
+  // For an op that selects instead of adding (the max pool): the share element by element, q = u * W + k, and the share
+  // of lane ^ o.  With q a constant of an unrolled loop `at` is a register name.
+  static constexpr int kElems = NV * W;
+  __device__ __forceinline__ float& at(int q) { return a[q / W].at(q % W); }
+  __device__ __forceinline__ RowFrag xor_get(int o) const {
+    RowFrag r;
+#pragma unroll
+    for (int u = 0; u < NV; ++u) r.a[u] = a[u].xor_get(o);
+    return r;
   }
 };
 

@@ -33,6 +33,22 @@ constexpr int kFinList = 3;      // fin[0] work-list length, fin[1] long-list le
 // tail summary and a flag, and the chunk where such a run ENDS is queued for the fix-up.
 // waves per SIMD the register budget is sized for: at 4 (128 VGPRs) the FM policy spilled 28 bytes per lane to scratch
 #define RBX_REDUCE_WAVES 3
+// Lookups in flight per lane group for rows of more than 32 floats: 4 (see U below).  A policy whose fetch holds more than
+// the row itself specialises this to take fewer where a lane's share (`per_lane` floats) would otherwise spill.
+template <class Policy>
+struct ReduceWideBatch {
+  static constexpr int of(int) { return 4; }
+};
+// The zero-tail test below reads `zero` of the group's other lanes behind a short-circuit: a lane whose own share is not
+// zero does not take part in the exchange, and what a lane that does take part reads from it is not defined.  That is
+// harmless while a contribution is zero in every lane of its group or in none (a zero weight, a zero gradient row).  A
+// policy that zeroes single ELEMENTS of a contribution (the max pool's mask) has lanes that disagree, and lane 0 -- which
+// writes the flag -- then marked tails zero that held the other lanes' sums: it specialises this to true and every lane
+// joins the exchange.
+template <class Policy>
+struct ReduceLaneZeros {
+  static constexpr bool value = false;
+};
 template <class Policy, int G, int NV, bool VEC>
 __global__ __launch_bounds__(256, RBX_REDUCE_WAVES) void segment_reduce_kernel(const RedPack P, const int n_cat,
                                                              const typename Policy::Args args,
@@ -71,7 +87,7 @@ __global__ __launch_bounds__(256, RBX_REDUCE_WAVES) void segment_reduce_kernel(c
 #define RBX_REDUCE_U 8
   // lookups in flight per lane group: 8 for rows of up to 32 floats (the FM tables; 16 measured slower), 4 for wider rows
   // (D = 64 / 128: cfg 4 5.32 -> 5.29 ms, cfg 3 1.93 -> 1.82 ms with 4 instead of 8; with 16 cfg 3 took 2.87 ms)
-  constexpr int U = (G * NV * F::W <= 32) ? RBX_REDUCE_U : 4;
+  constexpr int U = (G * NV * F::W <= 32) ? RBX_REDUCE_U : ReduceWideBatch<Policy>::of(NV * F::W);
   for (unsigned i0 = s; i0 < e; i0 += U) {
     unsigned kk[U + 1], vv[U];
     {
@@ -188,7 +204,14 @@ __global__ __launch_bounds__(256, RBX_REDUCE_WAVES) void segment_reduce_kernel(c
 #pragma unroll
       for (int q = 0; q < static_cast<int>(sizeof(acc.a) / sizeof(float)); ++q) zero = zero && (acc.a[q] == 0.f);
 #pragma unroll
-      for (int o = 1; o < G; o <<= 1) zero = zero && (__shfl_xor(static_cast<int>(zero), o, 64) != 0);
+      for (int o = 1; o < G; o <<= 1) {
+        if constexpr (ReduceLaneZeros<Policy>::value) {
+          const int other = __shfl_xor(static_cast<int>(zero), o, 64);
+          zero = zero && (other != 0);
+        } else {
+          zero = zero && (__shfl_xor(static_cast<int>(zero), o, 64) != 0);
+        }
+      }
       if (zero) flag |= kFlagZero;
     } else if (is_head) {
       float* dst = head + static_cast<size_t>(c) * sum_stride;
