@@ -604,7 +604,10 @@ int rbx_pairdot_bwd(const float* d_u, const float* d_v, const float* d_dout, int
  * the backward then takes that y as d_y_relu (mask y > 0) -- NULL when no activation was fused.
  * Backward: d_dgamma = sum dy * xhat, d_dbeta = sum dy (always written, also used as scratch),
  * d_dx = gamma * rstd * (dy - dbeta/M - xhat * dgamma/M) (training) or gamma * rstd * dy (eval); NULL skips it.
- * Reductions are two-stage in a fixed order (Welford partials merged with Chan's formula): deterministic. */
+ * Reductions are two-stage in a fixed order (Welford partials merged with Chan's formula): deterministic.
+ * Alignment: none is required of any pointer beyond that of a float.  The element-wise passes take their float4 form
+ * when cols % 4 == 0 and x, y (forward) or x, dy, dx and d_y_relu (backward) are all 16-byte aligned, the scalar form
+ * otherwise; the results are the same. */
 size_t rbx_batchnorm_workspace_size(int64_t rows, int32_t cols);
 int rbx_batchnorm_fwd(const float* d_x, int64_t rows, int32_t cols, const float* d_gamma, const float* d_beta, float eps,
                       int32_t training, float momentum, float* d_running_mean, float* d_running_var, int32_t relu,

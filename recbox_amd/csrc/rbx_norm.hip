@@ -489,8 +489,10 @@ static unsigned bn_grid(long long total_vecs, int cols, int w) {
 }
 
 static int bn_blocks(int64_t rows) { return static_cast<int>((rows + bn_rows(rows) - 1) / bn_rows(rows)); }
-static bool bn_vec(int cols, const void* a, const void* b, const void* c) {
-  return cols % 4 == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
+// the float4 forms: cols % 4 == 0 and EVERY tensor they read or write four at a time 16-byte aligned (NULL counts as aligned)
+static bool bn_vec(int cols, const void* a, const void* b, const void* c, const void* d = nullptr) {
+  return cols % 4 == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
+                            reinterpret_cast<uintptr_t>(d)) & 15) == 0;
 }
 
 }  // namespace rbx
@@ -581,7 +583,8 @@ static int bn_bwd_dx(const float* d_x, const float* d_dy, const float* d_y_relu,
                      const float* d_gamma, const float* d_mean, const float* d_rstd, const float* d_dgamma,
                      const float* d_dbeta, int32_t training, int64_t total_rows, float* d_dx, hipStream_t s,
                      const BnPrelu pr = {nullptr, 0, nullptr, nullptr}) {
-  const bool vec = bn_vec(cols, d_x, d_dy, d_dx);
+  // the float4 form reads d_y_relu (the fused ReLU's mask) four at a time too: the fourth operand of the alignment test
+  const bool vec = bn_vec(cols, d_x, d_dy, d_dx, d_y_relu);
   const long long total = static_cast<long long>(rows) * cols / (vec ? 4 : 1);
   const unsigned blocks = bn_grid(total, cols, vec ? 4 : 1);
   const float inv_m = 1.0f / static_cast<float>(total_rows);
