@@ -769,6 +769,23 @@ int rbx_penalize_members(const int64_t* d_candidates, int64_t rows, int32_t k, c
 int rbx_membership(const int64_t* d_candidates, int64_t rows, int32_t k, const int64_t* d_query,
                    const int64_t* d_offsets, const int64_t* d_items, uint8_t* d_flags, void* stream);
 
+/* rbx_search_ip: IndexFlatIP.search as one fused op -- for every user row the k (<= 1024) items with the largest
+ * inner product d_users[r, :] . d_items[i, :] (fp32 products and accumulation on the fp32 MFMA, 1 <= dim <= 512),
+ * without writing the [rows, n_items] score matrix: the scores of 8 192 strided sample items give a per-row
+ * threshold, ONE sweep of the score kernel over all items keeps (in its epilogue, from the accumulator registers)
+ * the (score, item) pairs at or above it, and rbx_topk's exact selection runs among those <= 8 192 candidates.
+ * d_users: row r at d_users + r * user_stride (>= dim); d_items: [n_items, dim] contiguous; neither needs 16-byte
+ * alignment.  d_row_state[r] = 1: row r of the outputs is final -- the k largest scores sorted by (score descending,
+ * item index ascending), the order of rbx_topk.  d_row_state[r] = 0: the row was not served (fewer than k candidates,
+ * or an overflow from ties / a skewed sample) and its outputs are unspecified: the caller computes it through
+ * rbx_linear_fwd + rbx_topk.  Nothing synchronises the device; everything runs on `stream`.
+ * Unsupported (rbx_search_ip_workspace_size returns 0, rbx_search_ip returns RBX_ERR_UNSUPPORTED): n_items <= 16 384
+ * or k not selective (rbx_topk's sample-rank rule), k > 1024, n_items >= 2^31, dim outside [1, 512]. */
+size_t rbx_search_ip_workspace_size(int64_t rows, int64_t n_items, int32_t dim, int32_t k);
+int rbx_search_ip(const float* d_users, int64_t rows, int64_t user_stride, const float* d_items, int64_t n_items,
+                  int32_t dim, int32_t k, float* d_out_scores, int64_t* d_out_index, int32_t* d_row_state,
+                  void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* ---- cross layers (ranking/pytorch/layers/interactions/cross_net.py:22-59).
  * out = xi + x0 * h + bias:  CrossNetV2: h = Linear_i(xi) [rows, dim] (h_cols == dim, bias NULL);
  * CrossNet: h = xi w_i [rows, 1] (h_cols == 1) and bias[dim].  The Linear itself is rbx_linear_fwd.

@@ -7,6 +7,8 @@ time in Python; here
 
   scores = U I^T          rbx_linear_fwd (fp32 MFMA GEMM, a chunk of users x all items)
   top 500 per user        rbx_topk
+                          (catalogues too large to score 1000 users at once: both as ONE op, rbx_search_ip, which
+                          never writes the score matrix -- see evaluate_metrics)
   scores += -1e9 * mask   rbx_penalize_members (items the user clicked in the training data)
   argsort(-scores)[:k]    rbx_topk on the 500 survivors
   item in true_items      rbx_membership
@@ -122,12 +124,16 @@ def build_csr(user2items, n_queries, device):
             torch.from_numpy(lens).to(device).double())
 
 
-def evaluate_block(user_embs, item_embs, query_indices, train_csr, valid_csr, metric_funcs, max_topk):
+def evaluate_block(user_embs, item_embs, query_indices, train_csr, valid_csr, metric_funcs, max_topk, fused=False):
     """Device form of metrics.py:54-68 for one chunk of users: returns (results [users, n_metrics] float64,
-    topk_items [users, max_topk] int64)."""
-    scores = ops.linear(user_embs, item_embs)                        # [users, n_items] = U I^T
+    topk_items [users, max_topk] int64).  ``fused``: the search (scores -> top 500) runs as ops.search_ip, without the
+    [users, n_items] score matrix."""
     k_search = min(_SEARCH_TOPK, item_embs.shape[0])
-    vals, idx = ops.topk(scores, k_search)
+    if fused:
+        vals, idx = ops.search_ip(user_embs, item_embs, k_search)
+    else:
+        scores = ops.linear(user_embs, item_embs)                    # [users, n_items] = U I^T
+        vals, idx = ops.topk(scores, k_search)
     ops.penalize_members_(vals, idx, query_indices, train_csr[0], train_csr[1], -1e9)
     k_out = min(max_topk, k_search)
     _, order = ops.topk(vals, k_out)                                 # argsort(-scores)[:, :max_topk]
@@ -143,7 +149,13 @@ def evaluate_block(user_embs, item_embs, query_indices, train_csr, valid_csr, me
 def evaluate_metrics(user_embs, item_embs, train_user2items, valid_user2items, query_indices, metrics, num_workers=1,
                      device="cuda"):
     """Same signature and return value as the reference (dict metric-string -> average over users);
-    ``num_workers`` is accepted and ignored (one GPU does the work of the process pool)."""
+    ``num_workers`` is accepted and ignored (one GPU does the work of the process pool).
+
+    The reference scores 1000 users per block.  While a [1000, n_items] fp32 score matrix fits 2^28 elements
+    (n_items <= 268 435) that is what happens here, through rbx_linear_fwd + rbx_topk.  Above that size the search runs
+    fused (ops.search_ip, blocks of 1000 users): the selected scores are then the exact top-k of fp32 scores that are
+    within dim * 2^-24 * sum_d |u_d v_d| of the float64 scores, but they are not bit-equal to the GEMM's, so items whose
+    scores nearly tie may come in another order than through the matrix path."""
     logging.info("Evaluating metrics for {} users.".format(len(user_embs)))
     metric_funcs = []
     max_topk = 0
@@ -161,9 +173,13 @@ def evaluate_metrics(user_embs, item_embs, train_user2items, valid_user2items, q
     train_csr = build_csr(train_user2items, n_q, dev)
     valid_csr = build_csr(valid_user2items, n_q, dev)
     chunk = max(1, min(1000, (1 << 28) // max(V.shape[0], 1)))       # the reference scores 1000 users per block
+    fused = chunk < 1000                                             # the matrix of 1000 users does not fit: no matrix
+    if fused:
+        chunk = 1000
     parts = []
     for i in range(0, U.shape[0], chunk):
-        res, _ = evaluate_block(U[i:i + chunk], V, q[i:i + chunk], train_csr, valid_csr, metric_funcs, max_topk)
+        res, _ = evaluate_block(U[i:i + chunk], V, q[i:i + chunk], train_csr, valid_csr, metric_funcs, max_topk,
+                                fused=fused)
         parts.append(res)
     average_result = torch.cat(parts, 0).mean(0).tolist() if parts else [float("nan")] * len(metrics)
     return_dict = dict(zip(metrics, average_result))

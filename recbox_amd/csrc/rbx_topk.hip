@@ -17,23 +17,9 @@
 // HBM is read once and the five sweeps run out of LDS.  Longer rows are cut into segments (a single query
 // still fills the chip): every segment keeps its k best and further launches select among the survivors
 // until one segment per row is left.  HBM-bound streaming read + LDS integer work: no MFMA.
-#include "rbx_internal.h"
+#include "rbx_topk.h"
 
 namespace rbx {
-
-constexpr int kTopkMaxK = 1024;
-constexpr int kTopkSeg = 8192;        // scores per workgroup: their keys are staged in LDS once (32 KB)
-
-__device__ __forceinline__ unsigned key_of(float v) {
-  const unsigned u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);          // larger float <=> larger key
-}
-__device__ __forceinline__ unsigned long long pack_winner(unsigned key, long long index) {
-  return (static_cast<unsigned long long>(key) << 32) | static_cast<unsigned>(~static_cast<unsigned>(index));
-}
-__device__ __forceinline__ float value_of(unsigned k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
 
 // One workgroup per (query, segment).  vals: query u at vals + u * row_stride; the segment covers elements
 // [s * seg, min(n, (s+1) * seg)).  idx_in == nullptr: the index of an element is its position in the row; otherwise
@@ -210,7 +196,6 @@ __global__ __launch_bounds__(256) void membership_kernel(const long long* __rest
 // dominant level into ONE streaming sweep that keeps the elements >= threshold: kTopkCand slots per row.  The exact
 // selection then runs on those candidates.  A row whose candidates are fewer than k, or do not fit (ties, a skewed
 // sample), is flagged and served by the exact multi-level path instead -- both paths check the flag on the device.
-constexpr int kTopkCand = kTopkSeg;          // candidate slots per row (one segment of the final selection)
 constexpr int kTopkStage = 512;              // candidates one workgroup can hand over from its 8 192 scores
 
 __global__ __launch_bounds__(256) void topk_filter_kernel(const float* __restrict__ vals, const long long row_stride,
@@ -270,14 +255,25 @@ __global__ __launch_bounds__(256) void topk_state_kernel(const unsigned* __restr
 
 static int topk_nseg(long long n) { return static_cast<int>((n + kTopkSeg - 1) / kTopkSeg); }
 
-// sample rank for the threshold estimate, or 0 when the fast path does not apply (short rows, k not selective)
-static int topk_sample_rank(long long n, int k, long long* m_out, long long* stride_out) {
-  if (n <= 2ll * kTopkSeg) return 0;
-  const long long m = kTopkSeg, stride = n / m;
-  const long long r = (4ll * k * m + n - 1) / n + 8;
-  *m_out = m;
-  *stride_out = stride;
-  return (r < m / 4) ? static_cast<int>(r) : 0;
+void topk_launch_threshold(const float* vals, long long rows, long long row_stride, long long m, long long sample_stride,
+                           int rank, unsigned* thr, hipStream_t s) {
+  hipLaunchKernelGGL(topk_kernel, dim3(static_cast<unsigned>(rows)), dim3(256), 0, s, vals,
+                     static_cast<const long long*>(nullptr), row_stride, m, kTopkSeg, 1, rank, static_cast<float*>(nullptr),
+                     static_cast<long long*>(nullptr), static_cast<const long long*>(nullptr), 0ll, false,
+                     static_cast<const unsigned*>(nullptr), static_cast<const int*>(nullptr), 0, sample_stride, thr);
+}
+
+void topk_launch_state(const unsigned* cnt, const unsigned* fail, long long rows, unsigned need, int* state, hipStream_t s) {
+  hipLaunchKernelGGL(topk_state_kernel, dim3(static_cast<unsigned>((rows + 255) / 256)), dim3(256), 0, s, cnt, fail, rows,
+                     need, state);
+}
+
+void topk_launch_candidates(const float* cval, const long long* cpos, const unsigned* cnt, const int* state, long long rows,
+                            int k, float* out_vals, long long* out_idx, const long long* remap, long long remap_stride,
+                            hipStream_t s) {
+  hipLaunchKernelGGL(topk_kernel, dim3(static_cast<unsigned>(rows)), dim3(256), 0, s, cval, cpos,
+                     static_cast<long long>(kTopkCand), static_cast<long long>(kTopkCand), kTopkSeg, 1, k, out_vals, out_idx,
+                     remap, remap_stride, true, cnt, state, 1, 1ll, static_cast<unsigned*>(nullptr));
 }
 
 static size_t topk_fast_bytes(long long rows) {
@@ -335,22 +331,16 @@ extern "C" int rbx_topk(const float* d_scores, const int64_t* d_index, int64_t r
     if (hipMemsetAsync(cnt, 0, static_cast<size_t>(rows) * 2 * sizeof(unsigned), s) != hipSuccess)
       return fail(RBX_ERR_LAUNCH, "topk: memset of the candidate counters failed");
     // (1) threshold = key of the rank-th largest of m strided samples of the row
-    hipLaunchKernelGGL(topk_kernel, dim3(static_cast<unsigned>(rows)), dim3(256), 0, s, d_scores,
-                       static_cast<const long long*>(nullptr), static_cast<long long>(row_stride), m, kTopkSeg, 1, rank,
-                       static_cast<float*>(nullptr), static_cast<long long*>(nullptr), static_cast<const long long*>(nullptr),
-                       0ll, false, no_len, static_cast<const int*>(nullptr), 0, sstride, thr);
+    topk_launch_threshold(d_scores, rows, static_cast<long long>(row_stride), m, sstride, rank, thr, s);
     // (2) one sweep over the scores keeps what is >= threshold
     hipLaunchKernelGGL(topk_filter_kernel, dim3(static_cast<unsigned>(rows * nseg)), dim3(256), 0, s, d_scores,
                        static_cast<long long>(row_stride), static_cast<long long>(n), kTopkSeg, nseg, thr, cnt, failed, cval,
                        cpos);
     // (3) which rows have what they need
-    hipLaunchKernelGGL(topk_state_kernel, dim3(static_cast<unsigned>((rows + 255) / 256)), dim3(256), 0, s, cnt, failed,
-                       static_cast<long long>(rows), static_cast<unsigned>(k), state);
+    topk_launch_state(cnt, failed, rows, static_cast<unsigned>(k), state, s);
     // (4) exact selection + sort among the candidates of those rows
-    hipLaunchKernelGGL(topk_kernel, dim3(static_cast<unsigned>(rows)), dim3(256), 0, s, cval, cpos,
-                       static_cast<long long>(kTopkCand), static_cast<long long>(kTopkCand), kTopkSeg, 1, k, d_out_scores, oidx,
-                       reinterpret_cast<const long long*>(d_index), static_cast<long long>(row_stride), true, cnt, state, 1, 1ll,
-                       no_thr);
+    topk_launch_candidates(cval, cpos, cnt, state, rows, k, d_out_scores, oidx, reinterpret_cast<const long long*>(d_index),
+                           static_cast<long long>(row_stride), s);
     int rc = check_launch("topk fast path");
     if (rc != RBX_OK) return rc;
   }

@@ -2418,6 +2418,51 @@ def topk(scores, k, index=None):
     return vals, idx
 
 
+# fused_rows / fallback_rows of the last search_ip call (tests, profiling)
+search_ip_stats = {"fused_rows": 0, "fallback_rows": 0}
+_SEARCH_MATRIX_BYTES = 1 << 30          # the matrix path of rows the fused search gave up: score matrix below 1 GB
+
+
+def search_ip(users, items, k):
+    """IndexFlatIP.search: per row of users [rows, dim] the k items [n_items, dim] with the largest inner product ->
+    (values [rows, k] fp32, index [rows, k] int64), layout and tie rule of ``topk(linear(users, items), k)`` (score
+    descending, then item index ascending).  Where rbx_search_ip serves the shape (more than 16 384 items, k <= 1024 and
+    selective, dim <= 512) the score matrix is never written: one fused call, exact top-k of fp32 scores.  Rows it reports
+    as not served (ties or a skewed sample overflowing the candidate slots) are recomputed through the matrix path in
+    sub-blocks; every other shape runs ``topk(linear(users, items), k)`` itself.  Evaluation only: the op reads the
+    per-row state back to the host once, so it cannot be captured into a graph."""
+    _require_cuda(users, "users")
+    _require_cuda(items, "items")
+    if users.dim() != 2 or items.dim() != 2 or users.shape[1] != items.shape[1]:
+        raise ValueError("search_ip: users [rows, dim] and items [n_items, dim]")
+    rows, dim = users.shape
+    n = items.shape[0]
+    ws_bytes = lib.rbx_search_ip_workspace_size(rows, n, dim, k) if rows > 0 else 0
+    if ws_bytes == 0:
+        search_ip_stats.update(fused_rows=0, fallback_rows=rows)
+        return topk(linear(users, items), k)
+    if users.dtype != torch.float32 or users.stride(1) != 1 or (rows > 1 and users.stride(0) < dim):
+        users = users.float().contiguous()
+    if items.dtype != torch.float32 or not items.is_contiguous():
+        items = items.float().contiguous()
+    vals = torch.empty((rows, k), dtype=torch.float32, device=users.device)
+    idx = torch.empty((rows, k), dtype=torch.int64, device=users.device)
+    state = torch.empty(rows, dtype=torch.int32, device=users.device)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=users.device)
+    check(lib.rbx_search_ip(_ptr(users), rows, users.stride(0) if rows > 1 else dim, _ptr(items), n, dim, k, _ptr(vals),
+                            _ptr(idx), _ptr(state), _ptr(ws), ws_bytes, _stream()))
+    del ws
+    todo = torch.nonzero(state == 0).flatten()                      # the one read-back
+    search_ip_stats.update(fused_rows=rows - todo.numel(), fallback_rows=todo.numel())
+    block = max(1, _SEARCH_MATRIX_BYTES // (4 * n + 1))
+    for i in range(0, todo.numel(), block):
+        sel = todo[i:i + block]
+        v, j = topk(linear(users[sel], items), k)
+        vals[sel] = v
+        idx[sel] = j
+    return vals, idx
+
+
 def _csr_args(candidates, query, offsets, items):
     for t in (candidates, query, offsets, items):
         _require_cuda(t, "membership input")
