@@ -1059,6 +1059,38 @@ size_t rbx_seqblock_inproj_dw_workspace_size(int64_t m);
 int rbx_seqblock_inproj_dw(const float* d_dQ, const float* d_dKV, const float* d_x, const float* d_mean, const float* d_rstd,
                            int64_t m, const float* d_ln_w, const float* d_ln_b, float* d_dw, float* d_db, void* d_workspace,
                            size_t workspace_bytes, void* stream);
+
+/* ---- DIN's local activation unit (rbx_din.hip) ---------------------------------------------------------------------------
+ * d_hist [batch, seq_len, dim]: the rows of a sample contiguous, samples hist_stride_b floats apart; d_target [batch, dim]
+ * at a row stride of target_stride_b (a slice of a wider block is read in place).  Everything written is contiguous.
+ *   rbx_din_pairs_fwd   d_y [batch * seq_len, n] = act([t, h, t - h, t o h] W^T + bias), d_w [n, 4 dim] with the four column
+ *                       blocks in that order, act 0 | 1 = ReLU, d_bias may be NULL.  The [batch * seq_len, 4 dim] operand is
+ *                       never stored: it is formed from h and t on the way into the fp32 matrix cores.
+ *   rbx_din_pairs_bwd   with dP = dy' W (dy' = d_dy where d_y > 0 when act = 1; d_y may be NULL when act = 0), never stored:
+ *                       d_dhist [batch, seq_len, dim] = dP_b - dP_c + dP_d o t, d_dtarget [batch, dim] = sum_l (dP_a + dP_c
+ *                       + dP_d o h), d_dw [n, 4 dim] = dy'^T [t, h, t - h, t o h], d_db [n] = column sums of dy'.  Each of
+ *                       the four may be NULL; the workspace is needed for d_dw / d_db.  All sums run in a fixed order.
+ *   rbx_din_pool_fwd    d_weight [batch, seq_len] = score o mask, or with softmax != 0 softmax over seq_len of
+ *                       score o mask + (-1e9)(1 - mask) (a fully masked sample gets 1 / seq_len); d_mask may be NULL (no mask
+ *                       terms).  d_out [batch, dim] = sum_l weight[b, l] h[b, l, :].  d_score, d_mask, d_weight contiguous.
+ *   rbx_din_pool_bwd    d_dscore [batch, seq_len] = (softmax ? w o (dw - sum_l w dw) : dw) o mask with dw[l] = <dout, h_l>;
+ *                       d_dhist [batch, seq_len, dim] = w_l dout.  Either may be NULL.
+ * Supported: dim a multiple of 4 in [4, 128]; 1 <= n <= 64; batch * seq_len <= INT_MAX; the pool calls seq_len <= 4096;
+ * 16-byte aligned bases (d_hist, d_target, d_w, d_dhist), strides multiples of 4.  Anything else: RBX_ERR_UNSUPPORTED before
+ * any launch.  batch = 0 launches nothing.  No call allocates or reads back: all are capturable. */
+int rbx_din_pairs_fwd(const float* d_hist, int64_t hist_stride_b, const float* d_target, int64_t target_stride_b,
+                      int64_t batch, int32_t seq_len, int32_t dim, const float* d_w, const float* d_bias, int32_t n,
+                      int32_t act, float* d_y, void* stream);
+size_t rbx_din_pairs_bwd_workspace_size(int64_t batch, int32_t seq_len, int32_t dim, int32_t n);
+int rbx_din_pairs_bwd(const float* d_hist, int64_t hist_stride_b, const float* d_target, int64_t target_stride_b,
+                      int64_t batch, int32_t seq_len, int32_t dim, const float* d_w, int32_t n, int32_t act,
+                      const float* d_y, const float* d_dy, float* d_dhist, float* d_dtarget, float* d_dw, float* d_db,
+                      void* d_workspace, size_t workspace_bytes, void* stream);
+int rbx_din_pool_fwd(const float* d_score, const float* d_mask, const float* d_hist, int64_t hist_stride_b, int64_t batch,
+                     int32_t seq_len, int32_t dim, int32_t softmax, float* d_weight, float* d_out, void* stream);
+int rbx_din_pool_bwd(const float* d_dout, const float* d_weight, const float* d_mask, const float* d_hist,
+                     int64_t hist_stride_b, int64_t batch, int32_t seq_len, int32_t dim, int32_t softmax, float* d_dscore,
+                     float* d_dhist, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -259,6 +259,12 @@ SIGNATURES = {
     "rbx_pair_logsigmoid_bwd": (ctypes.c_int, [_P, _P, _P, _P, _i64, _f32, _P, _P, _P]),
     "rbx_pool_fwd": (ctypes.c_int, [_P, _P, _i64, _i32, _i32, _i32, _i32, _f32, _P, _P, _P]),
     "rbx_pool_bwd": (ctypes.c_int, [_P, _P, _P, _i64, _i32, _i32, _i32, _P, _P]),
+    "rbx_din_pairs_fwd": (ctypes.c_int, [_P, _i64, _P, _i64, _i64, _i32, _i32, _P, _P, _i32, _i32, _P, _P]),
+    "rbx_din_pairs_bwd_workspace_size": (_sz, [_i64, _i32, _i32, _i32]),
+    "rbx_din_pairs_bwd": (ctypes.c_int, [_P, _i64, _P, _i64, _i64, _i32, _i32, _P, _i32, _i32, _P, _P, _P, _P, _P, _P, _P,
+                                         _sz, _P]),
+    "rbx_din_pool_fwd": (ctypes.c_int, [_P, _P, _P, _i64, _i64, _i32, _i32, _i32, _P, _P, _P]),
+    "rbx_din_pool_bwd": (ctypes.c_int, [_P, _P, _P, _P, _i64, _i64, _i32, _i32, _i32, _P, _P, _P]),
 }
 
 

@@ -90,7 +90,8 @@ _RECHUB = {
     "models.matching.dssm": ("recbox_amd.rechub.models.matching", ["DSSM"]),
     "models.matching.youtube_dnn": ("recbox_amd.rechub.models.matching", ["YoutubeDNN"]),
     "models.matching.sasrec": ("recbox_amd.rechub.models.matching", ["SASRec", "PointWiseFeedForward"]),
-    "models.ranking": ("recbox_amd.rechub.models.ranking", ["DeepFM"]),
+    "models.ranking": ("recbox_amd.rechub.models.ranking", ["DeepFM", "DIN"]),
+    "models.ranking.din": ("recbox_amd.rechub.models.ranking", ["DIN", "ActivationUnit"]),
     "models.ranking.deepfm": ("recbox_amd.rechub.models.ranking", ["DeepFM"]),
 }
 

@@ -5,8 +5,11 @@ ReLU into the GEMM epilogue; nn.BatchNorm1d on 2-D activations runs through
 ``rbx_batchnorm_fwd/bwd`` (a following ReLU or PReLU fused in; nn.SyncBatchNorm modules
 normalise over all ranks).  nn.PReLU standing alone, nn.Dropout in training mode and Dice run
 ``rbx_prelu_*`` / ``rbx_dropout`` / ``rbx_dice_*`` (csrc/rbx_act.hip); Dropout with p = 0 or in
-evaluation launches nothing; Sigmoid / Tanh / Softmax heads are elementwise ATen kernels.
+evaluation launches nothing; Sigmoid / Tanh / Softmax heads are elementwise ATen kernels.  ``run_din_unit`` is DIN's activation
+unit over such a tower: its first Linear and its pooling read the history and the target in place
+(``rbx_din_*``, csrc/rbx_din.hip).
 """
+import torch
 from torch import nn
 
 from . import ops
@@ -107,3 +110,31 @@ def run_sequential(seq, x):
             x = m(x)                              # Dice modules route themselves (ops.dice); Sigmoid / Tanh / ...: ATen
             i += 1
     return x
+
+
+def run_din_unit(seq, history, target, mask=None, softmax=False):
+    """DIN's local activation unit over the attention tower ``seq`` (an nn.Sequential that ends in one score per row):
+    history [B, L, E], target [B, E], mask [B, L] with 0 at masked positions or None -> [B, E].  The tower's first Linear
+    runs as ``ops.din_scores`` (a following ReLU fused), the masked / soft-maxed weighted sum as ``ops.din_pool``; where
+    ``ops.config.din_fused`` is off or the library does not serve the shape, the reference's composition: concatenate
+    [t, h, t - h, t * h], the tower, mask, softmax, weighted sum."""
+    mods = list(seq)
+    seq_len = history.size(1)
+    if mods and type(mods[0]) is nn.Linear and ops.din_scores_supported(history, target, mods[0].weight):
+        fuse = len(mods) > 1 and type(mods[1]) is nn.ReLU
+        x = ops.din_scores(history, target, mods[0].weight, mods[0].bias, "relu" if fuse else None)
+        weight = run_sequential(mods[2 if fuse else 1:], x)
+    else:
+        t = target.unsqueeze(1).expand(-1, seq_len, -1)
+        pairs = torch.cat([t, history, t - history, t * history], dim=-1)
+        weight = run_sequential(mods, pairs.view(-1, pairs.shape[-1]))
+    weight = weight.view(-1, seq_len)
+    if ops.din_pool_supported(history):
+        return ops.din_pool(weight, history, mask, softmax)
+    if mask is not None:
+        weight = weight * mask.float()
+    if softmax:
+        if mask is not None:
+            weight = weight + -1.e9 * (1 - mask.float())
+        weight = weight.softmax(dim=-1)
+    return (weight.unsqueeze(-1) * history).sum(dim=1)

@@ -103,6 +103,15 @@ class config(object):
     # SASRec's position rows read in place and their gradient as a column sum over the batch (sasrec_input) instead of a
     # lookup of tile(arange(L)) with the generic sort + segmented reduce behind it
     seq_positions_in_place = True
+    # DIN's activation unit (DIN_Attention, rechub's ActivationUnit): the first Linear over [t, h, t - h, t * h] and the masked
+    # / soft-maxed pooling as two ops that read h and t (din_scores, din_pool: csrc/rbx_din.hip) instead of a [B, L, 4E]
+    # concatenation, a GEMM over it and six element-wise kernels.  Off, or for a shape the library refuses: that composition.
+    din_fused = os.environ.get("RECBOX_AMD_DIN_FUSED", "1") != "0"
+    # ... from this embedding width up.  Measured at B = 4096, forward + backward (profiles/din/INDEX.md): E = 32, 64, 128 win
+    # (1.13 x, 1.19 x, 1.38 x with units [64, 32], L = 50; 1.49 x with 16 units, 1.51 x at L = 10, E = 64), rechub's E = 16
+    # with dims [36] loses (0.95 x): the concatenation there is small and the composition's GEMM cheap.  Widths 20 to 28
+    # were not measured and stay on the composition.  The ops themselves (din_scores, din_pool) serve every supported width.
+    din_min_dim = int(os.environ.get("RECBOX_AMD_DIN_MIN_DIM", "32"))
 
 
 def _require_cuda(t, what):
@@ -4056,3 +4065,137 @@ def pair_logsigmoid_loss(pos, neg, weight=None, scale=1.0):
     """``scale * sum(-weight * (logsigmoid(pos) + logsigmoid(-neg)))``: the pos / neg objective over SASRec's [B, L] logit
     blocks (weight = 1 on real positions, 0 on padding; scale = 1 / number of real positions for the mean)."""
     return _PairLogSigmoid.apply(pos, neg, weight, scale)
+
+
+# ---- DIN's local activation unit (csrc/rbx_din.hip) ----------------------------------------------------------------------
+DIN_MAX_UNITS, DIN_MAX_DIM, DIN_MAX_POOL_LEN = 64, 128, 4096
+
+
+def _din_rows(history):
+    """history [B, L, E] as the kernels read it: float32, a sample's rows contiguous (the sample stride is free)."""
+    L, E = history.shape[1], history.shape[2]
+    if history.dtype != torch.float32 or history.stride(2) != 1 or (L > 1 and history.stride(1) != E):
+        history = history.float().contiguous()
+    return history
+
+
+def _din_row_stride(t, inner):
+    return t.stride(0) if t.shape[0] > 1 else inner
+
+
+def _din_layout_ok(history, target=None):
+    """What rbx_din_* serve: E a multiple of 4 in [4, 128], 16-byte aligned bases, sample strides that are multiples of 4."""
+    if history.dim() != 3 or not history.is_cuda:
+        return False
+    B, L, E = history.shape
+    if E % 4 != 0 or not 4 <= E <= DIN_MAX_DIM or L < 1 or B * L >= 2 ** 31:
+        return False
+    for t, inner in ((history, L * E), (target, E)):
+        if t is None:
+            continue
+        rows_ok = t.dtype == torch.float32 and t.stride(-1) == 1 and (t.dim() == 2 or L == 1 or t.stride(1) == E)
+        if rows_ok and (t.data_ptr() % 16 != 0 or _din_row_stride(t, inner) % 4 != 0):
+            return False                           # a view the kernels cannot read in place (a copy would be aligned)
+    return True
+
+
+def din_scores_supported(history, target, weight):
+    """Whether the layers take this activation unit's first Linear through din_scores: the switch, the measured width
+    class, and what the library serves."""
+    return (config.din_fused and _din_layout_ok(history, target) and history.shape[2] >= config.din_min_dim
+            and target.dim() == 2 and weight.dim() == 2 and weight.dtype == torch.float32
+            and 1 <= weight.shape[0] <= DIN_MAX_UNITS
+            and weight.shape[1] == 4 * history.shape[2])
+
+
+def din_pool_supported(history):
+    return (config.din_fused and _din_layout_ok(history) and history.shape[2] >= config.din_min_dim
+            and history.shape[1] <= DIN_MAX_POOL_LEN)
+
+
+class _DinScores(torch.autograd.Function):
+    """y [B L, n] = act([t, h, t - h, t * h] W^T + b) via rbx_din_pairs_fwd / _bwd: the [B L, 4E] operand and its gradient
+    exist in neither pass.  act in {None, "relu"}."""
+
+    @staticmethod
+    def forward(ctx, history, target, weight, bias, act):
+        for t, what in ((history, "din history"), (target, "din target"), (weight, "din weight")):
+            _require_cuda(t, what)
+        h = _din_rows(history)
+        t = target if (target.dtype == torch.float32 and target.stride(1) == 1) else target.float().contiguous()
+        w = weight.float().contiguous()
+        bias = bias.float().contiguous() if bias is not None else None
+        B, L, E = h.shape
+        n = w.shape[0]
+        if t.shape != (B, E) or w.shape[1] != 4 * E or (bias is not None and bias.shape != (n,)):
+            raise RuntimeError("din_scores: history %s, target %s, weight %s do not fit"
+                               % (tuple(h.shape), tuple(t.shape), tuple(w.shape)))
+        y = torch.empty((B * L, n), dtype=torch.float32, device=h.device)
+        check(lib.rbx_din_pairs_fwd(_ptr(h), _din_row_stride(h, L * E), _ptr(t), _din_row_stride(t, E), B, L, E, _ptr(w),
+                                    _ptr(bias), n, act, _ptr(y), _stream()))
+        ctx.save_for_backward(h, t, w, y if act == 1 else None)      # (y only gates the ReLU's gradient)
+        ctx.act, ctx.has_bias = act, bias is not None
+        ctx.grad_keys = (weight.data_ptr() if weight.is_contiguous() else 0, bias.data_ptr() if bias is not None else 0)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        h, t, w, y = ctx.saved_tensors
+        B, L, E = h.shape
+        n = w.shape[0]
+        dev = dy.device
+        dy2 = dy.reshape(B * L, n).contiguous().float()
+        need = ctx.needs_input_grad
+        dh = torch.empty((B, L, E), dtype=torch.float32, device=dev) if need[0] else None
+        dt = torch.empty((B, E), dtype=torch.float32, device=dev) if need[1] else None
+        dw = _grad_dest(ctx.grad_keys[0], w.shape, dev) if need[2] else None
+        db = _grad_dest(ctx.grad_keys[1], (n,), dev) if (ctx.has_bias and need[3]) else None
+        ws_bytes = lib.rbx_din_pairs_bwd_workspace_size(B, L, E, n) if (dw is not None or db is not None) else 0
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+        check(lib.rbx_din_pairs_bwd(_ptr(h), _din_row_stride(h, L * E), _ptr(t), _din_row_stride(t, E), B, L, E, _ptr(w), n,
+                                    ctx.act, _ptr(y), _ptr(dy2), _ptr(dh), _ptr(dt), _ptr(dw), _ptr(db), _ptr(ws), ws_bytes,
+                                    _stream()))
+        return dh, dt, dw, db, None
+
+
+def din_scores(history, target, weight, bias=None, act=None):
+    """The first Linear of DIN's activation unit over [target, history, target - history, target * history], without that
+    tensor: history [B, L, E], target [B, E], weight [n, 4E] -> [B L, n]."""
+    return _DinScores.apply(history, target, weight, bias, 1 if act == "relu" else 0)
+
+
+class _DinPool(torch.autograd.Function):
+    """out [B, E] = sum_l w[b, l] h[b, l, :], w = score * mask or softmax(score * mask - 1e9 (1 - mask)): rbx_din_pool_*."""
+
+    @staticmethod
+    def forward(ctx, score, history, mask, softmax):
+        _require_cuda(score, "din score")
+        _require_cuda(history, "din history")
+        h = _din_rows(history)
+        B, L, E = h.shape
+        s = score.reshape(B, L).contiguous().float()
+        m = mask.reshape(B, L).contiguous().float() if mask is not None else None
+        weight = torch.empty((B, L), dtype=torch.float32, device=h.device)
+        out = torch.empty((B, E), dtype=torch.float32, device=h.device)
+        check(lib.rbx_din_pool_fwd(_ptr(s), _ptr(m), _ptr(h), _din_row_stride(h, L * E), B, L, E, int(bool(softmax)),
+                                   _ptr(weight), _ptr(out), _stream()))
+        ctx.save_for_backward(weight, m, h)
+        ctx.softmax, ctx.score_shape = int(bool(softmax)), score.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        weight, m, h = ctx.saved_tensors
+        B, L, E = h.shape
+        do = dout.contiguous().float()
+        ds = torch.empty((B, L), dtype=torch.float32, device=do.device) if ctx.needs_input_grad[0] else None
+        dh = torch.empty((B, L, E), dtype=torch.float32, device=do.device) if ctx.needs_input_grad[1] else None
+        check(lib.rbx_din_pool_bwd(_ptr(do), _ptr(weight), _ptr(m), _ptr(h), _din_row_stride(h, L * E), B, L, E, ctx.softmax,
+                                   _ptr(ds), _ptr(dh), _stream()))
+        return (ds.view(ctx.score_shape) if ds is not None else None), dh, None, None
+
+
+def din_pool(score, history, mask=None, softmax=False):
+    """The tail of DIN's activation unit: score [B, L] (or [B L, 1]), history [B, L, E], mask [B, L] with 0 at masked
+    positions -> [B, E]."""
+    return _DinPool.apply(score, history, mask, softmax)

@@ -121,8 +121,9 @@ class SqueezeExcitation(nn.Module):
 
 class DIN_Attention(nn.Module):
     """DIN's local activation unit (target_attention.py:25-66): an MLP over [target, history, target - history,
-    target * history] scores every position of the behaviour sequence (``attention_layer`` = MLP_Block, i.e. the
-    [B L, 4E] x [4E, units] products on the fp32 matrix cores); masked, optionally soft-maxed, weighted sum."""
+    target * history] scores every position of the behaviour sequence (``attention_layer`` = MLP_Block); masked, optionally
+    soft-maxed, weighted sum.  The first Linear forms the four blocks from the history and the target inside its kernel
+    (``ops.din_scores``) and the tail is one pass over the history (``ops.din_pool``): dense.run_din_unit."""
 
     def __init__(self, embedding_dim=64, attention_units=[32], hidden_activations="ReLU", output_activation=None,
                  dropout_rate=0, batch_norm=False, use_softmax=False):
@@ -137,14 +138,4 @@ class DIN_Attention(nn.Module):
                                          dropout_rates=dropout_rate, batch_norm=batch_norm)
 
     def forward(self, target_item, history_sequence, mask=None):
-        seq_len = history_sequence.size(1)
-        target = target_item.unsqueeze(1).expand(-1, seq_len, -1)
-        pairs = torch.cat([target, history_sequence, target - history_sequence, target * history_sequence], dim=-1)
-        weight = self.attention_layer(pairs.view(-1, 4 * self.embedding_dim)).view(-1, seq_len)
-        if mask is not None:
-            weight = weight * mask.float()
-        if self.use_softmax:
-            if mask is not None:
-                weight = weight + -1.e9 * (1 - mask.float())
-            weight = weight.softmax(dim=-1)
-        return (weight.unsqueeze(-1) * history_sequence).sum(dim=1)
+        return dense.run_din_unit(self.attention_layer.mlp, history_sequence, target_item, mask, self.use_softmax)

@@ -1,5 +1,6 @@
 """DeepFM (drop-in for ``torch_rechub.models.ranking.DeepFM``,
-/root/reference/recbox/third_party/rechub/models/ranking/deepfm.py:14-42)."""
+/root/reference/recbox/third_party/rechub/models/ranking/deepfm.py:14-42) and DIN with its ActivationUnit
+(``torch_rechub.models.ranking.din``, rechub/models/ranking/din.py:16-91)."""
 import torch
 
 from ... import dense, ops
@@ -56,3 +57,44 @@ class DeepFM(torch.nn.Module):
         y_deep = self.mlp(input_deep)
         y = y_linear + y_fm + y_deep
         return ops.sigmoid_output(y.squeeze(1))
+
+
+class ActivationUnit(torch.nn.Module):
+    """DIN's target attention over one behaviour sequence: ``attention`` (an MLP over [target, history, target - history,
+    target * history], one score per position), optional softmax over the positions (no mask in rechub), weighted sum of
+    the history.  history [B, L, E], target [B, E] -> [B, E]; both may be slices of wider blocks (read in place)."""
+
+    def __init__(self, emb_dim, dims=None, activation="dice", use_softmax=False):
+        super(ActivationUnit, self).__init__()
+        self.emb_dim = emb_dim
+        self.use_softmax = use_softmax
+        self.attention = MLP(4 * emb_dim, dims=[36] if dims is None else dims, activation=activation)
+
+    def forward(self, history, target):
+        return dense.run_din_unit(self.attention.mlp, history, target, None, self.use_softmax)
+
+
+class DIN(torch.nn.Module):
+    """Deep Interest Network: every history feature is pooled by its own ActivationUnit against the target feature of the
+    same position; [pooled histories | targets | profile features] feed a Dice MLP.  ``attention_mlp_params`` are the
+    ActivationUnit's keyword arguments, ``mlp_params`` the final MLP's (its activation is always "dice")."""
+
+    def __init__(self, features, history_features, target_features, mlp_params, attention_mlp_params):
+        super(DIN, self).__init__()
+        self.features = features
+        self.history_features = history_features
+        self.target_features = target_features
+        self.num_history_features = len(history_features)
+        self.all_dims = sum(f.embed_dim for f in features + history_features + target_features)
+        self.embedding = EmbeddingLayer(features + history_features + target_features)
+        self.attention_layers = torch.nn.ModuleList(ActivationUnit(f.embed_dim, **attention_mlp_params)
+                                                    for f in history_features)
+        self.mlp = MLP(self.all_dims, activation="dice", **mlp_params)
+
+    def forward(self, x):
+        profile = self.embedding(x, self.features)              # [B, n_features, E]
+        history = self.embedding(x, self.history_features)      # [B, n_history, L, E]
+        target = self.embedding(x, self.target_features)        # [B, n_target, E]
+        pooled = [unit(history[:, i], target[:, i]) for i, unit in enumerate(self.attention_layers)]
+        mlp_in = torch.cat(pooled + [target.flatten(start_dim=1), profile.flatten(start_dim=1)], dim=1)
+        return torch.sigmoid(self.mlp(mlp_in).squeeze(1))

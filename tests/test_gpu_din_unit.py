@@ -1,0 +1,462 @@
+"""DIN's local activation unit on the HIP path (csrc/rbx_din.hip: ops.din_scores, ops.din_pool, DIN_Attention, rechub's
+ActivationUnit / DIN) against the reference's composition (ranking/pytorch/layers/attentions/target_attention.py:48-66,
+third_party/rechub/models/ranking/din.py:39-91) restated in torch float64 on the CPU.  Every float64 comparison also runs
+the float32 composition this op replaces (``din_fused`` off) through the same assert, so an input for which fp32 itself
+misses the bar shows up as that, not as a kernel fault."""
+import os
+
+import pytest
+import torch
+from torch import nn
+
+from conftest import GOLDEN, assert_close
+
+pytestmark = pytest.mark.gpu
+TOL = 1e-4
+B = 37
+
+
+@pytest.fixture(autouse=True)
+def every_supported_width_takes_the_fused_path():
+    """The layers route embedding widths below ops.config.din_min_dim (where the composition measured faster) to the
+    composition; these tests are about the kernels, at the small widths where their tiling can go wrong."""
+    from recbox_amd import ops
+    old = ops.config.din_min_dim
+    ops.config.din_min_dim = 4
+    yield
+    ops.config.din_min_dim = old
+
+
+def test_default_routing_follows_the_measurement():
+    """Widths from 32 up measured faster fused, 16 slower: the layers' gates say so at the shipped threshold."""
+    from recbox_amd import ops
+    ops.config.din_min_dim = 32                              # the shipped default (the fixture restores its own value)
+
+    def gates(E):
+        h, t, w = torch.randn(4, 5, E).cuda(), torch.randn(4, E).cuda(), torch.randn(8, 4 * E).cuda()
+        return ops.din_scores_supported(h, t, w), ops.din_pool_supported(h)
+
+    assert gates(32) == (True, True) and gates(64) == (True, True) and gates(128) == (True, True)
+    assert gates(16) == (False, False) and gates(28) == (False, False)
+    assert not ops.din_scores_supported(torch.randn(4, 5, 64).cuda(), torch.randn(4, 64).cuda(), torch.randn(8, 256).cuda().half())
+    ops.config.din_fused = False
+    try:
+        assert gates(64) == (False, False)
+    finally:
+        ops.config.din_fused = True
+
+
+def _ref_pairs(h, t, w, b, act):
+    tt = t.unsqueeze(1).expand(-1, h.shape[1], -1)
+    pairs = torch.cat([tt, h, tt - h, tt * h], dim=-1)
+    y = pairs.reshape(-1, pairs.shape[-1]) @ w.t()
+    if b is not None:
+        y = y + b
+    return torch.relu(y) if act else y
+
+
+def _parent_pairs(h, t, w, b, act):
+    """The float32 composition of the parent: concatenate in HBM, then the project's GEMM."""
+    from recbox_amd import ops
+    tt = t.unsqueeze(1).expand(-1, h.shape[1], -1)
+    pairs = torch.cat([tt, h, tt - h, tt * h], dim=-1)
+    return ops.linear(pairs.view(-1, pairs.shape[-1]), w, b, "relu" if act else None)
+
+
+def _pairs_inputs(E, L, n, bias, seed, batch=B):
+    g = torch.Generator().manual_seed(seed)
+    h = torch.randn(batch, L, E, generator=g, dtype=torch.float64)
+    t = torch.randn(batch, E, generator=g, dtype=torch.float64)
+    w = torch.randn(n, 4 * E, generator=g, dtype=torch.float64) * 0.3
+    b = torch.randn(n, generator=g, dtype=torch.float64) * 0.3 if bias else None
+    # The upstream gradient at std 1 / sqrt(L).  dW and db are sums over B L rows, dt over L n terms: with a unit
+    # gradient they grow to several hundred at 1850 rows, and fp32 itself -- the composition this op replaces, run through
+    # the same asserts below -- is then 2e-4 away from float64 in absolute terms (rounding ~ 6e-8 x the sum of the terms'
+    # magnitudes).  At 1 / sqrt(L) the sums stay at O(sqrt(B n)) whatever L is and the absolute bar holds for fp32.
+    r = torch.randn(batch * L, n, generator=g, dtype=torch.float64) / L ** 0.5
+    return h, t, w, b, r
+
+
+def _run(fn, tensors, act, r, device):
+    leaves = [None if x is None else (x.float().to(device) if device != "cpu" else x.clone()).requires_grad_() for x in tensors]
+    y = fn(*leaves, act)
+    (y * (r.float().to(device) if device != "cpu" else r)).sum().backward()
+    return [y.detach()] + [None if x is None else x.grad for x in leaves]
+
+
+# E, L, n, act, bias: every E / L / n of the issue once, both act values, with and without bias; L = 5 (tiles straddle
+# samples), L = 65 (a sample straddles tiles); M = 37 * 50 = 1850 > the 1024 rows of one dW split; what the tiling makes
+# special: E that is no multiple of the 16 / 32 column slices (12, 20), L = 128 / 129 / 130 (the dx kernel's one-sample
+# chunks), n = 32 / 33 (one or two 32-column accumulators), n odd (the k loop of dx runs in pairs)
+PAIR_CASES = [(4, 1, 1, 0, False), (8, 5, 12, 1, True), (16, 50, 36, 0, True), (64, 65, 64, 1, True), (128, 5, 64, 0, False),
+              (64, 50, 36, 1, True), (16, 65, 12, 1, False), (128, 50, 33, 1, True), (12, 7, 5, 1, True),
+              (32, 128, 32, 0, True), (20, 129, 64, 1, True), (64, 130, 12, 0, True), (128, 1, 1, 1, True)]
+
+
+@pytest.mark.parametrize("E,L,n,act,bias", PAIR_CASES)
+def test_pairs_forward_and_backward_match_float64(E, L, n, act, bias):
+    from recbox_amd import ops
+    h, t, w, b, r = _pairs_inputs(E, L, n, bias, 1000 * E + 10 * L + n)
+    want = _run(_ref_pairs, (h, t, w, b), act, r, "cpu")
+    assert ops.din_scores_supported(h.float().cuda(), t.float().cuda(), w.float().cuda())
+    fused = _run(lambda h_, t_, w_, b_, a: ops.din_scores(h_, t_, w_, b_, "relu" if a else None), (h, t, w, b), act, r, "cuda")
+    parent = _run(_parent_pairs, (h, t, w, b), act, r, "cuda")
+    for tag, got in (("parent fp32", parent), ("fused", fused)):
+        for name, a, e in zip(("y", "dh", "dt", "dW", "db"), got, want):
+            if e is None:
+                assert a is None
+                continue
+            print("%s %s: max abs err %.3e (|ref| max %.3e)" % (tag, name, float((a.cpu().double() - e).abs().max()),
+                                                               float(e.abs().max())))
+            assert_close(a, e.float(), TOL, "%s %s" % (tag, name))
+
+
+def test_strided_operands_are_read_in_place_and_give_the_same_bits():
+    """hist = block[:, 1] of [B, 3, L, E], target = tblock[:, 2] of [B, 3, E] (rechub's layout): equal, bit for bit, to the
+    call on contiguous copies; the neighbouring slices are not written."""
+    from recbox_amd import ops
+    E, L, n = 16, 7, 12
+    g = torch.Generator().manual_seed(5)
+    sentinel = 12345.0
+    block = torch.full((B, 3, L, E), sentinel).cuda()
+    tblock = torch.full((B, 3, E), sentinel).cuda()
+    block[:, 1] = torch.randn(B, L, E, generator=g).cuda()
+    tblock[:, 2] = torch.randn(B, E, generator=g).cuda()
+    w = (torch.randn(n, 4 * E, generator=g) * 0.3).cuda()
+    b = (torch.randn(n, generator=g) * 0.3).cuda()
+    r = torch.randn(B * L, n, generator=g).cuda()
+    r2 = torch.randn(B, E, generator=g).cuda()
+    block0, tblock0 = block.clone(), tblock.clone()
+
+    def run(h, t):
+        h, t = h.detach().requires_grad_(), t.detach().requires_grad_()
+        w_, b_ = w.clone().requires_grad_(), b.clone().requires_grad_()
+        y = ops.din_scores(h, t, w_, b_, "relu")
+        (y * r).sum().backward()
+        out = [y.detach(), h.grad.clone(), t.grad.clone(), w_.grad, b_.grad]
+        h.grad = None
+        score = y.detach()[:, :1].clone().requires_grad_()
+        pooled = ops.din_pool(score, h, None, True)
+        (pooled * r2).sum().backward()
+        return out + [pooled.detach(), score.grad, h.grad]
+
+    hs, ts = block[:, 1], tblock[:, 2]
+    assert not hs.is_contiguous() and not ts.is_contiguous() and ops.din_scores_supported(hs, ts, w)
+    strided = run(hs, ts)
+    dense_ = run(hs.contiguous(), ts.contiguous())
+    for a, e in zip(strided, dense_):
+        assert torch.equal(a, e)
+    assert torch.equal(block, block0) and torch.equal(tblock, tblock0)
+    assert bool((block[:, 0] == sentinel).all()) and bool((block[:, 2] == sentinel).all())
+    assert bool((tblock[:, :2] == sentinel).all())
+
+
+def _ref_pool(score, h, mask, softmax):
+    w = score
+    if mask is not None:
+        w = w * mask
+    if softmax:
+        if mask is not None:
+            w = w + -1.e9 * (1 - mask)
+        w = w.softmax(dim=-1)
+    return (w.unsqueeze(-1) * h).sum(dim=1)
+
+
+@pytest.mark.parametrize("softmax", [False, True])
+@pytest.mark.parametrize("masking", ["none", "random", "one_sample_all_masked"])
+@pytest.mark.parametrize("L,E", [(1, 4), (5, 16), (50, 128), (300, 16), (300, 4), (50, 12)])
+def test_pool_forward_and_backward_match_float64(L, E, masking, softmax):
+    from recbox_amd import _lib, ops
+    g = torch.Generator().manual_seed(100 * L + E)
+    score = torch.randn(B, L, generator=g, dtype=torch.float64)
+    h = torch.randn(B, L, E, generator=g, dtype=torch.float64)
+    r = torch.randn(B, E, generator=g, dtype=torch.float64)
+    mask = None
+    if masking != "none":
+        mask = (torch.rand(B, L, generator=g) < 0.7).double()
+        if masking == "one_sample_all_masked":
+            mask[3] = 0.0
+
+    def run(fn, dev):
+        cast = (lambda x: x.clone()) if dev == "cpu" else (lambda x: x.float().cuda())
+        s, hh = cast(score).requires_grad_(), cast(h).requires_grad_()
+        out = fn(s, hh, None if mask is None else cast(mask), softmax)
+        (out * cast(r)).sum().backward()
+        return out.detach(), s.grad, hh.grad
+
+    want = run(_ref_pool, "cpu")
+    fused = run(lambda s, hh, m, sm: ops.din_pool(s, hh, m, sm), "cuda")
+    parent = run(_ref_pool, "cuda")                         # the same expression in float32: what the layer ran before
+    for tag, got in (("parent fp32", parent), ("fused", fused)):
+        for name, a, e in zip(("out", "dscore", "dh"), got, want):
+            print("%s %s: max abs err %.3e" % (tag, name, float((a.cpu().double() - e).abs().max())))
+            assert_close(a, e.float(), TOL, "%s %s" % (tag, name))
+    if mask is not None:
+        assert bool((fused[1].cpu()[mask == 0] == 0).all())                 # no gradient reaches a masked score
+    if masking == "one_sample_all_masked" and softmax:
+        # the reference's -1e9 fill: a sample without a single valid position gets the uniform 1 / L, exactly
+        s, m, hh = score.float().cuda(), mask.float().cuda(), h.float().cuda()
+        weight, out = torch.empty(B, L, device="cuda"), torch.empty(B, E, device="cuda")
+        rc = _lib.lib.rbx_din_pool_fwd(s.data_ptr(), m.data_ptr(), hh.data_ptr(), L * E, B, L, E, 1, weight.data_ptr(),
+                                       out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        assert rc == _lib.RBX_OK
+        assert torch.equal(weight[3].cpu(), torch.full((L,), 1.0) / L)
+        assert_close(weight, (score * mask + -1.e9 * (1 - mask)).softmax(-1).float(), 1e-6, "weights")
+
+
+def test_refusals_come_back_unsupported_and_the_layer_falls_back():
+    from recbox_amd import _lib, ops
+    from recbox_amd.ranking.pytorch.layers.attentions import DIN_Attention
+    lib, stream = _lib.lib, torch.cuda.current_stream().cuda_stream
+    L, n = 5, 8
+
+    def pairs_rc(E, n_, h=None):
+        h = torch.randn(B, L, E).cuda() if h is None else h
+        t, w = torch.randn(B, E).cuda(), torch.randn(n_, 4 * E).cuda()
+        y = torch.full((B * L, n_), 7.0).cuda()
+        rc = lib.rbx_din_pairs_fwd(h.data_ptr(), L * E, t.data_ptr(), E, B, L, E, w.data_ptr(), None, n_, 0, y.data_ptr(), stream)
+        torch.cuda.synchronize()
+        assert bool((y == 7.0).all()) or rc == _lib.RBX_OK          # refused: nothing was launched
+        return rc
+
+    assert pairs_rc(8, n) == _lib.RBX_OK
+    assert pairs_rc(6, n) == _lib.RBX_ERR_UNSUPPORTED
+    assert pairs_rc(132, n) == _lib.RBX_ERR_UNSUPPORTED
+    assert pairs_rc(8, ops.DIN_MAX_UNITS + 1) == _lib.RBX_ERR_UNSUPPORTED
+    skewed = torch.randn(B * L * 8 + 1).cuda()[1:].view(B, L, 8)       # 4 bytes past a 16-byte boundary
+    assert skewed.data_ptr() % 16 == 4
+    assert pairs_rc(8, n, skewed) == _lib.RBX_ERR_UNSUPPORTED
+    assert "16-byte" in _lib.last_error()
+    assert not ops.din_scores_supported(skewed, torch.randn(B, 8).cuda(), torch.randn(n, 32).cuda())
+    with pytest.raises(NotImplementedError):
+        ops.din_scores(skewed, torch.randn(B, 8).cuda(), torch.randn(n, 32).cuda())
+    out, wt = torch.empty(B, 8).cuda(), torch.empty(B, L).cuda()
+    assert lib.rbx_din_pool_fwd(wt.data_ptr(), None, skewed.data_ptr(), L * 8, B, L, 8, 0, wt.data_ptr(), out.data_ptr(),
+                                stream) == _lib.RBX_ERR_UNSUPPORTED
+    assert lib.rbx_din_pairs_bwd(skewed.data_ptr(), L * 6, skewed.data_ptr(), 6, B, L, 6, skewed.data_ptr(), n, 0, None,
+                                 skewed.data_ptr(), None, None, None, None, None, 0, stream) == _lib.RBX_ERR_UNSUPPORTED
+
+    # E = 6 and the misaligned view through the layer: the composition, and the float64 answer
+    for E, view in ((6, False), (8, True)):
+        torch.manual_seed(E)
+        net = DIN_Attention(embedding_dim=E, attention_units=[12, 6], hidden_activations="ReLU", use_softmax=True)
+        twin = DIN_Attention(embedding_dim=E, attention_units=[12, 6], hidden_activations="ReLU", use_softmax=True).double()
+        twin.load_state_dict({k: v.double() for k, v in net.state_dict().items()})
+        net.cuda()
+        t, h = torch.randn(B, E, dtype=torch.float64), torch.randn(B, L, E, dtype=torch.float64)
+        mask = (torch.rand(B, L) < 0.7).double()
+        tt = t.unsqueeze(1).expand(-1, L, -1)
+        x = torch.cat([tt, h, tt - h, tt * h], dim=-1).view(-1, 4 * E)
+        for m in twin.attention_layer.mlp:
+            x = m(x)
+        want = _ref_pool(x.view(-1, L), h, mask, True)
+        hc = h.float().cuda()
+        if view:
+            hc = torch.cat([hc.new_zeros(1), hc.flatten()])[1:].view(B, L, E)
+            assert not ops.din_scores_supported(hc, t.float().cuda(), net.attention_layer.mlp[0].weight)
+        assert_close(net(t.float().cuda(), hc, mask.float().cuda()), want.float(), TOL, "fallback output (E=%d)" % E)
+
+
+def test_two_backward_passes_give_the_same_bits():
+    from recbox_amd import ops
+    E, L, n = 64, 50, 36                                     # two splits of the dW reduction, samples across tiles
+    h, t, w, b, r = [None if x is None else x.float().cuda() for x in _pairs_inputs(E, L, n, True, 9)]
+    mask = (torch.rand(B, L, generator=torch.Generator().manual_seed(2)) < 0.7).float().cuda()
+    head = (torch.randn(n, generator=torch.Generator().manual_seed(3)) * 0.3).cuda()
+
+    def grads():
+        leaves = [x.clone().requires_grad_() for x in (h, t, w, b)]
+        y = ops.din_scores(*leaves, "relu")
+        out = ops.din_pool(y @ head, leaves[0], mask, True)
+        (out * r[:B, :1]).sum().backward()
+        return [x.grad for x in leaves]
+
+    first, second = grads(), grads()
+    for a, e in zip(first, second):
+        assert torch.equal(a, e)
+
+
+def _attention(E, units, acts, softmax, seed=0):
+    from recbox_amd.ranking.pytorch.layers.attentions import DIN_Attention
+    torch.manual_seed(seed)
+    net = DIN_Attention(embedding_dim=E, attention_units=units, hidden_activations=acts, use_softmax=softmax).cuda()
+    with torch.no_grad():
+        for p in net.parameters():
+            p.copy_(torch.randn_like(p) * 0.3)
+    return net.train()
+
+
+def test_training_step_replays_from_a_graph_bit_for_bit():
+    """One DIN_Attention step (forward, .sum().backward()) captured on one stream, replayed twice on refreshed inputs."""
+    E, L, Bc = 16, 10, 64                                    # B L = 640 rows: the towers' dW stays on the capturing stream
+    net = _attention(E, [12, 6], "ReLU", True)
+    g = torch.Generator().manual_seed(4)
+
+    def inputs():
+        return (torch.randn(Bc, E, generator=g).cuda(), torch.randn(Bc, L, E, generator=g).cuda(),
+                (torch.rand(Bc, L, generator=g) < 0.7).float().cuda())
+
+    t, h, mask = inputs()
+    t.requires_grad_(), h.requires_grad_()
+
+    def step():
+        for p in list(net.parameters()) + [t, h]:
+            p.grad = None
+        out = net(t, h, mask)
+        out.sum().backward()
+        return out
+
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(2):
+            step()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    for p in list(net.parameters()) + [t, h]:
+        p.grad = None
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = net(t, h, mask)
+        out.sum().backward()
+    held = [out] + [p.grad for p in list(net.parameters()) + [t, h]]
+    assert all(x is not None for x in held)
+    for _ in range(2):
+        t1, h1, m1 = inputs()
+        with torch.no_grad():
+            t.copy_(t1), h.copy_(h1), mask.copy_(m1)
+        graph.replay()
+        torch.cuda.synchronize()
+        got = [x.detach().clone() for x in held]
+        eager_out = step()
+        torch.cuda.synchronize()
+        want = [eager_out.detach()] + [p.grad for p in list(net.parameters()) + [t, h]]
+        for a, e in zip(got, want):
+            assert torch.equal(a, e)
+
+
+def test_training_step_launches_the_din_kernels_and_no_concat_or_softmax_kernel():
+    from torch.profiler import ProfilerActivity, profile
+    E, L, Bp = 16, 50, 128
+    net = _attention(E, [32, 16], "Dice", True)
+    g = torch.Generator().manual_seed(6)
+    t = torch.randn(Bp, E, generator=g).cuda().requires_grad_()
+    h = torch.randn(Bp, L, E, generator=g).cuda().requires_grad_()
+    mask = (torch.rand(Bp, L, generator=g) < 0.7).float().cuda()
+    net(t, h, mask).sum().backward()
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        net(t, h, mask).sum().backward()
+        torch.cuda.synchronize()
+    names = [e.key for e in prof.key_averages() if e.device_type is not None and "Memcpy" not in e.key and "Memset" not in e.key]
+    bad = [n for n in names if any(s in n for s in ("CatArray", "oftMax", "oftmax"))]
+    assert not bad, bad
+    for kernel in ("rbx::din_pairs_fwd_kernel", "rbx::din_pairs_dx_kernel", "rbx::din_pairs_dw_kernel", "rbx::din_pool_fwd_kernel",
+                   "rbx::din_pool_bwd_kernel"):
+        assert any(kernel in n for n in names), (kernel, names)
+
+
+class _TwinDice(nn.Module):
+    """rechub's Dice (basic/activation.py) as the mirror keeps it, for the float64 twin."""
+
+    def __init__(self, epsilon=1e-3):
+        super().__init__()
+        self.epsilon = epsilon
+        self.alpha = nn.Parameter(torch.randn(1))
+
+    def forward(self, x):
+        avg = x.mean(dim=1).unsqueeze(dim=1)
+        var = (torch.pow(x - avg, 2) + self.epsilon).sum(dim=1).unsqueeze(dim=1)
+        ps = torch.sigmoid((x - avg) / torch.sqrt(var))
+        return ps * x + (1 - ps) * self.alpha * x
+
+
+def _twin_mlp(fan_in, dims):
+    mods = []
+    for d in dims:
+        mods += [nn.Linear(fan_in, d), nn.BatchNorm1d(d), _TwinDice(), nn.Dropout(p=0)]
+        fan_in = d
+    mods.append(nn.Linear(fan_in, 1))
+    holder = nn.Module()
+    holder.mlp = nn.Sequential(*mods)
+    return holder
+
+
+class _TwinDIN(nn.Module):
+    """rechub's DIN from plain torch modules, under the reference's attribute names."""
+
+    def __init__(self, tables, E, n_hist, all_dims, mlp_dims, att_dims, softmax):
+        super().__init__()
+        self.embedding = nn.Module()
+        self.embedding.embed_dict = nn.ModuleDict({k: nn.Embedding(v, E) for k, v in tables})
+        self.attention_layers = nn.ModuleList()
+        for _ in range(n_hist):
+            unit = nn.Module()
+            unit.attention = _twin_mlp(4 * E, att_dims)
+            self.attention_layers.append(unit)
+        self.mlp = _twin_mlp(all_dims, mlp_dims)
+        self.softmax = softmax
+
+    def forward(self, x):
+        tab = self.embedding.embed_dict
+        profile = tab["user"](x["user"])
+        hist = [tab["item"](x["hist_item"]), tab["cate"](x["hist_cate"])]
+        target = [tab["item"](x["item"]), tab["cate"](x["cate"])]
+        pooled = []
+        for unit, h, t in zip(self.attention_layers, hist, target):
+            L = h.shape[1]
+            tt = t.unsqueeze(1).expand(-1, L, -1)
+            pairs = torch.cat([tt, h, tt - h, tt * h], dim=-1)
+            w = unit.attention.mlp(pairs.view(-1, pairs.shape[-1])).view(-1, L)
+            if self.softmax:
+                w = w.softmax(dim=-1)
+            pooled.append((w.unsqueeze(-1) * h).sum(dim=1))
+        y = self.mlp.mlp(torch.cat(pooled + target + [profile], dim=1))
+        return torch.sigmoid(y.squeeze(1))
+
+
+@pytest.mark.parametrize("softmax", [False, True])
+def test_rechub_din_matches_its_float64_twin(softmax):
+    from recbox_amd import compat
+    from recbox_amd.rechub.basic.features import SequenceFeature, SparseFeature
+    from recbox_amd.rechub.models.ranking import DIN, ActivationUnit
+    E, L, Bm = 8, 7, 48
+    torch.manual_seed(11)
+    features = [SparseFeature("user", 11, E)]
+    history = [SequenceFeature("hist_item", 23, E, pooling="concat", shared_with="item", padding_idx=0),
+               SequenceFeature("hist_cate", 13, E, pooling="concat", shared_with="cate")]
+    targets = [SparseFeature("item", 23, E), SparseFeature("cate", 13, E)]
+    dut = DIN(features, history, targets, {"dims": [16, 8]}, {"dims": [12], "use_softmax": softmax})
+    with open(os.path.join(GOLDEN, "rechub_din_keys.txt")) as fh:
+        assert list(dut.state_dict().keys()) == fh.read().split()
+    assert isinstance(dut.attention_layers[0], ActivationUnit) and dut.attention_layers[0].use_softmax is softmax
+    with torch.no_grad():
+        for p in dut.parameters():
+            p.copy_(torch.randn_like(p) * 0.3)
+    twin = _TwinDIN([("user", 11), ("item", 23), ("cate", 13)], E, 2, 5 * E, [16, 8], [12], softmax).double()
+    twin.load_state_dict({k: (v.double() if v.is_floating_point() else v) for k, v in dut.state_dict().items()})
+    dut.cuda().train(), twin.train()
+    g = torch.Generator().manual_seed(12)
+    x = {"user": torch.randint(0, 11, (Bm,), generator=g), "item": torch.randint(1, 23, (Bm,), generator=g),
+         "cate": torch.randint(0, 13, (Bm,), generator=g), "hist_item": torch.randint(0, 23, (Bm, L), generator=g),
+         "hist_cate": torch.randint(0, 13, (Bm, L), generator=g)}
+    x["hist_item"][:, -2:] = 0                               # padding ids at the tail of every sequence
+    r = torch.randn(Bm, generator=g, dtype=torch.float64)
+    want = twin(x)
+    (want * r).sum().backward()
+    got = dut({k: v.cuda() for k, v in x.items()})
+    (got * r.float().cuda()).sum().backward()
+    assert_close(got, want.float(), TOL, "DIN output")
+    named = dict(twin.named_parameters())
+    for name, p in dut.named_parameters():
+        assert p.grad is not None, name
+        assert_close(p.grad, named[name].grad.float(), TOL, "grad " + name)
+
+    report = compat.install(prefixes=("torch_rechub",))
+    try:
+        import importlib
+        mod = importlib.import_module("torch_rechub.models.ranking.din")
+        assert mod.DIN is DIN and mod.ActivationUnit is ActivationUnit
+        assert importlib.import_module("torch_rechub.models.ranking").DIN is DIN
+    finally:
+        compat.uninstall(report)
