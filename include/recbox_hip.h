@@ -1091,6 +1091,38 @@ int rbx_din_pool_fwd(const float* d_score, const float* d_mask, const float* d_h
 int rbx_din_pool_bwd(const float* d_dout, const float* d_weight, const float* d_mask, const float* d_hist,
                      int64_t hist_stride_b, int64_t batch, int32_t seq_len, int32_t dim, int32_t softmax, float* d_dscore,
                      float* d_dhist, void* stream);
+
+/* ---- field-aware FM: gather and cross, no [B, F, F, D] tensor (csrc/rbx_ffm.hip; additions only, the version stays) ----
+ * Replaces third_party/rechub/models/ranking/deepffm.py:58-66 / :133-141 (the ffm_embedding lookups of x * F +
+ * fields_offset, concatenated to [B, F, F, D]) together with basic/layers.py:651-680 (FFM: P = F(F-1)/2 sliced
+ * multiplies and a stack) and their autograd backward.  F = n_fields one-id categorical descriptors (pool NONE, seq_len 1)
+ * of one dim D; fields[i].table is the contiguous [vocab_i, D] weight of the reference's nn.Embedding, an id x of field i
+ * names its rows x*F .. x*F+F-1.  With E[b,i,j] = table_i[x_i(b)*F + j] and the pairs i < j in the reference's order (i
+ * outer, j inner):
+ *   reduce_sum == 0   d_out[b * out_stride_b + p(i,j) * D + d] = E[b,i,j][d] * E[b,j,i][d]        ([B, P, D])
+ *   reduce_sum != 0   d_out[b * out_stride_b + p(i,j)]         = sum_d of that product            ([B, P])
+ * Ids are read in place (any rbx_dtype_t, element stride ids_stride_b) as rbx_embed_fwd reads them.  The diagonal rows
+ * E[b,i,i] are never read.  An id with x < 0 or x*F + F > vocab_i reads as a block of zeros and sets bit 0 of *d_status.
+ *   rbx_ffm_fwd    one launch; reads F(F-1) rows and writes P rows (or P floats) per sample.
+ *   rbx_ffm_sort   the (block, sample) pairs of every field with a gradient, sorted by the passes of rbx_embed_sort over
+ *                  the view of table i as [vocab_i / F, F*D].  fields[i].grad: non-NULL for every table that will get a
+ *                  gradient (the pointer is not used here: a placeholder does), as in the rbx_ffm_bwd that follows.
+ *   rbx_ffm_bwd    dense [vocab_i, D] gradients into fields[i].grad (NULL = frozen): dE[b,i,j] = dout[b, p(i,j)] o E[b,j,i]
+ *                  is formed inside the segmented reduce and never stored; the partner ids are read in place.  Every touched
+ *                  block is written once -- its diagonal row i with zeros --; accumulate as in rbx_embed_bwd (0: the caller
+ *                  zero-filled the gradients, touched blocks are stored; else read-modify-write).  No float atomics: the
+ *                  same bits from run to run.  The workspace is that of rbx_ffm_sort for the same fields and batch.
+ * RBX_ERR_UNSUPPORTED before anything is launched or cleared: D % 4 != 0 or D > 128; F < 2 or F > RBX_MAX_FIELDS;
+ * F * D > 1024; a table_stride other than dim; a padding_idx; two descriptors with one table; a table, gradient or (with
+ * reduce_sum == 0) d_out / d_dout base that is not 16-byte aligned, or a row stride of those that is not a multiple of 4.
+ * A vocab below F (no whole block) is RBX_ERR_INVALID.  batch == 0: RBX_OK, nothing launched.  All calls are capturable. */
+int rbx_ffm_fwd(const rbx_field_t* fields, int32_t n_fields, int64_t batch, int32_t reduce_sum, float* d_out,
+                int64_t out_stride_b, int32_t* d_status, void* stream);
+size_t rbx_ffm_bwd_workspace_size(const rbx_field_t* fields, int32_t n_fields, int64_t batch);
+int rbx_ffm_sort(const rbx_field_t* fields, int32_t n_fields, int64_t batch, void* d_workspace, size_t workspace_bytes,
+                 int32_t* d_status, void* stream);
+int rbx_ffm_bwd(const rbx_field_t* fields, int32_t n_fields, int64_t batch, int32_t reduce_sum, const float* d_dout,
+                int64_t dout_stride_b, int32_t accumulate, void* d_workspace, size_t workspace_bytes, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -265,6 +265,10 @@ SIGNATURES = {
                                          _sz, _P]),
     "rbx_din_pool_fwd": (ctypes.c_int, [_P, _P, _P, _i64, _i64, _i32, _i32, _i32, _P, _P, _P]),
     "rbx_din_pool_bwd": (ctypes.c_int, [_P, _P, _P, _P, _i64, _i64, _i32, _i32, _i32, _P, _P, _P]),
+    "rbx_ffm_fwd": (ctypes.c_int, [_FP, _i32, _i64, _i32, _P, _i64, _P, _P]),
+    "rbx_ffm_bwd_workspace_size": (_sz, [_FP, _i32, _i64]),
+    "rbx_ffm_sort": (ctypes.c_int, [_FP, _i32, _i64, _P, _sz, _P, _P]),
+    "rbx_ffm_bwd": (ctypes.c_int, [_FP, _i32, _i64, _i32, _P, _i64, _i32, _P, _sz, _P]),
 }
 
 

@@ -90,9 +90,10 @@ _RECHUB = {
     "models.matching.dssm": ("recbox_amd.rechub.models.matching", ["DSSM"]),
     "models.matching.youtube_dnn": ("recbox_amd.rechub.models.matching", ["YoutubeDNN"]),
     "models.matching.sasrec": ("recbox_amd.rechub.models.matching", ["SASRec", "PointWiseFeedForward"]),
-    "models.ranking": ("recbox_amd.rechub.models.ranking", ["DeepFM", "DIN"]),
+    "models.ranking": ("recbox_amd.rechub.models.ranking", ["DeepFM", "DIN", "DeepFFM", "FatDeepFFM"]),
     "models.ranking.din": ("recbox_amd.rechub.models.ranking", ["DIN", "ActivationUnit"]),
     "models.ranking.deepfm": ("recbox_amd.rechub.models.ranking", ["DeepFM"]),
+    "models.ranking.deepffm": ("recbox_amd.rechub.models.ranking", ["DeepFFM", "FatDeepFFM"]),
 }
 
 

@@ -112,6 +112,11 @@ class config(object):
     # with dims [36] loses (0.95 x): the concatenation there is small and the composition's GEMM cheap.  Widths 20 to 28
     # were not measured and stay on the composition.  The ops themselves (din_scores, din_pool) serve every supported width.
     din_min_dim = int(os.environ.get("RECBOX_AMD_DIN_MIN_DIM", "32"))
+    # field-aware FM (rechub's DeepFFM / FatDeepFFM): the F lookups per field and the P = F(F-1)/2 crosses as one op over the raw
+    # ids and the ffm_embedding tables (ffm_cross: csrc/rbx_ffm.hip) instead of F.embedding into [B, F, F, D], an indexed
+    # multiply, and autograd's two copies of that tensor.  Off, or for a shape ffm_supported refuses: that composition.
+    # Measurements: profiles/ffm/INDEX.md.
+    ffm_fused = os.environ.get("RECBOX_AMD_FFM_FUSED", "1") != "0"
 
 
 def _require_cuda(t, what):
@@ -4199,3 +4204,118 @@ def din_pool(score, history, mask=None, softmax=False):
     """The tail of DIN's activation unit: score [B, L] (or [B L, 1]), history [B, L, E], mask [B, L] with 0 at masked
     positions -> [B, E]."""
     return _DinPool.apply(score, history, mask, softmax)
+
+
+# ---- field-aware FM: gather and cross, no [B, F, F, D] tensor (csrc/rbx_ffm.hip) ------------------------------------------
+_ffm_plans = {}
+
+
+def _ffm_plan(F, D, vocabs):
+    key = (F, D, tuple(vocabs))
+    plan = _ffm_plans.get(key)
+    if plan is None:
+        specs = [FieldSpec("ffm%d" % i, FIELD_CATEGORICAL, D, 0, param=i, vocab=int(v)) for i, v in enumerate(vocabs)]
+        plan = _ffm_plans[key] = EmbedPlan(specs, F * (F - 1) // 2 * D)
+    return plan
+
+
+def ffm_supported(tables, ids=None, padding_idx=None):
+    """Whether ``ffm_cross`` takes these ``ffm_embedding`` tables (the refusals of rbx_ffm_fwd, decided on the host): fp32,
+    contiguous, on the GPU, one ``[vocab_i * F, D]`` table per field with 2 <= F <= 64, D a multiple of 4 up to 128 and
+    F * D <= 1024, no table given twice, no ``padding_idx`` (``padding_idx``: one entry per field, None = unset)."""
+    F = len(tables)
+    if F < 2 or F > _lib.RBX_MAX_FIELDS:
+        return False
+    if padding_idx is not None and any(p is not None for p in padding_idx):
+        return False
+    D = tables[0].shape[-1] if tables[0].dim() == 2 else 0
+    if D % 4 != 0 or D <= 0 or D > 128 or F * D > 1024:
+        return False
+    seen = set()
+    for t in tables:
+        if (not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != D or not t.is_contiguous()
+                or t.shape[0] < F or t.data_ptr() % 16 != 0 or t.data_ptr() in seen):
+            return False
+        seen.add(t.data_ptr())
+    if ids is not None:
+        if len(ids) != F or any((not t.is_cuda) or t.numel() != ids[0].numel() for t in ids):
+            return False
+    return True
+
+
+class _FfmCross(torch.autograd.Function):
+    """out[B, P, D] (or [B, P]) = E[b,i,j] * E[b,j,i] over the pairs i < j, E[b,i,j] = table_i[x_i(b) * F + j]; backward =
+    the sorted segmented reduce over (block, sample) pairs with the cross formed in its fetch."""
+
+    @staticmethod
+    def forward(ctx, n, train, reduce_sum, *tensors):
+        inputs, params = tensors[:n], tensors[n:]
+        for p in params:
+            _require_cuda(p, "ffm table")
+            if p.dtype != torch.float32 or not p.is_contiguous() or p.dim() != 2:
+                raise RuntimeError("recbox_amd: ffm tables must be contiguous fp32 [vocab * F, D]")
+        D = params[0].shape[1]
+        plan = _ffm_plan(n, D, [p.shape[0] for p in params])
+        B, keep = plan.bind_inputs(inputs)
+        plan.bind_params(params)
+        dev = params[0].device
+        P = n * (n - 1) // 2
+        out = torch.empty((B, P) if reduce_sum else (B, P, D), dtype=torch.float32, device=dev)
+        width = P if reduce_sum else P * D
+        status = _status_word(dev)
+        check(_timed(("ffm_fwd", n, D, B),
+                     lambda: lib.rbx_ffm_fwd(plan.arr, n, B, int(reduce_sum), _ptr(out), width, _ptr(status), _stream())))
+        _check_status(status)
+        ctx.plan, ctx.inputs, ctx.B, ctx.params, ctx.reduce_sum, ctx.width = plan, keep, B, params, int(reduce_sum), width
+        ctx.sort = None
+        if B > 0 and train:
+            # same descriptor set as the backward (placeholder grad pointers), sorted on the side stream
+            placeholders = [p if p.requires_grad else None for p in params]
+            plan.bind_params(params, placeholders)
+            ws_bytes = lib.rbx_ffm_bwd_workspace_size(plan.arr, n, B)
+            if ws_bytes > 0:
+                ctx.sort = _EarlySort(dev, ws_bytes,
+                                      lambda ws, st: lib.rbx_ffm_sort(plan.arr, n, B, _ptr(ws), ws_bytes, None, st))
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        plan, params, B, n = ctx.plan, ctx.params, ctx.B, ctx.plan.n
+        dout = dout.contiguous().float()
+        want = [ctx.needs_input_grad[3 + n + i] for i in range(n)]
+        want_now = [p.requires_grad for p in params]
+        grads = _flat_zero_grads(params, want, dout.device)
+        none = (None, None, None) + (None,) * n
+        if B == 0:
+            return none + tuple(grads)
+        plan.bind_inputs(ctx.inputs)
+        plan.bind_params(params, grads)
+        if ctx.sort is not None and want_now == list(want):
+            ctx.sort.join()
+            ws, ws_bytes = ctx.sort.ws, ctx.sort.ws_bytes
+        else:                                          # e.g. torch.autograd.grad on a subset: sort now
+            ws_bytes = lib.rbx_ffm_bwd_workspace_size(plan.arr, n, B)
+            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dout.device)
+            check(lib.rbx_ffm_sort(plan.arr, n, B, _ptr(ws), ws_bytes, None, _stream()))
+        # grads are views of a freshly zeroed buffer: accumulate=0 lets the kernel store instead of RMW
+        check(_timed(("ffm_bwd", n, params[0].shape[1], B),
+                     lambda: lib.rbx_ffm_bwd(plan.arr, n, B, ctx.reduce_sum, _ptr(dout), ctx.width, 0, _ptr(ws), ws_bytes,
+                                             _stream())))
+        return none + tuple(grads)
+
+
+def ffm_cross(tables, ids, reduce_sum=False):
+    """Field-aware FM crosses straight from the raw ids: ``tables[i]`` is field i's ``[vocab_i * F, D]`` embedding weight
+    (id ``x`` names its rows ``x * F .. x * F + F - 1``), ``ids[i]`` its ``[B]`` id column (int32 / int64 / float32 / float64,
+    any stride).  Returns ``[B, F(F-1)/2, D]`` -- ``table_i[x_i * F + j] * table_j[x_j * F + i]`` for the pairs i < j, i outer
+    -- or, with ``reduce_sum``, its sum over D as ``[B, F(F-1)/2]``.  The ``[B, F, F, D]`` block of the reference never
+    exists, forward or backward.  An id outside its table raises IndexError as ``embed_lookup`` does (at once, or through
+    ``check_deferred_ids()`` when ``config.check_ids`` is off).  Shapes ``ffm_supported`` refuses raise NotImplementedError."""
+    tables, ids = list(tables), list(ids)
+    if len(tables) != len(ids):
+        raise ValueError("ffm_cross: %d tables but %d id columns" % (len(tables), len(ids)))
+    for t in tables:
+        _require_cuda(t, "ffm table")
+    ids = [_id_column(t) for t in ids]
+    train = torch.is_grad_enabled() and any(p.requires_grad for p in tables)   # grad mode is off inside forward()
+    return _FfmCross.apply(len(ids), train, bool(reduce_sum), *ids, *tables)

@@ -2,7 +2,7 @@
 /root/reference/recbox/third_party/rechub/basic/layers.py): ``EmbeddingLayer`` (+``InputMask``
 and the three pooling modules), ``MLP``, ``FM``, ``LR``, ``PredictionLayer`` with the same
 constructors, outputs, exceptions and parameter names (``embed_dict.<feature>.weight``,
-``mlp.<i>.*``, ``fc.*``).  ``EmbeddingLayer.forward`` is ONE ``rbx_embed_fwd`` launch for all
+``mlp.<i>.*``, ``fc.*``), and ``FFM`` / ``CEN`` of DeepFFM / FatDeepFFM (``u``, ``mlp_att.*``).  ``EmbeddingLayer.forward`` is ONE ``rbx_embed_fwd`` launch for all
 requested features: one-hot lookups, id-masked mean/sum pooling (mask = ``id != padding_idx``,
 eps 1e-16, the pad row is a normal trainable row that just gets weight 0), concat pooling and
 dense pass-through all land in one ``[B, width]`` row.
@@ -298,3 +298,46 @@ class FM(nn.Module):
 
     def forward(self, x):
         return ops.interaction(x, "product_sum" if self.reduce_sum else "bi_interaction")
+
+
+class FFM(nn.Module):
+    """Field-aware crosses of an already gathered block (rechub/basic/layers.py:651-682): x [B, F, F, D] ->
+    x[:, i, j] * x[:, j, i] over the pairs i < j (i outer), [B, P, D], or its sum over D as [B, P, 1] with ``reduce_sum``.
+    One indexed expression instead of the reference's P sliced multiplies and a stack.  This is NOT the hot path: the
+    DeepFFM / FatDeepFFM mirrors never build the block, they call ``ops.ffm_cross`` on the raw ids."""
+
+    def __init__(self, num_fields, reduce_sum=True):
+        super().__init__()
+        self.num_fields = num_fields
+        self.reduce_sum = reduce_sum
+        iu = torch.triu_indices(num_fields, num_fields, offset=1)
+        self.register_buffer("_pair_i", iu[0].contiguous(), persistent=False)
+        self.register_buffer("_pair_j", iu[1].contiguous(), persistent=False)
+
+    def forward(self, x):
+        crossed = x[:, self._pair_i, self._pair_j] * x[:, self._pair_j, self._pair_i]
+        if self.reduce_sum:
+            crossed = torch.sum(crossed, dim=-1, keepdim=True)
+        return crossed
+
+
+class CEN(nn.Module):
+    """Compose-Excitation Network of FAT-DeepFFM (rechub/basic/layers.py:685-719): d = relu(sum_d u * em), s = mlp_att(d),
+    out = (s[..., None] * em) flattened to [B, P * D].  The two FC layers run on the project's ``MLP``; the rescale is
+    ``ops.row_scale`` where that op can be used -- its scale carries no gradient, so only when ``s`` needs none
+    (inference).  There is no kernel of its own for the descriptor or the rescale."""
+
+    def __init__(self, embed_dim, num_field_crosses, reduction_ratio):
+        super().__init__()
+        self.u = torch.nn.Parameter(torch.rand(num_field_crosses, embed_dim), requires_grad=True)
+        self.mlp_att = MLP(num_field_crosses, dims=[num_field_crosses // reduction_ratio, num_field_crosses],
+                           output_layer=False, activation="relu")
+
+    def forward(self, em):
+        d = torch.relu((self.u.squeeze(0) * em).sum(-1))
+        s = self.mlp_att(d)
+        if em.is_cuda and not (torch.is_grad_enabled() and s.requires_grad):
+            aem = ops.row_scale(em, s)
+        else:
+            aem = s.unsqueeze(-1) * em
+        return aem.flatten(start_dim=1)

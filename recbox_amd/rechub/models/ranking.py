@@ -1,11 +1,12 @@
 """DeepFM (drop-in for ``torch_rechub.models.ranking.DeepFM``,
-/root/reference/recbox/third_party/rechub/models/ranking/deepfm.py:14-42) and DIN with its ActivationUnit
-(``torch_rechub.models.ranking.din``, rechub/models/ranking/din.py:16-91)."""
+/root/reference/recbox/third_party/rechub/models/ranking/deepfm.py:14-42), DIN with its ActivationUnit
+(``torch_rechub.models.ranking.din``, rechub/models/ranking/din.py:16-91), and DeepFFM / FatDeepFFM
+(``torch_rechub.models.ranking.deepffm``, rechub/models/ranking/deepffm.py:15-123)."""
 import torch
 
 from ... import dense, ops
 from ..basic.features import DenseFeature, SparseFeature
-from ..basic.layers import FM, LR, MLP, EmbeddingLayer
+from ..basic.layers import CEN, FFM, FM, LR, MLP, EmbeddingLayer
 
 
 class DeepFM(torch.nn.Module):
@@ -98,3 +99,74 @@ class DIN(torch.nn.Module):
         pooled = [unit(history[:, i], target[:, i]) for i, unit in enumerate(self.attention_layers)]
         mlp_in = torch.cat(pooled + [target.flatten(start_dim=1), profile.flatten(start_dim=1)], dim=1)
         return torch.sigmoid(self.mlp(mlp_in).squeeze(1))
+
+
+class _DeepFFMBase(torch.nn.Module):
+    """What DeepFFM and FatDeepFFM share (deepffm.py:27-66 / :83-123): a first-order part summed over ``linear_features``, the
+    field-aware crosses of ``cross_features`` -- feature i owns a table of ``vocab_i * F`` rows, id x names rows
+    x * F .. x * F + F - 1 -- an MLP over them, and a bias ``b``."""
+
+    def _build(self, linear_features, cross_features, embed_dim, mlp_params):
+        self.linear_features = linear_features
+        self.cross_features = cross_features
+        self.num_fields = len(cross_features)
+        self.num_field_cross = self.num_fields * (self.num_fields - 1) // 2
+        self.ffm = FFM(num_fields=self.num_fields, reduce_sum=False)
+        self.mlp_out = MLP(self.num_field_cross * embed_dim, **mlp_params)
+        self.linear_embedding = EmbeddingLayer(linear_features)
+        self.ffm_embedding = EmbeddingLayer(cross_features)
+        self.b = torch.nn.Parameter(torch.zeros(1))
+        self.register_buffer('fields_offset', torch.arange(0, self.num_fields, dtype=torch.long))
+
+    def _ffm_tables(self):
+        return [self.ffm_embedding.embed_dict[f.name if f.shared_with is None else f.shared_with]
+                for f in self.cross_features]
+
+    def _ffm_padding(self):
+        """One entry per cross feature: the padding_idx its feature or its table declares (None = unset).  The reference
+        looks such a feature up like any other; the fused op's gate refuses it and the composition serves it."""
+        return [f.padding_idx if f.padding_idx is not None else t.padding_idx
+                for f, t in zip(self.cross_features, self._ffm_tables())]
+
+    def _crosses(self, x):
+        """[B, P, D]: ``ops.ffm_cross`` on the raw ids and the tables; what its gate refuses (a width that is no multiple
+        of 4, F * D > 1024, a padding_idx, a shared table, ...) runs the reference's composition."""
+        tables = self._ffm_tables()
+        ids = [x[f.name] for f in self.cross_features]
+        weights = [t.weight for t in tables]
+        if ops.config.ffm_fused and ops.ffm_supported(weights, ids, self._ffm_padding()):
+            return ops.ffm_cross(weights, [t.reshape(-1) for t in ids], reduce_sum=False)
+        rows = [torch.nn.functional.embedding(i.long().reshape(-1, 1) * self.num_fields + self.fields_offset, t.weight,
+                                              t.padding_idx) for i, t in zip(ids, tables)]
+        return self.ffm(torch.stack(rows, dim=1))                 # [B, F, F, D] -> [B, P, D]
+
+    def _linear(self, x):
+        return self.linear_embedding(x, self.linear_features, squeeze_dim=True).sum(1, keepdim=True)
+
+
+class DeepFFM(_DeepFFMBase):
+    def __init__(self, linear_features, cross_features, embed_dim, mlp_params):
+        super().__init__()
+        self._build(linear_features, cross_features, embed_dim, mlp_params)
+
+    def forward(self, x):
+        y_linear = self._linear(x)
+        em = self._crosses(x)
+        y_ffm = self.mlp_out(em.flatten(start_dim=1))
+        y = y_linear + y_ffm
+        return torch.sigmoid(y.squeeze(1) + self.b)
+
+
+class FatDeepFFM(_DeepFFMBase):
+    def __init__(self, linear_features, cross_features, embed_dim, reduction_ratio, mlp_params):
+        super().__init__()
+        self._build(linear_features, cross_features, embed_dim, mlp_params)
+        self.cen = CEN(embed_dim, self.num_field_cross, reduction_ratio)
+
+    def forward(self, x):
+        y_linear = self._linear(x)
+        em = self._crosses(x)
+        aem = self.cen(em)
+        y_ffm = self.mlp_out(aem)
+        y = y_linear + y_ffm
+        return torch.sigmoid(y.squeeze(1) + self.b)
