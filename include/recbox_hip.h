@@ -1123,6 +1123,52 @@ int rbx_ffm_sort(const rbx_field_t* fields, int32_t n_fields, int64_t batch, voi
                  int32_t* d_status, void* stream);
 int rbx_ffm_bwd(const rbx_field_t* fields, int32_t n_fields, int64_t batch, int32_t reduce_sum, const float* d_dout,
                 int64_t dout_stride_b, int32_t accumulate, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ---- multi-interest dynamic routing: MIND, ComirecDR (csrc/rbx_capsule.hip; additions only, the version stays) -----------
+ * Replaces third_party/rechub/basic/layers.py:588-643 (CapsuleNetwork.forward) and its autograd backward.  B = batch,
+ * L = seq_len, D = dim, K = interests, N = K D.  hat is addressed as hat[b sb + k sk + l sl + e]: [B, L, N] with sk = D for
+ * the per-interest forms, [B, L, D] with sk = 0 for the shared form (bilinear_type 0, layers.py:590-591).
+ *   rbx_capsule_hat          layers.py:595-596, whose product is [B, L, N, D]: d_hat [B, L, N] (contiguous) with
+ *                            hat[b, l, n] = sum_d w[l, n, d] x[b, l, d], one fp32-MFMA GEMM per position; d_x is read in place at
+ *                            x[b x_stride_b + l x_stride_l + d], d_w is the contiguous [L, N, D] parameter.
+ *   rbx_capsule_route_fwd    layers.py:607-641 for one (b, k) per wavefront with its [L, D] slice of hat in LDS: `updates`
+ *                            (0..2 = min(routing_times - 1, 2)) rounds of c = softmax_l(logits) set to 0 where the mask is 0
+ *                            (not renormalised), s = sum_l c[l] hat[l], v = squash(s), logits += hat v, then the output round.
+ *                            d_init [B, K, L]: the starting logits, NULL = zeros.  The mask is read in place at
+ *                            mask[b mask_stride_b + l mask_stride_l] as RBX_I32 / RBX_I64 / RBX_F32 / RBX_MASK_U8 (bool).
+ *                            Writes d_v [B, K, D], and what the backward needs: d_c [B, K, L], d_s [B, K, D].  No atomics.
+ *   rbx_capsule_route_bwd    the output round's gradient (earlier rounds are detached, layers.py:602-603): d_ds [B, K, D] =
+ *                            f(n) dv + 2 f'(n) (s . dv) s with n = |s|^2, f(n) = n / (1 + n) / sqrt(n + 1e-9) (NULL: not stored);
+ *                            d_dhat (NULL: not formed) = c ds in hat's layout: [B, L, N], or with shared != 0 [B, L, D] summed
+ *                            over k in order.
+ *   rbx_capsule_bilinear_dx  d_dx [B, L, D] = sum_n G[b, l, n] w[l, n, d]
+ *   rbx_capsule_bilinear_dw  d_dw [L, N, D] = sum_b G[b, l, n] x[b, l, d]; samples are summed in splits of
+ *                            rbx_capsule_dw_split() whose partial sums (in the workspace) are added in order.
+ *                            G[b, l, n] = g[b g_stride_b + l g_stride_l + n], times c[b, n / D, l] when d_c is given: with
+ *                            g = ds (g_stride_b = N, g_stride_l = 0) the operand c ds is formed on the way into the MFMA and
+ *                            neither d_hat nor a [B, L, N, D] tensor exists; with g = a stored d_hat and d_c = NULL they are the
+ *                            backward of rbx_capsule_hat alone.
+ * Supported: D a multiple of 4 in [4, 128]; 1 <= K <= 32; L (D + 1) + 3 L + D <= 14336 floats for the routing call
+ * (rbx_capsule_route_supported; covers L = 200 at D = 64 and L = 50 at D = 128); 16-byte aligned float bases and strides that
+ * are multiples of 4.  Anything else: RBX_ERR_UNSUPPORTED before any launch.  batch = 0 launches nothing (dw: zeros).  No
+ * call allocates or reads back: all are capturable. */
+#define RBX_MASK_U8 4
+int rbx_capsule_route_supported(int32_t seq_len, int32_t dim);
+int32_t rbx_capsule_dw_split(void);
+int rbx_capsule_hat(const float* d_x, int64_t x_stride_b, int64_t x_stride_l, const float* d_w, int64_t batch,
+                    int32_t seq_len, int32_t dim, int32_t interests, float* d_hat, void* stream);
+int rbx_capsule_route_fwd(const float* d_hat, int64_t hat_stride_b, int64_t hat_stride_k, int64_t hat_stride_l,
+                          const void* d_mask, int32_t mask_dtype, int64_t mask_stride_b, int64_t mask_stride_l,
+                          const float* d_init, int64_t batch, int32_t interests, int32_t seq_len, int32_t dim,
+                          int32_t updates, float* d_v, float* d_c, float* d_s, void* stream);
+int rbx_capsule_route_bwd(const float* d_dv, const float* d_s, const float* d_c, int64_t batch, int32_t interests,
+                          int32_t seq_len, int32_t dim, int32_t shared, float* d_ds, float* d_dhat, void* stream);
+int rbx_capsule_bilinear_dx(const float* d_w, const float* d_g, int64_t g_stride_b, int64_t g_stride_l, const float* d_c,
+                            int64_t batch, int32_t seq_len, int32_t dim, int32_t interests, float* d_dx, void* stream);
+size_t rbx_capsule_bilinear_dw_workspace_size(int64_t batch, int32_t seq_len, int32_t dim, int32_t interests);
+int rbx_capsule_bilinear_dw(const float* d_x, int64_t x_stride_b, int64_t x_stride_l, const float* d_g, int64_t g_stride_b,
+                            int64_t g_stride_l, const float* d_c, int64_t batch, int32_t seq_len, int32_t dim,
+                            int32_t interests, float* d_dw, void* d_workspace, size_t workspace_bytes, void* stream);
 #ifdef __cplusplus
 }
 #endif

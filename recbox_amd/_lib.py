@@ -16,6 +16,7 @@ RBX_NO_ID = -(1 << 63)
 
 RBX_OK, RBX_ERR_INVALID, RBX_ERR_LAUNCH, RBX_ERR_WORKSPACE, RBX_ERR_UNSUPPORTED = 0, -1, -2, -3, -4
 RBX_I32, RBX_I64, RBX_F32, RBX_F64 = 0, 1, 2, 3
+RBX_MASK_U8 = 4                              # a bool / uint8 mask of rbx_capsule_route_fwd
 FIELD_CATEGORICAL, FIELD_NUMERIC, FIELD_DENSE = 0, 1, 2
 POOL_NONE, POOL_SUM, POOL_MEAN_VALUE, POOL_MEAN_ID, POOL_SUM_ID, POOL_CONCAT, POOL_MAX = 0, 1, 2, 3, 4, 5, 6
 INTERACTION_MODES = {"product_sum": 0, "bi_interaction": 1, "inner_product": 2, "elementwise_product": 3}
@@ -269,6 +270,15 @@ SIGNATURES = {
     "rbx_ffm_bwd_workspace_size": (_sz, [_FP, _i32, _i64]),
     "rbx_ffm_sort": (ctypes.c_int, [_FP, _i32, _i64, _P, _sz, _P, _P]),
     "rbx_ffm_bwd": (ctypes.c_int, [_FP, _i32, _i64, _i32, _P, _i64, _i32, _P, _sz, _P]),
+    "rbx_capsule_route_supported": (ctypes.c_int, [_i32, _i32]),
+    "rbx_capsule_dw_split": (_i32, []),
+    "rbx_capsule_hat": (ctypes.c_int, [_P, _i64, _i64, _P, _i64, _i32, _i32, _i32, _P, _P]),
+    "rbx_capsule_route_fwd": (ctypes.c_int, [_P, _i64, _i64, _i64, _P, _i32, _i64, _i64, _P, _i64, _i32, _i32, _i32, _i32, _P,
+                                             _P, _P, _P]),
+    "rbx_capsule_route_bwd": (ctypes.c_int, [_P, _P, _P, _i64, _i32, _i32, _i32, _i32, _P, _P, _P]),
+    "rbx_capsule_bilinear_dx": (ctypes.c_int, [_P, _P, _i64, _i64, _P, _i64, _i32, _i32, _i32, _P, _P]),
+    "rbx_capsule_bilinear_dw_workspace_size": (_sz, [_i64, _i32, _i32, _i32]),
+    "rbx_capsule_bilinear_dw": (ctypes.c_int, [_P, _i64, _i64, _P, _i64, _i64, _P, _i64, _i32, _i32, _i32, _P, _P, _sz, _P]),
 }
 
 

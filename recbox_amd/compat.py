@@ -86,7 +86,9 @@ _RECHUB = {
     "basic.initializers": ("recbox_amd.rechub.basic.initializers", None),
     "basic.layers": ("recbox_amd.rechub.basic.layers", None),
     "basic.activation": ("recbox_amd.rechub.basic.layers", ["Dice", "activation_layer"]),
-    "models.matching": ("recbox_amd.rechub.models.matching", ["DSSM", "YoutubeDNN", "SASRec"]),
+    "models.matching": ("recbox_amd.rechub.models.matching", ["DSSM", "YoutubeDNN", "SASRec", "MIND", "ComirecDR"]),
+    "models.matching.mind": ("recbox_amd.rechub.models.matching", ["MIND"]),
+    "models.matching.comirec": ("recbox_amd.rechub.models.matching", ["ComirecDR"]),
     "models.matching.dssm": ("recbox_amd.rechub.models.matching", ["DSSM"]),
     "models.matching.youtube_dnn": ("recbox_amd.rechub.models.matching", ["YoutubeDNN"]),
     "models.matching.sasrec": ("recbox_amd.rechub.models.matching", ["SASRec", "PointWiseFeedForward"]),

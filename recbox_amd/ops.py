@@ -4319,3 +4319,240 @@ def ffm_cross(tables, ids, reduce_sum=False):
     ids = [_id_column(t) for t in ids]
     train = torch.is_grad_enabled() and any(p.requires_grad for p in tables)   # grad mode is off inside forward()
     return _FfmCross.apply(len(ids), train, bool(reduce_sum), *ids, *tables)
+
+
+# ---- multi-interest dynamic routing: MIND / ComirecDR (csrc/rbx_capsule.hip) -----------------------------------------------
+CAPSULE_MAX_DIM, CAPSULE_MAX_INTERESTS = 128, 32
+CAPSULE_DW_SPLIT = int(lib.rbx_capsule_dw_split())       # samples per split of the bilinear dW reduction
+_MASK_CODE = {torch.int32: _lib.RBX_I32, torch.int64: _lib.RBX_I64, torch.float32: _lib.RBX_F32, torch.bool: _lib.RBX_MASK_U8,
+              torch.uint8: _lib.RBX_MASK_U8}
+
+
+def capsule_supported(seq_len, dim, interest_num, routing_times=3, dtype=torch.float32):
+    """Whether the capsule kernels take this shape (the refusals of rbx_capsule_*, decided on the host): fp32, ``dim`` a
+    multiple of 4 up to 128, 1 to 32 interests, an ``[L, D]`` slice the routing kernel holds on chip (L = 200 at D = 64 and
+    L = 50 at D = 128 are inside) and ``routing_times >= 1``.  What it refuses runs ``capsule_route_torch``."""
+    return bool(dtype == torch.float32 and dim % 4 == 0 and 4 <= dim <= CAPSULE_MAX_DIM and seq_len >= 1
+                and 1 <= interest_num <= CAPSULE_MAX_INTERESTS and routing_times >= 1
+                and lib.rbx_capsule_route_supported(int(seq_len), int(dim)))
+
+
+def capsule_route_torch(hat, mask, interest_num, routing_times=3, init=None, shared=False):
+    """The reference's routing loop (layers.py:598-643) as torch expressions, for what ``capsule_supported`` refuses (and as
+    the composition the kernels are measured against).  ``hat`` [B, L, K D], or [B, L, D] with ``shared``."""
+    B, L = hat.shape[0], hat.shape[1]
+    K = interest_num
+    if shared:
+        hat4 = hat.unsqueeze(1).expand(B, K, L, hat.shape[2])
+    else:
+        hat4 = hat.reshape(B, L, K, -1).transpose(1, 2)
+    hat_iter = hat4.detach()
+    logits = init if init is not None else torch.zeros(B, K, L, dtype=hat.dtype, device=hat.device)
+    keep = (mask.reshape(B, 1, L) != 0)
+    out = None
+    for i in range(routing_times):
+        c = torch.softmax(logits, dim=-1) * keep
+        src = hat_iter if i < 2 else hat4
+        s = torch.einsum("bkl,bkld->bkd", c, src)
+        n = (s * s).sum(-1, keepdim=True)
+        out = n / (1 + n) / torch.sqrt(n + 1e-9) * s
+        if i < 2:
+            logits = logits + torch.einsum("bkld,bkd->bkl", hat_iter, out)
+    return out
+
+
+def capsule_bilinear_torch(x, w):
+    """hat [B, L, K D] of the bilinear form as an einsum that never forms the [B, L, K D, D] product of layers.py:595-596."""
+    return torch.einsum("lnd,bld->bln", w.reshape(w.shape[-3], w.shape[-2], w.shape[-1])[:x.shape[1]], x)
+
+
+def _capsule_x(x):
+    """x [B, L, D] as rbx_capsule_hat / _dw read it: fp32, unit inner stride, 16-byte aligned, strides multiples of 4."""
+    if (x.dtype != torch.float32 or x.stride(2) != 1 or x.data_ptr() % 16 != 0
+            or (x.shape[0] > 1 and x.stride(0) % 4 != 0) or (x.shape[1] > 1 and x.stride(1) % 4 != 0)):
+        x = x.float().contiguous()
+    return x
+
+
+def _capsule_w(w, L, N, D):
+    _require_cuda(w, "capsule weight")
+    if w.numel() < L * N * D or w.shape[-1] != D or w.shape[-2] != N:
+        raise RuntimeError("capsule_bilinear: weight %s does not fit x [.., %d, %d] with %d outputs" % (tuple(w.shape), L, D, N))
+    return w.float().contiguous()         # [1, seq_len, N, D] or [seq_len, N, D]: the first L positions are the first L N D floats
+
+
+def _capsule_hat(x, w, K):
+    B, L, D = x.shape
+    hat = torch.empty((B, L, K * D), dtype=torch.float32, device=x.device)
+    check(_timed(("capsule_hat", B, L, K, D),
+                 lambda: lib.rbx_capsule_hat(_ptr(x), x.stride(0), x.stride(1), _ptr(w), B, L, D, K, _ptr(hat), _stream())))
+    return hat
+
+
+def _capsule_route_fwd(hat, mask, K, D, routing_times, init, shared):
+    B, L = hat.shape[0], hat.shape[1]
+    _require_cuda(mask, "capsule mask")
+    mask = mask.reshape(B, L)
+    if mask.dtype not in _MASK_CODE:
+        mask = mask.float() if mask.is_floating_point() else mask.long()
+    if init is not None:
+        _require_cuda(init, "capsule start logits")
+        init = init.detach().reshape(B, K, L).float().contiguous()
+    dev = hat.device
+    v = torch.empty((B, K, D), dtype=torch.float32, device=dev)
+    c = torch.empty((B, K, L), dtype=torch.float32, device=dev)
+    s = torch.empty((B, K, D), dtype=torch.float32, device=dev)
+    updates = min(routing_times - 1, 2)
+    check(_timed(("capsule_route_fwd", B, L, K, D),
+                 lambda: lib.rbx_capsule_route_fwd(_ptr(hat), hat.stride(0), 0 if shared else D, hat.stride(1), _ptr(mask),
+                                                   _MASK_CODE[mask.dtype], mask.stride(0), mask.stride(1), _ptr(init), B, K, L,
+                                                   D, updates, _ptr(v), _ptr(c), _ptr(s), _stream())))
+    return v, c, s
+
+
+def _capsule_check(what, L, D, K, routing_times):
+    if not capsule_supported(L, D, K, routing_times):
+        raise NotImplementedError("recbox_amd: %s has no kernel for seq_len=%d, dim=%d, interest_num=%d, routing_times=%d"
+                                  % (what, L, D, K, routing_times))
+
+
+class _CapsuleBilinear(torch.autograd.Function):
+    """hat [B, L, K D] = W_l x[:, l, :] (rbx_capsule_hat); backward = the two per-position GEMMs over the stored d_hat."""
+
+    @staticmethod
+    def forward(ctx, x, w):
+        _require_cuda(x, "capsule input")
+        x = _capsule_x(x)
+        B, L, D = x.shape
+        N = w.shape[-2]
+        w = _capsule_w(w, L, N, D)
+        ctx.save_for_backward(x, w)
+        ctx.w_shape = w.shape
+        return _capsule_hat(x, w, N // D)
+
+    @staticmethod
+    def backward(ctx, dhat):
+        x, w = ctx.saved_tensors
+        B, L, D = x.shape
+        N = w.shape[-2]
+        g = dhat.float().contiguous()
+        dx, dw = _capsule_bilinear_bwd(ctx, x, w, g, L * N, N, None, N // D)
+        return dx, dw
+
+
+def _capsule_bilinear_bwd(ctx, x, w, g, gs_b, gs_l, c, K):
+    B, L, D = x.shape
+    dev = x.device
+    dx = dw = None
+    if ctx.needs_input_grad[0]:
+        dx = torch.empty((B, L, D), dtype=torch.float32, device=dev)
+        check(_timed(("capsule_bilinear_dx", B, L, K, D),
+                     lambda: lib.rbx_capsule_bilinear_dx(_ptr(w), _ptr(g), gs_b, gs_l, _ptr(c), B, L, D, K, _ptr(dx),
+                                                         _stream())))
+    if ctx.needs_input_grad[1]:
+        dw = torch.empty(tuple(w.shape), dtype=torch.float32, device=dev)
+        if w.numel() > L * K * D * D:
+            dw.zero_()                                  # positions beyond L of a longer parameter
+        ws_bytes = lib.rbx_capsule_bilinear_dw_workspace_size(B, L, D, K)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+        check(_timed(("capsule_bilinear_dw", B, L, K, D),
+                     lambda: lib.rbx_capsule_bilinear_dw(_ptr(x), x.stride(0), x.stride(1), _ptr(g), gs_b, gs_l, _ptr(c), B, L,
+                                                         D, K, _ptr(dw), _ptr(ws), ws_bytes, _stream())))
+    return dx, dw
+
+
+def capsule_bilinear(x, w):
+    """The bilinear transform of ComirecDR's capsule layer: x [B, L, D], w [1, L, K D, D] (or [L, K D, D]) -> hat [B, L, K D]
+    with ``hat[b, l, n] = sum_d w[l, n, d] x[b, l, d]``; the [B, L, K D, D] product of the reference never exists.  Raises on
+    CPU tensors and (NotImplementedError) for a D the kernels do not serve."""
+    _require_cuda(x, "capsule input")
+    D = x.shape[2]
+    if x.dim() != 3 or D % 4 != 0 or not 4 <= D <= CAPSULE_MAX_DIM or w.shape[-2] % D != 0 \
+            or not 1 <= w.shape[-2] // D <= CAPSULE_MAX_INTERESTS:
+        raise NotImplementedError("recbox_amd: capsule_bilinear has no kernel for x %s, w %s" % (tuple(x.shape), tuple(w.shape)))
+    return _CapsuleBilinear.apply(x, w)
+
+
+class _CapsuleRoute(torch.autograd.Function):
+    """v [B, K, D] from hat by rbx_capsule_route_fwd; backward = rbx_capsule_route_bwd (d_hat = c ds in hat's layout)."""
+
+    @staticmethod
+    def forward(ctx, hat, mask, K, routing_times, init, shared):
+        h = hat if (hat.dtype == torch.float32 and hat.stride(2) == 1 and hat.data_ptr() % 16 == 0
+                    and hat.stride(0) % 4 == 0 and hat.stride(1) % 4 == 0) else hat.float().contiguous()
+        D = h.shape[2] if shared else h.shape[2] // K
+        v, c, s = _capsule_route_fwd(h, mask, K, D, routing_times, init, shared)
+        ctx.save_for_backward(c, s)
+        ctx.dims = (h.shape[0], h.shape[1], K, D, shared)
+        return v
+
+    @staticmethod
+    def backward(ctx, dv):
+        c, s = ctx.saved_tensors
+        B, L, K, D, shared = ctx.dims
+        dv = dv.float().contiguous()
+        dhat = torch.empty((B, L, D if shared else K * D), dtype=torch.float32, device=dv.device)
+        check(_timed(("capsule_route_bwd", B, L, K, D),
+                     lambda: lib.rbx_capsule_route_bwd(_ptr(dv), _ptr(s), _ptr(c), B, K, L, D, int(shared), None, _ptr(dhat),
+                                                       _stream())))
+        return dhat, None, None, None, None, None
+
+
+def capsule_route(hat, mask, interest_num, routing_times=3, init=None, shared=False):
+    """Dynamic routing of the capsule layer (B2I routing of MIND / ComirecDR): ``hat`` [B, L, K D] (or, with ``shared``, one
+    [B, L, D] block every interest reads), ``mask`` [B, L] (int64 / int32 / float32 / bool, 0 = padding), ``init`` the starting
+    logits [B, K, L] (None = zeros) -> interest capsules [B, K, D].  Gradients flow through the last of three iterations only,
+    as in the reference; with ``routing_times < 3`` the result comes from detached values and carries no gradient.  Raises on
+    CPU tensors and (NotImplementedError) for what ``capsule_supported`` refuses."""
+    _require_cuda(hat, "capsule hat")
+    K = int(interest_num)
+    D = hat.shape[2] if shared else hat.shape[2] // K
+    if hat.dim() != 3 or (not shared and hat.shape[2] != K * D):
+        raise RuntimeError("capsule_route: hat %s does not fit %d interests" % (tuple(hat.shape), K))
+    _capsule_check("capsule_route", hat.shape[1], D, K, routing_times)
+    if routing_times < 3:
+        with torch.no_grad():
+            return _CapsuleRoute.apply(hat, mask, K, routing_times, init, bool(shared))
+    return _CapsuleRoute.apply(hat, mask, K, routing_times, init, bool(shared))
+
+
+class _CapsuleBilinearRoute(torch.autograd.Function):
+    """capsule_bilinear + capsule_route as one node: hat lives only inside the forward, and the backward forms c ds inside the
+    dx / dW GEMMs -- no d_hat, no [B, L, K D, D]."""
+
+    @staticmethod
+    def forward(ctx, x, w, mask, K, routing_times):
+        x = _capsule_x(x)
+        B, L, D = x.shape
+        w = _capsule_w(w, L, K * D, D)
+        hat = _capsule_hat(x, w, K)
+        v, c, s = _capsule_route_fwd(hat, mask, K, D, routing_times, None, False)
+        ctx.save_for_backward(x, w, c, s)
+        ctx.K = K
+        return v
+
+    @staticmethod
+    def backward(ctx, dv):
+        x, w, c, s = ctx.saved_tensors
+        B, L, D = x.shape
+        K = ctx.K
+        dv = dv.float().contiguous()
+        ds = torch.empty((B, K, D), dtype=torch.float32, device=dv.device)
+        check(_timed(("capsule_route_bwd", B, L, K, D),
+                     lambda: lib.rbx_capsule_route_bwd(_ptr(dv), _ptr(s), None, B, K, L, D, 0, _ptr(ds), None, _stream())))
+        dx, dw = _capsule_bilinear_bwd(ctx, x, w, ds, K * D, 0, c, K)
+        return dx, dw, None, None, None
+
+
+def capsule_bilinear_route(x, w, mask, interest_num, routing_times=3):
+    """``capsule_route(capsule_bilinear(x, w), mask, interest_num, routing_times)`` (ComirecDR's capsule layer) as one autograd
+    node whose backward allocates neither d_hat nor the [B, L, K D, D] product."""
+    _require_cuda(x, "capsule input")
+    K = int(interest_num)
+    if x.dim() != 3 or w.shape[-2] != K * x.shape[2]:
+        raise RuntimeError("capsule_bilinear_route: x %s, w %s do not fit %d interests" % (tuple(x.shape), tuple(w.shape), K))
+    _capsule_check("capsule_bilinear_route", x.shape[1], x.shape[2], K, routing_times)
+    if routing_times < 3:
+        with torch.no_grad():
+            return _CapsuleBilinearRoute.apply(x, w, mask, K, routing_times)
+    return _CapsuleBilinearRoute.apply(x, w, mask, K, routing_times)

@@ -341,3 +341,69 @@ class CEN(nn.Module):
         else:
             aem = s.unsqueeze(-1) * em
         return aem.flatten(start_dim=1)
+
+
+class CapsuleNetwork(nn.Module):
+    """The dynamic-routing capsule layer of MIND (``bilinear_type`` 0) and ComirecDR (``bilinear_type`` 2), layers.py:553-648
+    of the reference: same constructor, parameter names (``linear.weight`` or ``w``, and the always-present
+    ``relu.0.weight``) and ``forward(item_eb [B, L, D], mask [B, L]) -> [B, interest_num, D]``.  Types 0 and 1 transform with
+    ``ops.linear``; type 2 with the per-position GEMMs of ``ops.capsule_bilinear_route``, so the ``[B, L, K D, D]`` product of
+    the reference exists in neither pass; the routing iterations run on chip in one launch (``ops.capsule_route``).  Type 0
+    draws its starting logits with exactly one ``torch.randn(B, K, L, device=...)`` call.
+
+    Deliberate deviations: ``stop_grad`` is fixed to True as in the reference and setting it to False raises
+    NotImplementedError at the next forward; the reference leaves ``w`` uninitialised (``torch.Tensor(...)``), here it is
+    filled with N(0, 0.01^2) so that no kernel ever reads uninitialised memory."""
+
+    def __init__(self, embedding_dim, seq_len, bilinear_type=2, interest_num=4, routing_times=3, relu_layer=False):
+        super(CapsuleNetwork, self).__init__()
+        self.embedding_dim = embedding_dim
+        self.seq_len = seq_len
+        self.bilinear_type = bilinear_type
+        self.interest_num = interest_num
+        self.routing_times = routing_times
+        self.relu_layer = relu_layer
+        self.stop_grad = True
+        self.relu = nn.Sequential(nn.Linear(self.embedding_dim, self.embedding_dim, bias=False), nn.ReLU())
+        if self.bilinear_type == 0:
+            self.linear = nn.Linear(self.embedding_dim, self.embedding_dim, bias=False)
+        elif self.bilinear_type == 1:
+            self.linear = nn.Linear(self.embedding_dim, self.embedding_dim * self.interest_num, bias=False)
+        else:
+            self.w = nn.Parameter(torch.empty(1, self.seq_len, self.interest_num * self.embedding_dim,
+                                              self.embedding_dim).normal_(0.0, 0.01))
+
+    def forward(self, item_eb, mask):
+        if not self.stop_grad:
+            raise NotImplementedError("CapsuleNetwork: stop_grad=False (gradients through every routing iteration) is not "
+                                      "implemented; the reference fixes it to True")
+        B, L, D = item_eb.shape[0], self.seq_len, self.embedding_dim
+        K, rt = self.interest_num, self.routing_times
+        mask = mask.reshape(B, L)
+        fused = ops.capsule_supported(L, D, K, rt, item_eb.dtype) and item_eb.is_cuda
+        if not item_eb.is_cuda:
+            ops._require_cuda(item_eb, "capsule input")
+        init = None
+        if self.bilinear_type == 0:
+            hat = ops.linear(item_eb, self.linear.weight)                       # [B, L, D], shared by the interests
+            init = torch.randn(B, K, L, device=item_eb.device)
+        elif self.bilinear_type == 1:
+            hat = ops.linear(item_eb, self.linear.weight)                       # [B, L, K D]
+        elif fused:
+            hat = None
+        else:
+            hat = ops.capsule_bilinear_torch(item_eb, self.w)
+        if rt < 1:
+            raise ValueError("CapsuleNetwork: routing_times=%d" % rt)
+        if fused:
+            if hat is None:
+                out = ops.capsule_bilinear_route(item_eb, self.w, mask, K, rt)
+            else:
+                out = ops.capsule_route(hat, mask, K, rt, init=init, shared=self.bilinear_type == 0)
+        else:
+            out = ops.capsule_route_torch(hat, mask, K, rt, init=init, shared=self.bilinear_type == 0)
+            if rt < 3:
+                out = out.detach()
+        if self.relu_layer:
+            out = ops.linear(out, self.relu[0].weight, act="relu")
+        return out

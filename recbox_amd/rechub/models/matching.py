@@ -10,7 +10,7 @@ import torch.nn as nn
 
 from ... import ops
 from ..basic.features import DenseFeature
-from ..basic.layers import MLP, EmbeddingLayer
+from ..basic.layers import MLP, CapsuleNetwork, EmbeddingLayer
 
 
 class DSSM(torch.nn.Module):
@@ -259,3 +259,76 @@ def ops_position(position_emb, positions):
         position_emb._rbx_plan = plan
     out = plan.run([positions])
     return out.view(positions.shape[0], L, position_emb.embedding_dim)
+
+
+class _MultiInterestDR(torch.nn.Module):
+    """What MIND and ComirecDR share (mind.py:32-101, comirec.py:118-188): a capsule layer over the history gives
+    ``interest_num`` vectors per user; training scores the interest that fits the positive item best."""
+    bilinear_type = 2
+
+    def __init__(self, user_features, history_features, item_features, neg_item_feature, max_length, temperature=1.0,
+                 interest_num=4):
+        super().__init__()
+        self.user_features = user_features
+        self.item_features = item_features
+        self.history_features = history_features
+        self.neg_item_feature = neg_item_feature
+        self.temperature = temperature
+        self.interest_num = interest_num
+        self.max_length = max_length
+        self.user_dims = sum([fea.embed_dim for fea in user_features + history_features])
+        self.embedding = EmbeddingLayer(user_features + item_features + history_features)
+        self.capsule = CapsuleNetwork(self.history_features[0].embed_dim, self.max_length, bilinear_type=self.bilinear_type,
+                                      interest_num=self.interest_num)
+        self.convert_user_weight = nn.Parameter(torch.rand(self.user_dims, self.history_features[0].embed_dim),
+                                                requires_grad=True)
+        self.mode = None
+
+    def forward(self, x):
+        user_embedding = self.user_tower(x)
+        item_embedding = self.item_tower(x)
+        if self.mode == "user":
+            return user_embedding
+        if self.mode == "item":
+            return item_embedding
+        # the interest with the largest inner product with the positive item: one argmax + gather instead of the reference's
+        # Python loop over the batch (mind.py:57-62)
+        pos = item_embedding[:, 0, :]
+        k_index = torch.argmax(torch.bmm(user_embedding.detach(), pos.detach().unsqueeze(-1)), dim=1)      # [B, 1]
+        best = torch.gather(user_embedding, 1, k_index.unsqueeze(-1).expand(-1, 1, user_embedding.shape[2]))
+        return torch.mul(best, item_embedding).sum(dim=1)                                                  # [B, D], as written
+
+    def user_tower(self, x):
+        if self.mode == "item":
+            return None
+        input_user = self.embedding(x, self.user_features, squeeze_dim=True).unsqueeze(1)
+        input_user = input_user.expand([input_user.shape[0], self.interest_num, input_user.shape[-1]])
+        history_emb = self.embedding(x, self.history_features).squeeze(1)                                  # [B, L, D]
+        multi_interest_emb = self.capsule(history_emb, self.gen_mask(x))                                   # [B, K, D]
+        input_user = torch.cat([input_user, multi_interest_emb], dim=-1)
+        user_embedding = ops.linear(input_user, self.convert_user_weight.t())
+        return ops.l2_normalize(user_embedding)                                                            # [B, K, D]
+
+    def item_tower(self, x):
+        if self.mode == "user":
+            return None
+        pos_embedding = ops.l2_normalize(self.embedding(x, self.item_features, squeeze_dim=False))         # [B, 1, D]
+        if self.mode == "item":
+            return pos_embedding.squeeze(1)
+        neg_embeddings = ops.l2_normalize(self.embedding(x, self.neg_item_feature, squeeze_dim=False).squeeze(1))
+        return torch.cat((pos_embedding, neg_embeddings), dim=1)                                           # [B, 1 + n_neg, D]
+
+    def gen_mask(self, x):
+        his_list = x[self.history_features[0].name]
+        return (his_list > 0).long()
+
+
+class MIND(_MultiInterestDR):
+    """``torch_rechub.models.matching.MIND`` (mind.py:17-101): ``CapsuleNetwork(bilinear_type=0)``, whose starting logits are
+    drawn with one ``torch.randn`` per forward."""
+    bilinear_type = 0
+
+
+class ComirecDR(_MultiInterestDR):
+    """``torch_rechub.models.matching.ComirecDR`` (comirec.py:103-188): ``CapsuleNetwork(bilinear_type=2)``."""
+    bilinear_type = 2
