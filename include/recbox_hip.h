@@ -1169,6 +1169,33 @@ size_t rbx_capsule_bilinear_dw_workspace_size(int64_t batch, int32_t seq_len, in
 int rbx_capsule_bilinear_dw(const float* d_x, int64_t x_stride_b, int64_t x_stride_l, const float* d_g, int64_t g_stride_b,
                             int64_t g_stride_l, const float* d_c, int64_t batch, int32_t seq_len, int32_t dim,
                             int32_t interests, float* d_dw, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ---- GRU recurrence: GRU4Rec, NARM (csrc/rbx_gru.hip; additions only, the version stays) ----------------------------------
+ * Replaces torch.nn.GRU under third_party/rechub/models/matching/gru4rec.py:40-44, 66-67 and narm.py:30, 50-55 (there with
+ * pack_padded_sequence / pad_packed_sequence around it, whose lengths narm.py:49 copies to the host).  B = batch, L = seq_len,
+ * H = hidden.  torch's gate convention: rows of d_w_hh [3H, H] (contiguous) and d_b_hh [3H] (NULL: none) are ordered r, z, n;
+ *   gh = h W_hh^T + b_hh   r = s(gi_r + gh_r)   z = s(gi_z + gh_z)   n = tanh(gi_n + r gh_n)   h' = (1 - z) n + z h.
+ * gi = x W_ih^T + b_ih comes from rbx_linear_fwd and is read at gi[b gi_stride_b + t gi_stride_t + c], c < 3H.
+ *   rbx_gru_fwd   one launch for all L steps: a workgroup owns 16 samples, gh runs on v_mfma_f32_16x16x4_f32 against W_hh held
+ *                 in registers, h stays on chip.  d_h0 [B, H] (NULL: zeros).  d_lengths [B] (RBX_I32 / RBX_I64; NULL: all L),
+ *                 clamped to [0, L]: for t >= lengths[b] the state is frozen and d_out[b, t, :] = 0; d_hn[b] is the state after
+ *                 step lengths[b] - 1 (length 0: h0).  Writes d_out [B, L, H], d_hn [B, H] and, for the backward,
+ *                 d_saved [B, L, 5, H] = r, z, n, gh_n, h_prev of every position (h_prev is also the x operand of dW_hh).
+ *   rbx_gru_bwd   one launch, t = L-1 .. 0 with dh on chip.  d_dout (NULL: none) is read at
+ *                 dout[b dout_stride_b + t dout_stride_t + j]; d_dhn [B, H] (NULL: none).  Writes d_dgi [B, L, 3H] (the
+ *                 gradient of gi), d_dghn [B, L, H] = d_gi_n r (the n-gate columns in which the gradient of gh differs from
+ *                 d_dgi) and d_dh0 [B, H]; positions at and beyond a sample's length get zeros.
+ * dW_ih, dx, dW_hh and the bias gradients are rbx_linear_bwd calls over these matrices.
+ * Supported (rbx_gru_supported): H a multiple of 4 in [4, 128], L >= 1; dtype (the RBX_* code of every float tensor) must be
+ * RBX_F32; gi and d_dout 16-byte aligned with strides that are multiples of 4.  Anything else: RBX_ERR_UNSUPPORTED before any
+ * launch.  batch = 0 launches nothing.  No atomics, sums in a fixed order; no call allocates or reads back: capturable. */
+int rbx_gru_supported(int32_t hidden, int32_t seq_len);
+int rbx_gru_fwd(const float* d_gi, int64_t gi_stride_b, int64_t gi_stride_t, const float* d_w_hh, const float* d_b_hh,
+                const float* d_h0, const void* d_lengths, int32_t lengths_dtype, int64_t batch, int32_t seq_len,
+                int32_t hidden, int32_t dtype, float* d_out, float* d_saved, float* d_hn, void* stream);
+int rbx_gru_bwd(const float* d_saved, const float* d_w_hh, const float* d_dout, int64_t dout_stride_b, int64_t dout_stride_t,
+                const float* d_dhn, const void* d_lengths, int32_t lengths_dtype, int64_t batch, int32_t seq_len,
+                int32_t hidden, int32_t dtype, float* d_dgi, float* d_dghn, float* d_dh0, void* stream);
 #ifdef __cplusplus
 }
 #endif

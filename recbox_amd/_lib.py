@@ -279,6 +279,9 @@ SIGNATURES = {
     "rbx_capsule_bilinear_dx": (ctypes.c_int, [_P, _P, _i64, _i64, _P, _i64, _i32, _i32, _i32, _P, _P]),
     "rbx_capsule_bilinear_dw_workspace_size": (_sz, [_i64, _i32, _i32, _i32]),
     "rbx_capsule_bilinear_dw": (ctypes.c_int, [_P, _i64, _i64, _P, _i64, _i64, _P, _i64, _i32, _i32, _i32, _P, _P, _sz, _P]),
+    "rbx_gru_supported": (ctypes.c_int, [_i32, _i32]),
+    "rbx_gru_fwd": (ctypes.c_int, [_P, _i64, _i64, _P, _P, _P, _P, _i32, _i64, _i32, _i32, _i32, _P, _P, _P, _P]),
+    "rbx_gru_bwd": (ctypes.c_int, [_P, _P, _P, _i64, _i64, _P, _P, _i32, _i64, _i32, _i32, _i32, _P, _P, _P, _P]),
 }
 
 

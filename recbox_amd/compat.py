@@ -86,7 +86,10 @@ _RECHUB = {
     "basic.initializers": ("recbox_amd.rechub.basic.initializers", None),
     "basic.layers": ("recbox_amd.rechub.basic.layers", None),
     "basic.activation": ("recbox_amd.rechub.basic.layers", ["Dice", "activation_layer"]),
-    "models.matching": ("recbox_amd.rechub.models.matching", ["DSSM", "YoutubeDNN", "SASRec", "MIND", "ComirecDR"]),
+    "models.matching": ("recbox_amd.rechub.models.matching", ["DSSM", "YoutubeDNN", "SASRec", "MIND", "ComirecDR", "GRU4Rec",
+                                                              "NARM"]),
+    "models.matching.gru4rec": ("recbox_amd.rechub.models.matching", ["GRU4Rec"]),
+    "models.matching.narm": ("recbox_amd.rechub.models.matching", ["NARM"]),
     "models.matching.mind": ("recbox_amd.rechub.models.matching", ["MIND"]),
     "models.matching.comirec": ("recbox_amd.rechub.models.matching", ["ComirecDR"]),
     "models.matching.dssm": ("recbox_amd.rechub.models.matching", ["DSSM"]),

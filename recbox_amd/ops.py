@@ -117,6 +117,12 @@ class config(object):
     # multiply, and autograd's two copies of that tensor.  Off, or for a shape ffm_supported refuses: that composition.
     # Measurements: profiles/ffm/INDEX.md.
     ffm_fused = os.environ.get("RECBOX_AMD_FFM_FUSED", "1") != "0"
+    # GRU layers (rechub's GRU4Rec / NARM): the recurrence of a layer as one launch forward and one backward with W_hh in
+    # registers and h on chip (gru: csrc/rbx_gru.hip) instead of a Python loop over t of a [B, H] x [H, 3H] GEMM and six
+    # element-wise kernels.  Off, or for what gru_supported refuses: that loop (gru_torch).  Forward + backward against the loop
+    # (profiles/gru/INDEX.md): 51 x / 24 x / 16 x at B = 4096, 12 x / 12 x / 9 x at B = 65 536 (H = 16 / 64 / 128, L = 50, two layers),
+    # 23 x at NARM's form (B = 512, L = 20, H = 100): no shape class loses, so there is no width threshold.
+    gru_fused = os.environ.get("RECBOX_AMD_GRU_FUSED", "1") != "0"
 
 
 def _require_cuda(t, what):
@@ -4556,3 +4562,157 @@ def capsule_bilinear_route(x, w, mask, interest_num, routing_times=3):
         with torch.no_grad():
             return _CapsuleBilinearRoute.apply(x, w, mask, K, routing_times)
     return _CapsuleBilinearRoute.apply(x, w, mask, K, routing_times)
+
+
+# ---- GRU recurrence: GRU4Rec / NARM (csrc/rbx_gru.hip) ---------------------------------------------------------------------
+GRU_MAX_HIDDEN = 128
+_GRU_SAVED = 5                 # r, z, n, gh_n, h_prev per position (rbx_gru_fwd's d_saved)
+
+
+def gru_supported(hidden, seq_len):
+    """Whether the fused recurrence takes this shape (rbx_gru_supported): ``hidden`` a multiple of 4 in 4 .. 128, ``seq_len``
+    >= 1.  What it refuses runs ``gru_torch``."""
+    return bool(lib.rbx_gru_supported(int(hidden), int(seq_len)))
+
+
+def _gru_lengths(lengths, B, device):
+    if lengths is None:
+        return None
+    _require_cuda(lengths, "gru lengths")
+    if lengths.dtype not in (torch.int32, torch.int64):
+        lengths = lengths.long()
+    return lengths.reshape(B).contiguous()
+
+
+def gru_torch(x, w_ih, w_hh, b_ih=None, b_hh=None, h0=None, lengths=None):
+    """The step-loop composition: ``ops.linear`` for the input projection of all positions and for ``h W_hh^T`` of every step,
+    ATen for the gates.  Serves what ``gru_supported`` refuses and is what the fused op is measured against.  Same semantics
+    as ``gru`` (``lengths`` read on the device: no packing, no host copy)."""
+    _require_cuda(x, "gru input")
+    B, L, _ = x.shape
+    H = w_hh.shape[1]
+    x, w_ih, w_hh = x.float(), w_ih.float(), w_hh.float()
+    gi = linear(x, w_ih, b_ih)                                                  # [B, L, 3H]
+    h = h0.float() if h0 is not None else torch.zeros(B, H, dtype=torch.float32, device=x.device)
+    lengths = _gru_lengths(lengths, B, x.device)
+    outs = []
+    for t in range(L):
+        gh = linear(h, w_hh, b_hh)
+        g = gi[:, t]
+        r = torch.sigmoid(g[:, :H] + gh[:, :H])
+        z = torch.sigmoid(g[:, H:2 * H] + gh[:, H:2 * H])
+        n = torch.tanh(g[:, 2 * H:] + r * gh[:, 2 * H:])
+        hnew = (1 - z) * n + z * h
+        if lengths is not None:
+            act = (lengths > t).unsqueeze(1)
+            h = torch.where(act, hnew, h)
+            outs.append(torch.where(act, hnew, torch.zeros_like(hnew)))
+        else:
+            h = hnew
+            outs.append(hnew)
+    return torch.stack(outs, dim=1), h
+
+
+def _gru_fused_ok(x, w_ih, w_hh, b_ih, b_hh, h0):
+    """The refusals of ``gru`` that run the composition: a hidden width outside the kernels' range, non-float32 tensors, an
+    input that is a strided view or whose base is not 16-byte aligned."""
+    if not config.gru_fused or x.dim() != 3 or not gru_supported(w_hh.shape[1], x.shape[1]):
+        return False
+    if any(t is not None and t.dtype != torch.float32 for t in (x, w_ih, w_hh, b_ih, b_hh, h0)):
+        return False
+    return x.is_contiguous() and x.data_ptr() % 16 == 0
+
+
+class _Gru(torch.autograd.Function):
+    """(out [B, L, H], h_n [B, H]) of one GRU layer: the input projection on the dense path, the recurrence as ONE launch
+    (rbx_gru_fwd); backward = ONE launch (rbx_gru_bwd) for d_gi / d_gh_n / d_h0, then the dense path's GEMMs for dx, dW_ih,
+    dW_hh and the bias gradients."""
+
+    @staticmethod
+    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, h0, lengths):
+        B, L, I = x.shape
+        H = w_hh.shape[1]
+        dev = x.device
+        x2 = x.reshape(B * L, I)
+        w_ih, w_hh = w_ih.contiguous(), w_hh.contiguous()
+        gi = _lin_fwd(x2, w_ih, b_ih.contiguous() if b_ih is not None else None)          # [B L, 3H]
+        out = torch.empty((B, L, H), dtype=torch.float32, device=dev)
+        hn = torch.empty((B, H), dtype=torch.float32, device=dev)
+        saved = torch.empty((B, L, _GRU_SAVED * H), dtype=torch.float32, device=dev)
+        b_hh = b_hh.contiguous() if b_hh is not None else None
+        h0 = h0.contiguous() if h0 is not None else None
+        check(_timed(("gru_fwd", B, L, H),
+                     lambda: lib.rbx_gru_fwd(_ptr(gi), L * 3 * H, 3 * H, _ptr(w_hh), _ptr(b_hh), _ptr(h0), _ptr(lengths),
+                                             _DTYPE_CODE[lengths.dtype] if lengths is not None else 0, B, L, H, _lib.RBX_F32,
+                                             _ptr(out), _ptr(saved), _ptr(hn), _stream())))
+        ctx.save_for_backward(x2, w_ih, w_hh, saved, lengths)
+        ctx.dims = (B, L, I, H)
+        ctx.has_bias = (b_ih is not None, b_hh is not None)
+        ctx.has_h0 = h0 is not None
+        ctx.set_materialize_grads(False)
+        return out, hn
+
+    @staticmethod
+    def backward(ctx, d_out, d_hn):
+        x2, w_ih, w_hh, saved, lengths = ctx.saved_tensors
+        B, L, I, H = ctx.dims
+        dev = x2.device
+        M = B * L
+        if d_out is not None:
+            d_out = d_out.float()
+            if d_out.stride(2) != 1 or d_out.data_ptr() % 16 != 0 or d_out.stride(0) % 4 != 0 or d_out.stride(1) % 4 != 0:
+                d_out = d_out.contiguous()
+        d_hn = d_hn.float().contiguous() if d_hn is not None else None
+        dgi = torch.empty((M, 3 * H), dtype=torch.float32, device=dev)
+        dghn = torch.empty((M, H), dtype=torch.float32, device=dev)
+        dh0 = torch.empty((B, H), dtype=torch.float32, device=dev)
+        check(_timed(("gru_bwd", B, L, H),
+                     lambda: lib.rbx_gru_bwd(_ptr(saved), _ptr(w_hh), _ptr(d_out),
+                                             d_out.stride(0) if d_out is not None else L * H,
+                                             d_out.stride(1) if d_out is not None else H, _ptr(d_hn), _ptr(lengths),
+                                             _DTYPE_CODE[lengths.dtype] if lengths is not None else 0, B, L, H, _lib.RBX_F32,
+                                             _ptr(dgi), _ptr(dghn), _ptr(dh0), _stream())))
+        need = ctx.needs_input_grad
+        dx = _lin_dx(dgi, w_ih).view(B, L, I) if need[0] else None
+        dw_ih = db_ih = dw_hh = db_hh = None
+        want_bih, want_bhh = ctx.has_bias[0] and need[3], ctx.has_bias[1] and need[4]
+        if need[1] or want_bih or want_bhh:
+            dw_ih = torch.empty((3 * H, I), dtype=torch.float32, device=dev)
+            db_ih = torch.empty(3 * H, dtype=torch.float32, device=dev)
+            _lin_dwdb(x2, w_ih, dgi, dw_ih, db_ih)
+        if need[2] or want_bhh:
+            # h_prev of every position is a column block of the saved rows (row stride 5H).  Rows r, z of dW_hh are rows of
+            # d_gi^T h_prev; the n rows come from d_gh_n^T h_prev (the first product's n rows are not used)
+            hp = saved.view(M, _GRU_SAVED * H)[:, 4 * H:]
+            g_all = torch.empty((3 * H, H), dtype=torch.float32, device=dev)
+            g_n = torch.empty((H, H), dtype=torch.float32, device=dev)
+            db_n = torch.empty(H, dtype=torch.float32, device=dev)
+            _lin_dwdb(hp, w_hh, dgi, g_all, None)
+            _lin_dwdb(hp, w_hh, dghn, g_n, db_n)
+            dw_hh = torch.cat([g_all[:2 * H], g_n], dim=0)
+            if want_bhh:
+                db_hh = torch.cat([db_ih[:2 * H], db_n], dim=0)
+        return (dx, dw_ih if need[1] else None, dw_hh if need[2] else None, db_ih if want_bih else None, db_hh,
+                dh0 if (ctx.has_h0 and need[5]) else None, None)
+
+
+def gru(x, w_ih, w_hh, b_ih=None, b_hh=None, h0=None, lengths=None):
+    """One GRU layer over ``x`` [B, L, I] (batch first) with torch's parameters ``w_ih`` [3H, I], ``w_hh`` [3H, H], ``b_ih`` /
+    ``b_hh`` [3H] (rows ordered r, z, n) -> ``(out [B, L, H], h_n [B, H])``, one autograd node.  ``h0`` [B, H] (None = zeros).
+    ``lengths`` [B] (int32 / int64, on the device, None = all L) gives packed-sequence semantics without packing: for
+    ``t >= lengths[b]`` the state is frozen and ``out[b, t] = 0``, ``h_n[b]`` is the state after step ``lengths[b] - 1``;
+    ``lengths[b] = 0`` gives ``h_n[b] = h0[b]`` and a zero row.  Raises on CPU tensors; a shape or layout the kernels refuse
+    (``gru_supported``, non-float32, oddly strided input) and ``config.gru_fused = False`` run ``gru_torch``."""
+    _require_cuda(x, "gru input")
+    _require_cuda(w_ih, "gru weight_ih")
+    _require_cuda(w_hh, "gru weight_hh")
+    if x.dim() != 3 or w_ih.shape[0] != w_hh.shape[0] or w_hh.shape[0] != 3 * w_hh.shape[1] or w_ih.shape[1] != x.shape[2]:
+        raise RuntimeError("gru: x %s, weight_ih %s, weight_hh %s do not fit" % (tuple(x.shape), tuple(w_ih.shape),
+                                                                                tuple(w_hh.shape)))
+    B = x.shape[0]
+    if h0 is not None:
+        _require_cuda(h0, "gru h0")
+        h0 = h0.reshape(B, w_hh.shape[1])
+    if B == 0 or not _gru_fused_ok(x, w_ih, w_hh, b_ih, b_hh, h0):
+        return gru_torch(x, w_ih, w_hh, b_ih, b_hh, h0, lengths)
+    return _Gru.apply(x, w_ih, w_hh, b_ih, b_hh, h0, _gru_lengths(lengths, B, x.device))

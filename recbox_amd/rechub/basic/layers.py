@@ -407,3 +407,45 @@ class CapsuleNetwork(nn.Module):
         if self.relu_layer:
             out = ops.linear(out, self.relu[0].weight, act="relu")
         return out
+
+
+class GRU(nn.Module):
+    """What GRU4Rec (gru4rec.py:40-44) and NARM (narm.py:30) use of ``torch.nn.GRU``: ``input_size``, ``hidden_size``,
+    ``num_layers``, ``bias``, ``batch_first``, with torch's parameter names (``weight_ih_l{k}``, ``weight_hh_l{k}``,
+    ``bias_ih_l{k}``, ``bias_hh_l{k}``), shapes, gate order (r, z, n) and U(-1/sqrt(H), 1/sqrt(H)) init, so a reference
+    checkpoint loads unchanged.  Each layer is one ``ops.gru`` call (input projection on the dense path, the recurrence as one
+    launch).  ``forward(x, h0=None, lengths=None) -> (out, h_n [num_layers, B, H])``; ``lengths`` [B] (on the device) stands in
+    for ``pack_padded_sequence`` / ``pad_packed_sequence``: positions at and beyond a sample's length are 0 in ``out`` and
+    ``h_n`` is the state after its last valid step.  ``bidirectional``, ``dropout > 0`` and ``proj_size`` are not implemented."""
+
+    def __init__(self, input_size, hidden_size, num_layers=1, bias=True, batch_first=False, dropout=0.0, bidirectional=False,
+                 proj_size=0):
+        super(GRU, self).__init__()
+        if bidirectional or dropout > 0 or proj_size != 0:
+            raise NotImplementedError("GRU: bidirectional, dropout > 0 and proj_size are not implemented")
+        self.input_size, self.hidden_size, self.num_layers = input_size, hidden_size, num_layers
+        self.bias, self.batch_first = bias, batch_first
+        self.dropout, self.bidirectional, self.proj_size = 0.0, False, 0
+        bound = 1.0 / hidden_size ** 0.5 if hidden_size > 0 else 0.0
+        for k in range(num_layers):
+            shapes = [("weight_ih_l%d" % k, (3 * hidden_size, input_size if k == 0 else hidden_size)),
+                      ("weight_hh_l%d" % k, (3 * hidden_size, hidden_size))]
+            if bias:
+                shapes += [("bias_ih_l%d" % k, (3 * hidden_size,)), ("bias_hh_l%d" % k, (3 * hidden_size,))]
+            for name, shape in shapes:
+                setattr(self, name, nn.Parameter(torch.empty(*shape).uniform_(-bound, bound)))
+
+    def forward(self, x, h0=None, lengths=None):
+        if x.dim() != 3:
+            raise NotImplementedError("GRU: the input must be [B, L, I] (batch_first) or [L, B, I]; packed and unbatched "
+                                      "inputs are not implemented -- pass `lengths`")
+        if not self.batch_first:
+            x = x.transpose(0, 1).contiguous()
+        finals = []
+        for k in range(self.num_layers):
+            x, h_n = ops.gru(x, getattr(self, "weight_ih_l%d" % k), getattr(self, "weight_hh_l%d" % k),
+                             getattr(self, "bias_ih_l%d" % k) if self.bias else None,
+                             getattr(self, "bias_hh_l%d" % k) if self.bias else None,
+                             h0[k] if h0 is not None else None, lengths)
+            finals.append(h_n)
+        return (x if self.batch_first else x.transpose(0, 1)), torch.stack(finals, dim=0)

@@ -10,7 +10,7 @@ import torch.nn as nn
 
 from ... import ops
 from ..basic.features import DenseFeature
-from ..basic.layers import MLP, CapsuleNetwork, EmbeddingLayer
+from ..basic.layers import GRU, MLP, CapsuleNetwork, EmbeddingLayer
 
 
 class DSSM(torch.nn.Module):
@@ -332,3 +332,98 @@ class MIND(_MultiInterestDR):
 class ComirecDR(_MultiInterestDR):
     """``torch_rechub.models.matching.ComirecDR`` (comirec.py:103-188): ``CapsuleNetwork(bilinear_type=2)``."""
     bilinear_type = 2
+
+
+class GRU4Rec(torch.nn.Module):
+    """``torch_rechub.models.matching.GRU4Rec`` (gru4rec.py:16-87): the history runs through a bias-free stacked GRU
+    (``user_params['num_layers']``, default 2) whose last layer's final state joins the user features in front of the user
+    tower.  Same constructor, ``mode`` protocol and parameter names (``embedding.*``, ``gru.weight_*_l{k}``, ``user_mlp.*``);
+    each GRU layer is one ``ops.gru`` call."""
+
+    def __init__(self, user_features, history_features, item_features, neg_item_feature, user_params, temperature=1.0):
+        super().__init__()
+        self.user_features = user_features
+        self.item_features = item_features
+        self.history_features = history_features
+        self.neg_item_feature = neg_item_feature
+        self.temperature = temperature
+        self.user_dims = sum([fea.embed_dim for fea in user_features + history_features])
+        self.embedding = EmbeddingLayer(user_features + item_features + history_features)
+        self.gru = GRU(input_size=history_features[0].embed_dim, hidden_size=history_features[0].embed_dim,
+                       num_layers=user_params.get('num_layers', 2), batch_first=True, bias=False)
+        self.user_mlp = MLP(self.user_dims, output_layer=False, **user_params)
+        self.mode = None
+
+    def forward(self, x):
+        user_embedding = self.user_tower(x)
+        item_embedding = self.item_tower(x)
+        if self.mode == "user":
+            return user_embedding
+        if self.mode == "item":
+            return item_embedding
+        return torch.mul(user_embedding, item_embedding).sum(dim=1)                          # [B, D], as written
+
+    def user_tower(self, x):
+        if self.mode == "item":
+            return None
+        input_user = self.embedding(x, self.user_features, squeeze_dim=True)
+        history_emb = self.embedding(x, self.history_features).squeeze(1)                    # [B, L, D]
+        _, h_n = self.gru(history_emb)
+        input_user = torch.cat([input_user, h_n[-1]], dim=-1)
+        user_embedding = ops.l2_normalize(self.user_mlp(input_user).unsqueeze(1))            # [B, 1, D]
+        if self.mode == "user":
+            return user_embedding.squeeze(1)
+        return user_embedding
+
+    def item_tower(self, x):
+        if self.mode == "user":
+            return None
+        pos_embedding = ops.l2_normalize(self.embedding(x, self.item_features, squeeze_dim=False))         # [B, 1, D]
+        if self.mode == "item":
+            return pos_embedding.squeeze(1)
+        neg_embeddings = ops.l2_normalize(self.embedding(x, self.neg_item_feature, squeeze_dim=False).squeeze(1))
+        return torch.cat((pos_embedding, neg_embeddings), dim=1)                                           # [B, 1 + n_neg, D]
+
+
+class NARM(torch.nn.Module):
+    """``torch_rechub.models.matching.NARM`` (narm.py:18-76): same constructor and ``state_dict`` keys (``item_emb.weight``,
+    ``gru.*``, ``a_1``, ``a_2``, ``v``, ``b``).  The session lengths (non-zero ids per row; sessions are left-aligned) are
+    counted on the device and handed to ``ops.gru`` as ``lengths``: no packing and no host copy (narm.py:49-50), so a step is
+    capturable.  The reference's additive attention broadcasts the last state against the padded states in a way that needs
+    one full-length session per batch; for every such batch the outputs agree.  The attention (Eq. 6-8) and the bilinear
+    scoring (Eq. 10) are ATen and ``ops.linear``; dropout is ``ops.dropout`` (its Philox mask differs from torch's)."""
+
+    def __init__(self, item_history_feature, hidden_dim, emb_dropout_p, session_rep_dropout_p):
+        super(NARM, self).__init__()
+        self.item_history_feature = item_history_feature
+        self.item_emb = nn.Embedding(item_history_feature.vocab_size, item_history_feature.embed_dim, padding_idx=0)
+        self.emb_dropout = nn.Dropout(emb_dropout_p)
+        self.gru = GRU(input_size=item_history_feature.embed_dim, hidden_size=hidden_dim)
+        self.a_1, self.a_2 = nn.Parameter(torch.randn(hidden_dim, hidden_dim)), nn.Parameter(torch.randn(hidden_dim, hidden_dim))
+        self.v = nn.Parameter(torch.randn(hidden_dim, 1))
+        self.session_rep_dropout = nn.Dropout(session_rep_dropout_p)
+        self.b = nn.Parameter(torch.randn(item_history_feature.embed_dim, hidden_dim * 2))
+
+    def _drop(self, layer, x):
+        return ops.dropout(x, layer.p, True) if (self.training and layer.p > 0) else x
+
+    def forward(self, input_dict):
+        ids = input_dict[self.item_history_feature.name]
+        ops._require_cuda(ids, "NARM input")
+        value_mask = (ids != 0)
+        lengths = value_mask.sum(dim=1)                                                      # stays on the device
+        embs = self._drop(self.emb_dropout, ops_position(self.item_emb, ids))                # [B, L, E]
+        # Eq. 1-4: hidden states of every step; positions beyond a session's length are 0, as pad_packed_sequence leaves them
+        h, h_t = ops.gru(embs, self.gru.weight_ih_l0, self.gru.weight_hh_l0, self.gru.bias_ih_l0, self.gru.bias_hh_l0,
+                         None, lengths)
+        c_g = h_t                                                                            # Eq. 5 [B, H]
+        # Eq. 8: similarity between the final state and every state
+        q = ops.linear(torch.sigmoid(ops.linear(h_t, self.a_1).unsqueeze(1) + ops.linear(h, self.a_2)), self.v.t())
+        # Eq. 7
+        alpha = torch.exp(q) * value_mask.unsqueeze(-1)
+        alpha = alpha / alpha.sum(dim=1, keepdim=True)
+        c_l = (alpha * h).sum(1)                                                             # Eq. 6
+        c = self._drop(self.session_rep_dropout, torch.cat((c_g, c_l), dim=1))               # Eq. 9
+        # Eq. 10 [B, V].  The table is also read by the lookup above, so autograd adds two gradients for it on the current stream:
+        # it goes in as a view (not a leaf), which keeps this Linear's dW off the side stream (ops.config.dw_beside_lookup)
+        return ops.linear(ops.linear(c, self.b), self.item_emb.weight.view_as(self.item_emb.weight))
