@@ -87,7 +87,8 @@ _RECHUB = {
     "basic.layers": ("recbox_amd.rechub.basic.layers", None),
     "basic.activation": ("recbox_amd.rechub.basic.layers", ["Dice", "activation_layer"]),
     "models.matching": ("recbox_amd.rechub.models.matching", ["DSSM", "YoutubeDNN", "SASRec", "MIND", "ComirecDR", "GRU4Rec",
-                                                              "NARM"]),
+                                                              "NARM", "ComirecSA", "SINE"]),
+    "models.matching.sine": ("recbox_amd.rechub.models.matching", ["SINE"]),
     "models.matching.gru4rec": ("recbox_amd.rechub.models.matching", ["GRU4Rec"]),
     "models.matching.narm": ("recbox_amd.rechub.models.matching", ["NARM"]),
     "models.matching.mind": ("recbox_amd.rechub.models.matching", ["MIND"]),
@@ -102,8 +103,20 @@ _RECHUB = {
 }
 
 
+# Names a path gained after its entry was published.  ``alias_table()`` keeps an entry as it was first listed (callers compare
+# entries); ``install()`` binds these as well.
+_RECHUB_ALSO = {"models.matching.comirec": ["ComirecSA"]}
+
+
+def alias_also():
+    """{reference dotted path: further names ``install()`` binds there} -- see ``_RECHUB_ALSO``."""
+    return {root + "." + rel: list(names) for root in ("torch_rechub", "recbox.third_party.rechub")
+            for rel, names in _RECHUB_ALSO.items()}
+
+
 def alias_table():
-    """{reference dotted path: (module of this package, names or None)} for every path ``install()`` serves."""
+    """{reference dotted path: (module of this package, names or None)} for every path ``install()`` serves.  Not the whole
+    list of names for every path: what a path gained after its entry was first listed is in ``alias_also()``."""
     table = {}
     for root, sub in (("recbox.ranking", _RANKING), ("fuxictr", _RANKING), ("recbox.core", _CORE), ("recbox.matching", _MATCHING),
                       ("torch_rechub", _RECHUB), ("recbox.third_party.rechub", _RECHUB)):
@@ -145,7 +158,10 @@ def install(prefixes=("recbox", "fuxictr", "torch_rechub"), overlay=True):
     names on it (False: leave installed modules alone, only fill in what cannot be imported).  Returns
     {"created": [...], "patched": {path: [names]}}; ``uninstall(report)`` undoes it."""
     created, patched, saved = [], {}, {}
+    also = alias_also()
     for path, (target, names) in sorted(alias_table().items()):
+        if names is not None and path in also:
+            names = names + also[path]
         if not any(path == p or path.startswith(p + ".") for p in prefixes):
             continue
         src = importlib.import_module(target)

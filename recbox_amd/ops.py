@@ -4716,3 +4716,26 @@ def gru(x, w_ih, w_hh, b_ih=None, b_hh=None, h0=None, lengths=None):
     if B == 0 or not _gru_fused_ok(x, w_ih, w_hh, b_ih, b_hh, h0):
         return gru_torch(x, w_ih, w_hh, b_ih, b_hh, h0, lengths)
     return _Gru.apply(x, w_ih, w_hh, b_ih, b_hh, h0, _gru_lengths(lengths, B, x.device))
+
+
+
+# ---- self-attentive multi-interest pooling: ComirecSA / SINE ----------------------------------------------------------------
+def sa_pool_torch(x, w1, w2, mask=None, pool=True):
+    """The reference's lines (layers.py:542-549) as they stand.  ``x`` [B, L, D], ``w1`` [D, H], ``w2`` [H, K], ``mask`` [B, L]
+    or [B, L, 1] (None = no mask term); returns ``(out [B, K, D] or None, attn [B, L, K])``.  The mask term is an fp32 addition
+    of ``-1e9 (1 - mask)``, not a select: a fully masked sample attends uniformly (1 / L) and still carries gradient."""
+    hid = torch.einsum('bse, ed -> bsd', x, w1).tanh()
+    if mask is not None:
+        a = torch.einsum('bsd, dk -> bsk', hid, w2) + -1.e9 * (1 - mask.reshape(x.shape[0], x.shape[1], 1).float())
+    else:
+        a = torch.einsum('bsd, dk -> bsk', hid, w2)
+    a = torch.softmax(a, dim=1)
+    return (torch.matmul(a.permute(0, 2, 1), x) if pool else None), a
+
+
+def sa_pool(x, w1, w2, mask=None, pool=True):
+    """Self-attentive multi-interest pooling (MultiInterestSA of ComirecSA, the three attention stages of SINE):
+    ``attn`` [B, L, K] = softmax over L of ``tanh(x w1) w2 + (-1e9) (1 - mask)`` and ``out`` [B, K, D] = ``attn^T x`` (None
+    with ``pool=False``).  The one entry point the mirrors call.  It has no kernel of its own: it is ``sa_pool_torch``, on
+    GPU and CPU tensors alike, and stores the [B, L, H] hidden layer (limits)."""
+    return sa_pool_torch(x, w1, w2, mask, pool)

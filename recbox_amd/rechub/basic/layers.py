@@ -2,7 +2,8 @@
 /root/reference/recbox/third_party/rechub/basic/layers.py): ``EmbeddingLayer`` (+``InputMask``
 and the three pooling modules), ``MLP``, ``FM``, ``LR``, ``PredictionLayer`` with the same
 constructors, outputs, exceptions and parameter names (``embed_dict.<feature>.weight``,
-``mlp.<i>.*``, ``fc.*``), and ``FFM`` / ``CEN`` of DeepFFM / FatDeepFFM (``u``, ``mlp_att.*``).  ``EmbeddingLayer.forward`` is ONE ``rbx_embed_fwd`` launch for all
+``mlp.<i>.*``, ``fc.*``), ``FFM`` / ``CEN`` of DeepFFM / FatDeepFFM (``u``, ``mlp_att.*``), and the extractors of the
+multi-interest and session models (``CapsuleNetwork``, ``MultiInterestSA``, ``GRU``).  ``EmbeddingLayer.forward`` is ONE ``rbx_embed_fwd`` launch for all
 requested features: one-hot lookups, id-masked mean/sum pooling (mask = ``id != padding_idx``,
 eps 1e-16, the pad row is a normal trainable row that just gets weight 0), concat pooling and
 dense pass-through all land in one ``[B, width]`` row.
@@ -407,6 +408,25 @@ class CapsuleNetwork(nn.Module):
         if self.relu_layer:
             out = ops.linear(out, self.relu[0].weight, act="relu")
         return out
+
+
+class MultiInterestSA(nn.Module):
+    """The self-attentive multi-interest extractor of ComirecSA (layers.py:516-550 of the reference): same constructor,
+    parameter names (``W1`` [D, H], ``W2`` [H, interest_num] and the unused ``W3`` [D, D]) and ``torch.rand`` init;
+    ``forward(seq_emb [B, L, D], mask [B, L, 1] or [B, L] or None) -> [B, interest_num, D]`` is one ``ops.sa_pool`` call.  An explicit ``hidden_dim`` is honoured (the reference never sets
+    the attribute in that case and fails in its constructor); the default is 4 D."""
+
+    def __init__(self, embedding_dim, interest_num, hidden_dim=None):
+        super(MultiInterestSA, self).__init__()
+        self.embedding_dim = embedding_dim
+        self.interest_num = interest_num
+        self.hidden_dim = self.embedding_dim * 4 if hidden_dim is None else hidden_dim
+        self.W1 = torch.nn.Parameter(torch.rand(self.embedding_dim, self.hidden_dim), requires_grad=True)
+        self.W2 = torch.nn.Parameter(torch.rand(self.hidden_dim, self.interest_num), requires_grad=True)
+        self.W3 = torch.nn.Parameter(torch.rand(self.embedding_dim, self.embedding_dim), requires_grad=True)
+
+    def forward(self, seq_emb, mask=None):
+        return ops.sa_pool(seq_emb, self.W1, self.W2, mask)[0]
 
 
 class GRU(nn.Module):

@@ -7,10 +7,11 @@ layers on the fp32 matrix cores, ``F.normalize`` and the pairwise dot as HIP ker
 kernel (``rbx_attn_*``)."""
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from ... import ops
-from ..basic.features import DenseFeature
-from ..basic.layers import GRU, MLP, CapsuleNetwork, EmbeddingLayer
+from ..basic.features import DenseFeature, SequenceFeature, SparseFeature
+from ..basic.layers import GRU, MLP, CapsuleNetwork, EmbeddingLayer, MultiInterestSA
 
 
 class DSSM(torch.nn.Module):
@@ -261,13 +262,12 @@ def ops_position(position_emb, positions):
     return out.view(positions.shape[0], L, position_emb.embedding_dim)
 
 
-class _MultiInterestDR(torch.nn.Module):
-    """What MIND and ComirecDR share (mind.py:32-101, comirec.py:118-188): a capsule layer over the history gives
-    ``interest_num`` vectors per user; training scores the interest that fits the positive item best."""
-    bilinear_type = 2
+class _MultiInterest(torch.nn.Module):
+    """What MIND, ComirecDR and ComirecSA share (mind.py:32-101, comirec.py:17-188): an extractor over the history gives
+    ``interest_num`` vectors per user; training scores the interest that fits the positive item best.  A subclass registers its
+    extractor (after ``embedding``, as the reference does) and answers ``extract``."""
 
-    def __init__(self, user_features, history_features, item_features, neg_item_feature, max_length, temperature=1.0,
-                 interest_num=4):
+    def __init__(self, user_features, history_features, item_features, neg_item_feature, temperature=1.0, interest_num=4):
         super().__init__()
         self.user_features = user_features
         self.item_features = item_features
@@ -275,14 +275,25 @@ class _MultiInterestDR(torch.nn.Module):
         self.neg_item_feature = neg_item_feature
         self.temperature = temperature
         self.interest_num = interest_num
-        self.max_length = max_length
         self.user_dims = sum([fea.embed_dim for fea in user_features + history_features])
         self.embedding = EmbeddingLayer(user_features + item_features + history_features)
-        self.capsule = CapsuleNetwork(self.history_features[0].embed_dim, self.max_length, bilinear_type=self.bilinear_type,
-                                      interest_num=self.interest_num)
         self.convert_user_weight = nn.Parameter(torch.rand(self.user_dims, self.history_features[0].embed_dim),
                                                 requires_grad=True)
         self.mode = None
+
+    def extract(self, history_emb, x):
+        """[B, L, D] -> [B, interest_num, D]"""
+        raise NotImplementedError
+
+    # the three places where a tower touches the kernels; ComirecSA, which also serves CPU tensors, overrides them
+    def _embed(self, x, features, squeeze_dim=False):
+        return self.embedding(x, features, squeeze_dim=squeeze_dim)
+
+    def _project(self, input_user):
+        return ops.linear(input_user, self.convert_user_weight.t())
+
+    def _normalize(self, t):
+        return ops.l2_normalize(t)
 
     def forward(self, x):
         user_embedding = self.user_tower(x)
@@ -301,26 +312,40 @@ class _MultiInterestDR(torch.nn.Module):
     def user_tower(self, x):
         if self.mode == "item":
             return None
-        input_user = self.embedding(x, self.user_features, squeeze_dim=True).unsqueeze(1)
+        input_user = self._embed(x, self.user_features, squeeze_dim=True).unsqueeze(1)
         input_user = input_user.expand([input_user.shape[0], self.interest_num, input_user.shape[-1]])
-        history_emb = self.embedding(x, self.history_features).squeeze(1)                                  # [B, L, D]
-        multi_interest_emb = self.capsule(history_emb, self.gen_mask(x))                                   # [B, K, D]
+        history_emb = self._embed(x, self.history_features).squeeze(1)                                     # [B, L, D]
+        multi_interest_emb = self.extract(history_emb, x)                                                  # [B, K, D]
         input_user = torch.cat([input_user, multi_interest_emb], dim=-1)
-        user_embedding = ops.linear(input_user, self.convert_user_weight.t())
-        return ops.l2_normalize(user_embedding)                                                            # [B, K, D]
+        return self._normalize(self._project(input_user))                                                  # [B, K, D]
 
     def item_tower(self, x):
         if self.mode == "user":
             return None
-        pos_embedding = ops.l2_normalize(self.embedding(x, self.item_features, squeeze_dim=False))         # [B, 1, D]
+        pos_embedding = self._normalize(self._embed(x, self.item_features, squeeze_dim=False))             # [B, 1, D]
         if self.mode == "item":
             return pos_embedding.squeeze(1)
-        neg_embeddings = ops.l2_normalize(self.embedding(x, self.neg_item_feature, squeeze_dim=False).squeeze(1))
+        neg_embeddings = self._normalize(self._embed(x, self.neg_item_feature, squeeze_dim=False).squeeze(1))
         return torch.cat((pos_embedding, neg_embeddings), dim=1)                                           # [B, 1 + n_neg, D]
 
     def gen_mask(self, x):
         his_list = x[self.history_features[0].name]
         return (his_list > 0).long()
+
+
+class _MultiInterestDR(_MultiInterest):
+    """The capsule-routing members (mind.py:32-101, comirec.py:118-188)."""
+    bilinear_type = 2
+
+    def __init__(self, user_features, history_features, item_features, neg_item_feature, max_length, temperature=1.0,
+                 interest_num=4):
+        super().__init__(user_features, history_features, item_features, neg_item_feature, temperature, interest_num)
+        self.max_length = max_length
+        self.capsule = CapsuleNetwork(self.history_features[0].embed_dim, self.max_length, bilinear_type=self.bilinear_type,
+                                      interest_num=self.interest_num)
+
+    def extract(self, history_emb, x):
+        return self.capsule(history_emb, self.gen_mask(x))
 
 
 class MIND(_MultiInterestDR):
@@ -332,6 +357,150 @@ class MIND(_MultiInterestDR):
 class ComirecDR(_MultiInterestDR):
     """``torch_rechub.models.matching.ComirecDR`` (comirec.py:103-188): ``CapsuleNetwork(bilinear_type=2)``."""
     bilinear_type = 2
+
+
+def _embed_aten(layer, x, features, squeeze_dim):
+    """``EmbeddingLayer.forward`` for CPU tensors, in ATen: one-hot features and ``pooling='concat'`` sequences, which is
+    what the multi-interest models feed it."""
+    rows = []
+    for fea in features:
+        table = layer.embed_dict[fea.name if fea.shared_with is None else fea.shared_with]
+        if isinstance(fea, SparseFeature):
+            rows.append(table(x[fea.name].long()).unsqueeze(1))                                            # [B, 1, D]
+        elif isinstance(fea, SequenceFeature) and fea.pooling == "concat":
+            rows.append(table(x[fea.name].long()).unsqueeze(1))                                            # [B, 1, L, D]
+        else:
+            raise NotImplementedError("feature '%s': the CPU path serves one-hot and pooling='concat' features" % fea.name)
+    out = torch.cat(rows, dim=1)
+    return out.flatten(start_dim=1) if squeeze_dim else out
+
+
+class ComirecSA(_MultiInterest):
+    """``torch_rechub.models.matching.ComirecSA`` (comirec.py:17-101): the towers of ComirecDR around ``MultiInterestSA``
+    (``multi_interest_sa.W1`` / ``W2`` / ``W3``), which is one ``ops.sa_pool`` call.  No ``max_length``, as in the
+    reference.  CPU tensors run the same model in ATen."""
+
+    def __init__(self, user_features, history_features, item_features, neg_item_feature, temperature=1.0, interest_num=4):
+        super().__init__(user_features, history_features, item_features, neg_item_feature, temperature, interest_num)
+        self.multi_interest_sa = MultiInterestSA(embedding_dim=self.history_features[0].embed_dim, interest_num=self.interest_num)
+
+    def extract(self, history_emb, x):
+        return self.multi_interest_sa(history_emb, self.gen_mask(x))
+
+    def _embed(self, x, features, squeeze_dim=False):
+        if x[features[0].name].is_cuda:
+            return self.embedding(x, features, squeeze_dim=squeeze_dim)
+        return _embed_aten(self.embedding, x, features, squeeze_dim)
+
+    def _project(self, input_user):
+        return super()._project(input_user) if input_user.is_cuda else torch.matmul(input_user, self.convert_user_weight)
+
+    def _normalize(self, t):
+        return super()._normalize(t) if t.is_cuda else F.normalize(t, p=2, dim=-1)
+
+
+class SINE(torch.nn.Module):
+    """``torch_rechub.models.matching.SINE`` (sine.py:14-151): same constructor (feature NAMES, not Feature objects), parameter
+    names (``item_embedding`` / ``concept_embedding`` / ``position_embedding``, ``w_1`` .. ``w_5``, ``w_k1``, ``w_k2``) and
+    ``mode`` protocol.  Its three self-attentive stages are ``ops.sa_pool`` calls -- the concept vector z_u (pooled, heads
+    summed), the per-intention weights P(t|k) (``attn`` only) and the next-intention vector over x_u_hat (pooled) -- and the
+    history, target and negatives are ONE lookup of the item table through the gather kernel.  Top-k over the concepts, the
+    softmaxes over K, the small einsums over K and the normalisations are ATen.  ``num_heads`` is kept; 1 is the only value for
+    which the reference's forward runs (sine.py:123 reshapes [B, L, heads] to [-1, L]) and anything else raises here too."""
+
+    def __init__(self, history_features, item_features, neg_item_features, num_items, embedding_dim, hidden_dim, num_concept,
+                 num_intention, seq_max_len, num_heads=1, temperature=1.0):
+        super().__init__()
+        self.item_features = item_features
+        self.history_features = history_features
+        self.neg_item_features = neg_item_features
+        self.temperature = temperature
+        self.num_concept = num_concept
+        self.num_intention = num_intention
+        self.seq_max_len = seq_max_len
+        self.num_heads = num_heads
+        std = 1e-4
+        self.item_embedding = torch.nn.Embedding(num_items, embedding_dim)
+        torch.nn.init.normal_(self.item_embedding.weight, 0, std)
+        self.concept_embedding = torch.nn.Embedding(num_concept, embedding_dim)
+        torch.nn.init.normal_(self.concept_embedding.weight, 0, std)
+        self.position_embedding = torch.nn.Embedding(seq_max_len, embedding_dim)
+        torch.nn.init.normal_(self.position_embedding.weight, 0, std)
+        self.w_1 = torch.nn.Parameter(torch.rand(embedding_dim, hidden_dim), requires_grad=True)
+        self.w_2 = torch.nn.Parameter(torch.rand(hidden_dim, num_heads), requires_grad=True)
+        self.w_3 = torch.nn.Parameter(torch.rand(embedding_dim, embedding_dim), requires_grad=True)
+        self.w_k1 = torch.nn.Parameter(torch.rand(embedding_dim, hidden_dim), requires_grad=True)
+        self.w_k2 = torch.nn.Parameter(torch.rand(hidden_dim, num_intention), requires_grad=True)
+        self.w_4 = torch.nn.Parameter(torch.rand(embedding_dim, hidden_dim), requires_grad=True)
+        self.w_5 = torch.nn.Parameter(torch.rand(hidden_dim, num_heads), requires_grad=True)
+        self.mode = None
+
+    def _items(self, x):
+        """(history [B, L, D] or None, candidates [B, 1 (+ n_neg), D] or None): every id the mode needs in one lookup."""
+        cols = []
+        if self.mode != "item":
+            cols.append(x[self.history_features[0]])
+        if self.mode != "user":
+            cols.append(x[self.item_features[0]].reshape(-1, 1))
+            if self.mode != "item":
+                neg = x[self.neg_item_features[0]]
+                cols.append(neg.reshape(neg.shape[0], -1))
+        ids = torch.cat([c.long() for c in cols], dim=1)
+        emb = ops_position(self.item_embedding, ids) if ids.is_cuda else self.item_embedding(ids)
+        n_hist = cols[0].shape[1] if self.mode != "item" else 0
+        return (emb[:, :n_hist] if n_hist else None), (emb[:, n_hist:] if self.mode != "user" else None)
+
+    def forward(self, x):
+        hist_emb, cand_emb = self._items(x)
+        user_embedding = self.user_tower(x, hist_emb)
+        item_embedding = self.item_tower(x, cand_emb)
+        if self.mode == "user":
+            return user_embedding
+        if self.mode == "item":
+            return item_embedding
+        return torch.mul(user_embedding, item_embedding).sum(dim=-1)                                       # [B, 1 + n_neg]
+
+    def user_tower(self, x, hist_emb=None):
+        if self.mode == "item":
+            return None
+        if self.num_heads != 1:
+            raise ValueError("SINE: num_heads=%d; the reference's forward runs with 1 head only" % self.num_heads)
+        if hist_emb is None:
+            hist_emb = self._items(x)[0]
+        einsum = torch.einsum
+        hist = x[self.history_features[0]]
+        x_u = hist_emb + self.position_embedding.weight.unsqueeze(0)                                      # [B, L, D]
+        mask = (hist > 0).long()
+        # sparse-interest extraction: the virtual concept vector z_u, its top concepts C^u
+        z_u = ops.sa_pool(x_u, self.w_1, self.w_2, mask)[0].sum(dim=1)                                     # [B, D]
+        s_u = einsum("be, te -> bt", z_u, self.concept_embedding.weight)
+        top = torch.topk(s_u, self.num_intention)
+        c_u = einsum("bk, bke -> bke", torch.sigmoid(top.values), F.embedding(top.indices, self.concept_embedding.weight))
+        # intention assignment P(k|t), attention weighing P(t|k)
+        p_u = torch.softmax(einsum("bse, bke -> bks", F.normalize(x_u @ self.w_3, dim=-1), F.normalize(c_u, p=2, dim=-1)), dim=1)
+        a_concept_k = ops.sa_pool(x_u, self.w_k1, self.w_k2, mask, pool=False)[1]                          # [B, L, K]
+        phi_u = einsum("bks, bse -> bke", p_u * a_concept_k.permute(0, 2, 1), x_u)
+        # adaptive interest aggregation: the intention-aware input, the next intention, the aggregation weights
+        x_u_hat = einsum("bks, bke -> bse", p_u, c_u)
+        # as written: sine.py:120-125 calls F.normalize(t, -1), whose second positional argument is p -- the p = -1 norm over dim 1
+        c_u_apt = F.normalize(ops.sa_pool(x_u_hat, self.w_4, self.w_5, mask)[0][:, 0], p=-1, dim=1)        # [B, D]
+        e_u = torch.softmax(einsum("be, bke -> bk", c_u_apt, phi_u) / self.temperature, dim=1)
+        v_u = einsum("bk, bke -> be", e_u, phi_u)
+        if self.mode == "user":
+            return v_u
+        return v_u.unsqueeze(1)
+
+    def item_tower(self, x, cand_emb=None):
+        if self.mode == "user":
+            return None
+        if cand_emb is None:
+            cand_emb = self._items(x)[1]
+        if self.mode == "item":
+            return cand_emb.squeeze(1)                                                                     # [B, D]
+        return cand_emb                                                                                    # [B, 1 + n_neg, D]
+
+    def gen_mask(self, x):
+        return (x[self.history_features[0]] > 0).long()
 
 
 class GRU4Rec(torch.nn.Module):
