@@ -1196,6 +1196,37 @@ int rbx_gru_fwd(const float* d_gi, int64_t gi_stride_b, int64_t gi_stride_t, con
 int rbx_gru_bwd(const float* d_saved, const float* d_w_hh, const float* d_dout, int64_t dout_stride_b, int64_t dout_stride_t,
                 const float* d_dhn, const void* d_lengths, int32_t lengths_dtype, int64_t batch, int32_t seq_len,
                 int32_t hidden, int32_t dtype, float* d_dgi, float* d_dghn, float* d_dh0, void* stream);
+
+/* ---- expert-gate mixing: MMOE, CGC / PLE, AITM (csrc/rbx_mix.hip; additions only, the version stays) -----------------------
+ * Replaces, under third_party/rechub/models/multi_task/mmoe.py:46-57, ple.py:102-128 and aitm.py:77-84, the torch.cat of the
+ * expert outputs into [B, E, H], one torch.mul per gate into another [B, E, H], and a torch.sum.  B = batch, H = hidden,
+ * E = experts, T = gates.  Gate t mixes the experts sel[sel_off[t]] .. sel[sel_off[t + 1] - 1] (n_t of them, distinct):
+ *   p_t[b, j] = softmax_j(z_t[b, j]) (softmax != 0; max-subtracted, fp32) or z_t[b, j];  out_t[b, :] = sum_j p_t[b, j] X_sel_t[j][b, :]
+ * x [E], x_stride [E], z [T], sel, sel_off [T + 1], dout [T], dx [E], dz [T] are HOST arrays; what x, z, dout, dx, dz hold are
+ * device pointers.  Expert e is read at x[e][b x_stride[e] + c], c < H; z[t] is a contiguous [B, n_t].  Everything travels to
+ * the kernel by value in its argument struct: a call is ONE kernel launch on `stream` and nothing else -- no allocation, copy,
+ * memset, stream, event, synchronisation, device-side table or workspace: capturable.
+ *   rbx_expert_mix_fwd  one pass over the experts for all T gates (X_e[b, :] is loaded once, whichever gates select e).  Writes
+ *                       d_out [T, B, H] and, with softmax, d_p [B, sel_off[T]] (gate t in columns sel_off[t] ..) for the backward
+ *                       (without softmax d_p is not written and may be NULL).
+ *   rbx_expert_mix_bwd  one pass again.  dout[t] [B, H] contiguous (NULL: that output had no gradient = zeros).  Writes, where
+ *                       the pointer is not NULL (dx or dz themselves may be NULL), dx[e] [B, H] = sum over (t, j) with
+ *                       sel_t[j] = e of p_t[b, j] dout_t[b, :] in full (zeros if no gate selects e) and dz[t] [B, n_t]:
+ *                       dp_t[b, j] = <dout_t[b, :], X_sel_t[j][b, :]>, dz = p (dp - sum_i p_i dp_i) with softmax (d_p as the
+ *                       forward wrote it; z is not read), else dp (z is read as p).
+ * Supported (rbx_expert_mix_supported): dtype (the RBX_* code of every float tensor) RBX_F32; H a multiple of 4 in [4, 1024];
+ * 1 <= E <= 16; 1 <= T <= 8; 1 <= n_t <= 16, every entry of sel in [0, E) and no expert twice in one gate; x, d_out, dout and
+ * dx 16-byte aligned, x_stride multiples of 4.  Anything else: RBX_ERR_UNSUPPORTED before any launch.  batch = 0 launches
+ * nothing.  No atomics, sums in a fixed order (out_t in ascending expert order, dx in ascending gate order). */
+int rbx_expert_mix_supported(int32_t hidden, int32_t experts, int32_t gates, const int32_t* sel, const int32_t* sel_off,
+                             int32_t dtype);
+int rbx_expert_mix_fwd(const float* const* x, const int64_t* x_stride, const float* const* z, const int32_t* sel,
+                       const int32_t* sel_off, int64_t batch, int32_t hidden, int32_t experts, int32_t gates, int32_t softmax,
+                       int32_t dtype, float* d_out, float* d_p, void* stream);
+int rbx_expert_mix_bwd(const float* const* x, const int64_t* x_stride, const float* const* z, const float* d_p,
+                       const float* const* dout, const int32_t* sel, const int32_t* sel_off, int64_t batch, int32_t hidden,
+                       int32_t experts, int32_t gates, int32_t softmax, int32_t dtype, float* const* dx, float* const* dz,
+                       void* stream);
 #ifdef __cplusplus
 }
 #endif

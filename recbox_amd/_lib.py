@@ -100,6 +100,8 @@ _OP = ctypes.POINTER(rbx_opt_t)
 _PP = ctypes.POINTER(ctypes.c_void_p)          # host array of device pointers
 _u64 = ctypes.c_uint64
 _i32, _i64, _sz, _f32 = ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
+_IP = ctypes.POINTER(ctypes.c_int32)           # host arrays of rbx_expert_mix_*: selections / offsets,
+_LP = ctypes.POINTER(ctypes.c_int64)           # row strides
 
 # name -> (restype, argtypes); must list every symbol of include/recbox_hip.h
 SIGNATURES = {
@@ -282,6 +284,9 @@ SIGNATURES = {
     "rbx_gru_supported": (ctypes.c_int, [_i32, _i32]),
     "rbx_gru_fwd": (ctypes.c_int, [_P, _i64, _i64, _P, _P, _P, _P, _i32, _i64, _i32, _i32, _i32, _P, _P, _P, _P]),
     "rbx_gru_bwd": (ctypes.c_int, [_P, _P, _P, _i64, _i64, _P, _P, _i32, _i64, _i32, _i32, _i32, _P, _P, _P, _P]),
+    "rbx_expert_mix_supported": (ctypes.c_int, [_i32, _i32, _i32, _IP, _IP, _i32]),
+    "rbx_expert_mix_fwd": (ctypes.c_int, [_PP, _LP, _PP, _IP, _IP, _i64, _i32, _i32, _i32, _i32, _i32, _P, _P, _P]),
+    "rbx_expert_mix_bwd": (ctypes.c_int, [_PP, _LP, _PP, _P, _PP, _IP, _IP, _i64, _i32, _i32, _i32, _i32, _i32, _PP, _PP, _P]),
 }
 
 

@@ -100,6 +100,12 @@ _RECHUB = {
     "models.ranking.din": ("recbox_amd.rechub.models.ranking", ["DIN", "ActivationUnit"]),
     "models.ranking.deepfm": ("recbox_amd.rechub.models.ranking", ["DeepFM"]),
     "models.ranking.deepffm": ("recbox_amd.rechub.models.ranking", ["DeepFFM", "FatDeepFFM"]),
+    "models.multi_task": ("recbox_amd.rechub.models.multi_task", ["SharedBottom", "ESMM", "MMOE", "PLE", "AITM", "CGC"]),
+    "models.multi_task.shared_bottom": ("recbox_amd.rechub.models.multi_task", ["SharedBottom"]),
+    "models.multi_task.esmm": ("recbox_amd.rechub.models.multi_task", ["ESMM"]),
+    "models.multi_task.mmoe": ("recbox_amd.rechub.models.multi_task", ["MMOE"]),
+    "models.multi_task.ple": ("recbox_amd.rechub.models.multi_task", ["PLE", "CGC"]),
+    "models.multi_task.aitm": ("recbox_amd.rechub.models.multi_task", ["AITM", "AttentionLayer"]),
 }
 
 

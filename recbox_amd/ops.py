@@ -123,6 +123,11 @@ class config(object):
     # (profiles/gru/INDEX.md): 51 x / 24 x / 16 x at B = 4096, 12 x / 12 x / 9 x at B = 65 536 (H = 16 / 64 / 128, L = 50, two layers),
     # 23 x at NARM's form (B = 512, L = 20, H = 100): no shape class loses, so there is no width threshold.
     gru_fused = os.environ.get("RECBOX_AMD_GRU_FUSED", "1") != "0"
+    # multi-task ranking (rechub's MMOE, CGC / PLE, AITM): mixing the expert outputs under the per-task gates as one launch
+    # forward and one backward that read every expert row once for all gates (expert_mix: csrc/rbx_mix.hip) instead of
+    # torch.cat into [B, E, H], a [B, E, H] product per gate that autograd keeps, and a sum.  Off, or for what
+    # expert_mix_supported refuses: that composition (expert_mix_torch).  Measurements: profiles/expert_mix/INDEX.md.
+    expert_mix_fused = os.environ.get("RECBOX_AMD_EXPERT_MIX_FUSED", "1") != "0"
 
 
 def _require_cuda(t, what):
@@ -4739,3 +4744,150 @@ def sa_pool(x, w1, w2, mask=None, pool=True):
     with ``pool=False``).  The one entry point the mirrors call.  It has no kernel of its own: it is ``sa_pool_torch``, on
     GPU and CPU tensors alike, and stores the [B, L, H] hidden layer (limits)."""
     return sa_pool_torch(x, w1, w2, mask, pool)
+
+
+# ---- expert-gate mixing: MMOE, CGC / PLE, AITM (csrc/rbx_mix.hip) ------------------------------------------------------------
+MIX_MAX_HIDDEN, MIX_MAX_EXPERTS, MIX_MAX_GATES, MIX_MAX_SELECT = 1024, 16, 8, 16
+
+
+def _mix_select(select, n_expert, n_gate):
+    """``select`` as a tuple of T tuples of ints; None = every gate mixes all experts in order."""
+    if select is None:
+        return (tuple(range(n_expert)),) * n_gate
+    select = tuple(tuple(int(i) for i in s) for s in select)
+    if len(select) != n_gate:
+        raise ValueError("expert_mix: %d gates but %d selections" % (n_gate, len(select)))
+    for s in select:
+        if any(i < 0 or i >= n_expert for i in s):
+            raise IndexError("expert_mix: selection %s names an expert outside 0 .. %d" % (list(s), n_expert - 1))
+    return select
+
+
+def _mix_sel_arrays(select):
+    flat = [i for s in select for i in s]
+    offs = [0]
+    for s in select:
+        offs.append(offs[-1] + len(s))
+    return (ctypes.c_int32 * max(len(flat), 1))(*flat), (ctypes.c_int32 * len(offs))(*offs), offs
+
+
+def expert_mix_supported(hidden, n_expert, select=None, n_gate=1, dtype=torch.float32):
+    """Whether the fused op takes this shape (rbx_expert_mix_supported): float32, ``hidden`` a multiple of 4 in 4 .. 1024,
+    1 .. 16 experts, 1 .. 8 gates, each mixing 1 .. 16 distinct experts.  ``select``: the gates' index lists (None: ``n_gate``
+    gates over all experts).  No shape class is gated off: none measured slower than the composition
+    (profiles/expert_mix/INDEX.md).  What it refuses runs ``expert_mix_torch``."""
+    if dtype not in _DTYPE_CODE:
+        return False
+    n_expert = int(n_expert)
+    if select is None:
+        select = (tuple(range(n_expert)),) * int(n_gate)
+    select = tuple(tuple(int(i) for i in s) for s in select)
+    if not 0 < len(select) <= MIX_MAX_GATES:
+        return False
+    sel, off, _ = _mix_sel_arrays(select)
+    return bool(lib.rbx_expert_mix_supported(int(hidden), n_expert, len(select), sel, off, _DTYPE_CODE[dtype]))
+
+
+def expert_mix_torch(experts, gates, select=None, softmax=True):
+    """The reference's composition (mmoe.py:46-57, ple.py:102-128): per gate ``torch.cat`` of its experts into [B, n_t, H], a
+    ``torch.mul`` with the gate's weights and a ``torch.sum``.  Same signature and result as ``expert_mix``; serves CPU tensors
+    and what the fused op refuses, and is what the fused op is measured against."""
+    select = _mix_select(select, len(experts), len(gates))
+    outs = []
+    for gate, sel in zip(gates, select):
+        w = torch.softmax(gate, dim=1) if softmax else gate
+        block = torch.cat([experts[i].unsqueeze(1) for i in sel], dim=1)                  # [B, n_t, H]
+        outs.append(torch.sum(torch.mul(w.unsqueeze(-1), block), dim=1))
+    return tuple(outs)
+
+
+def _mix_rows(t):
+    """An expert as the kernels read it: [B, H] float32 with a unit inner stride, a 16-byte aligned base and a row stride that
+    is a multiple of 4 floats -- in place where it is one (a column block or an interleaved row of a wider tensor)."""
+    if t.stride(1) != 1 or t.data_ptr() % 16 != 0 or (t.shape[0] > 1 and t.stride(0) % 4 != 0):
+        t = t.contiguous()
+    return t
+
+
+class _ExpertMix(torch.autograd.Function):
+    """(out_0 .. out_{T-1}) of ``expert_mix`` as views of one [T, B, H] buffer: ONE launch forward (rbx_expert_mix_fwd), ONE
+    backward (rbx_expert_mix_bwd).  Saved: the experts and, with softmax, p [B, sum n_t] (else the gates)."""
+
+    @staticmethod
+    def forward(ctx, select, softmax, n_expert, *tensors):
+        experts = [_mix_rows(t) for t in tensors[:n_expert]]
+        gates = [t.contiguous() for t in tensors[n_expert:]]
+        E, T = n_expert, len(gates)
+        B, H = experts[0].shape
+        dev = experts[0].device
+        sel, off, offs = _mix_sel_arrays(select)
+        xs = (ctypes.c_void_p * E)(*[t.data_ptr() for t in experts])
+        strides = (ctypes.c_int64 * E)(*[t.stride(0) if B > 1 else H for t in experts])
+        zs = (ctypes.c_void_p * T)(*[t.data_ptr() for t in gates])
+        out = torch.empty((T, B, H), dtype=torch.float32, device=dev)
+        p = torch.empty((B, offs[-1]), dtype=torch.float32, device=dev) if softmax else None
+        check(_timed(("expert_mix_fwd", B, H, E, T),
+                     lambda: lib.rbx_expert_mix_fwd(xs, strides, zs, sel, off, B, H, E, T, int(softmax), _lib.RBX_F32, _ptr(out),
+                                                    _ptr(p), _stream())))
+        ctx.save_for_backward(*(experts + ([p] if softmax else gates)))
+        ctx.select, ctx.softmax, ctx.dims, ctx.offs = select, bool(softmax), (B, H, E, T), offs
+        ctx.set_materialize_grads(False)
+        return tuple(out[t] for t in range(T))
+
+    @staticmethod
+    def backward(ctx, *douts):
+        B, H, E, T = ctx.dims
+        saved = ctx.saved_tensors
+        experts = saved[:E]
+        p, gates = (saved[E], None) if ctx.softmax else (None, saved[E:])
+        dev = experts[0].device
+        offs = ctx.offs
+        need = ctx.needs_input_grad[3:]
+        douts = [None if d is None else (d if (d.dtype == torch.float32 and d.is_contiguous() and d.data_ptr() % 16 == 0)
+                                         else d.float().contiguous()) for d in douts]
+        dx = torch.empty((E, B, H), dtype=torch.float32, device=dev) if any(need[:E]) else None
+        dz = torch.empty(B * offs[-1], dtype=torch.float32, device=dev) if any(need[E:]) else None
+        dzs = [dz[B * offs[t]:B * offs[t + 1]].view(B, offs[t + 1] - offs[t]) if need[E + t] else None for t in range(T)]
+        sel, off, _ = _mix_sel_arrays(ctx.select)
+        xs = (ctypes.c_void_p * E)(*[t.data_ptr() for t in experts])
+        strides = (ctypes.c_int64 * E)(*[t.stride(0) if B > 1 else H for t in experts])
+        # with softmax the backward reads p and never the gates: any valid pointer stands in for them
+        zs = (ctypes.c_void_p * T)(*[(p if ctx.softmax else gates[t]).data_ptr() for t in range(T)])
+        gs = (ctypes.c_void_p * T)(*[d.data_ptr() if d is not None else None for d in douts])
+        dxs = (ctypes.c_void_p * E)(*[dx[e].data_ptr() if need[e] else None for e in range(E)])
+        dzp = (ctypes.c_void_p * T)(*[d.data_ptr() if d is not None else None for d in dzs])
+        check(_timed(("expert_mix_bwd", B, H, E, T),
+                     lambda: lib.rbx_expert_mix_bwd(xs, strides, zs, _ptr(p), gs, sel, off, B, H, E, T, int(ctx.softmax),
+                                                    _lib.RBX_F32, dxs, dzp, _stream())))
+        return (None, None, None) + tuple(dx[e] if need[e] else None for e in range(E)) + tuple(dzs)
+
+
+def _expert_mix_fused_ok(experts, gates, select):
+    """The refusals of ``expert_mix`` that run the composition: the switch, CPU or non-float32 tensors, shapes that do not fit
+    each other, an empty batch, what ``expert_mix_supported`` refuses."""
+    if not config.expert_mix_fused or not experts or not gates:
+        return False
+    x0 = experts[0]
+    if x0.dim() != 2 or x0.shape[0] == 0:
+        return False
+    if any((not t.is_cuda) or t.dtype != torch.float32 or t.shape != x0.shape for t in experts):
+        return False
+    for gate, sel in zip(gates, select):
+        if (not gate.is_cuda) or gate.dtype != torch.float32 or gate.dim() != 2 or gate.shape != (x0.shape[0], len(sel)):
+            return False
+    return expert_mix_supported(x0.shape[1], len(experts), select)
+
+
+def expert_mix(experts, gates, select=None, softmax=True):
+    """Mix expert outputs under per-task gates (MMOE, CGC / PLE, AITM's AttentionLayer): ``experts`` E tensors [B, H],
+    ``gates`` T tensors [B, n_t], ``select`` T index lists into the experts (None: every gate mixes all experts in order) ->
+    a tuple of T tensors [B, H], ``out_t = sum_j p_t[:, j, None] * experts[select[t][j]]`` with ``p_t = softmax(gates[t], dim=1)``
+    (``softmax=True``) or ``gates[t]`` itself.  One autograd node; the outputs are views of one [T, B, H] buffer; every expert
+    row is read once for all gates, and strided expert views with a unit inner stride are read in place.  CPU or non-float32
+    tensors, ``B == 0``, what ``expert_mix_supported`` refuses and ``config.expert_mix_fused = False`` run
+    ``expert_mix_torch``."""
+    experts, gates = list(experts), list(gates)
+    select = _mix_select(select, len(experts), len(gates))
+    if not _expert_mix_fused_ok(experts, gates, select):
+        return expert_mix_torch(experts, gates, select, softmax)
+    return _ExpertMix.apply(select, bool(softmax), len(experts), *(experts + gates))
