@@ -1227,6 +1227,38 @@ int rbx_expert_mix_bwd(const float* const* x, const int64_t* x_stride, const flo
                        const float* const* dout, const int32_t* sel, const int32_t* sel_off, int64_t batch, int32_t hidden,
                        int32_t experts, int32_t gates, int32_t softmax, int32_t dtype, float* const* dx, float* const* dz,
                        void* stream);
+
+/* ---- additive attention pooling: NARM, STAMP (csrc/rbx_addattn.hip; additions only, the version stays) ---------------------
+ * Replaces the ATen lines third_party/rechub/models/matching/narm.py:60-68 (Eq. 6-8) and stamp.py:69-72 (Eq. 7-8), whose
+ * x W^T [B, L, H] is written, re-read three times and kept by autograd.  B = batch, L = seq_len, D = dim, H = hidden:
+ *   q[b,l] = v . sigmoid(x[b,l] W^T + ctx[b])      e[b,l] = exp(q[b,l]) mask[b,l]   (as written: no max subtraction)
+ *   alpha[b,l] = e[b,l] / max(sum_l e[b,l], eps)    out[b] = sum_l alpha[b,l] x[b,l]
+ * d_x is read at x[b x_stride_b + l x_stride_l + c], c < D; d_w [H, D] contiguous; d_ctx [B, H] (NULL: zeros); d_v [H];
+ * d_mask [B, L] contiguous as RBX_I32 / RBX_I64 / RBX_F32 / RBX_MASK_U8 (bool), nonzero = valid (NULL: all valid).
+ *   rbx_addattn_fwd  one launch.  x W^T runs tile by tile (16 positions) on v_mfma_f32_16x16x4_f32 against W held in
+ *                    registers for all samples of a workgroup; sigmoid, the v product, exp, the mask and the sums stay on
+ *                    chip.  The division is an IEEE division: one valid position gives alpha = 1 exactly, k equal logits
+ *                    1.0f / k.  eps = 0 and no valid position: NaN, as the composition; eps > 0: alpha = 0, out = 0.
+ *                    Writes d_out [B, D] and d_alpha [B, L].
+ *   rbx_addattn_bwd  d_dout is read at dout[b dout_stride_b + c]; alpha has no gradient of its own.  One launch recomputes
+ *                    s = sigmoid(x W^T + ctx) per tile and forms g_l = dout . x_l, dq_l = alpha_l (g_l - sum_j alpha_j g_j),
+ *                    dpre_lh = dq_l v_h s_lh (1 - s_lh); writes d_dctx [B, H] = sum_l dpre_l, d_dx [B, L, D] =
+ *                    alpha_l dout + dpre_l W, and d_dpre [B, L, H] (NULL: not wanted) -- a transient of the backward from
+ *                    which rbx_linear_bwd forms dW = dpre^T x.  dv = sum_{b,l} dq_l s_l: one row of H floats per workgroup in
+ *                    the workspace (rbx_addattn_bwd_workspace_size), summed in a fixed order by a second launch into d_dv [H].
+ * Supported (rbx_addattn_supported): D and H multiples of 4 in [4, 128], L >= 1; dtype (the RBX_* code of every float tensor)
+ * RBX_F32; x and d_dout 16-byte aligned with strides that are multiples of 4.  Anything else: RBX_ERR_UNSUPPORTED before any
+ * launch.  batch = 0 launches nothing.  No atomics, sums in a fixed order; no call allocates or reads back: capturable. */
+int rbx_addattn_supported(int32_t dim, int32_t hidden, int32_t seq_len);
+int rbx_addattn_fwd(const float* d_x, int64_t x_stride_b, int64_t x_stride_l, const float* d_w, const float* d_ctx,
+                    const float* d_v, const void* d_mask, int32_t mask_dtype, float eps, int64_t batch, int32_t seq_len,
+                    int32_t dim, int32_t hidden, int32_t dtype, float* d_out, float* d_alpha, void* stream);
+size_t rbx_addattn_bwd_workspace_size(int64_t batch, int32_t hidden);
+int rbx_addattn_bwd(const float* d_dout, int64_t dout_stride_b, const float* d_x, int64_t x_stride_b, int64_t x_stride_l,
+                    const float* d_w, const float* d_ctx, const float* d_v, const void* d_mask, int32_t mask_dtype,
+                    const float* d_alpha, float eps, int64_t batch, int32_t seq_len, int32_t dim, int32_t hidden,
+                    int32_t dtype, float* d_dx, float* d_dctx, float* d_dv, float* d_dpre, void* d_workspace,
+                    size_t workspace_bytes, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -287,6 +287,11 @@ SIGNATURES = {
     "rbx_expert_mix_supported": (ctypes.c_int, [_i32, _i32, _i32, _IP, _IP, _i32]),
     "rbx_expert_mix_fwd": (ctypes.c_int, [_PP, _LP, _PP, _IP, _IP, _i64, _i32, _i32, _i32, _i32, _i32, _P, _P, _P]),
     "rbx_expert_mix_bwd": (ctypes.c_int, [_PP, _LP, _PP, _P, _PP, _IP, _IP, _i64, _i32, _i32, _i32, _i32, _i32, _PP, _PP, _P]),
+    "rbx_addattn_supported": (ctypes.c_int, [_i32, _i32, _i32]),
+    "rbx_addattn_fwd": (ctypes.c_int, [_P, _i64, _i64, _P, _P, _P, _P, _i32, _f32, _i64, _i32, _i32, _i32, _i32, _P, _P, _P]),
+    "rbx_addattn_bwd_workspace_size": (_sz, [_i64, _i32]),
+    "rbx_addattn_bwd": (ctypes.c_int, [_P, _i64, _P, _i64, _i64, _P, _P, _P, _P, _i32, _P, _f32, _i64, _i32, _i32, _i32, _i32,
+                                       _P, _P, _P, _P, _P, _sz, _P]),
 }
 
 

@@ -87,7 +87,8 @@ _RECHUB = {
     "basic.layers": ("recbox_amd.rechub.basic.layers", None),
     "basic.activation": ("recbox_amd.rechub.basic.layers", ["Dice", "activation_layer"]),
     "models.matching": ("recbox_amd.rechub.models.matching", ["DSSM", "YoutubeDNN", "SASRec", "MIND", "ComirecDR", "GRU4Rec",
-                                                              "NARM", "ComirecSA", "SINE"]),
+                                                              "NARM", "ComirecSA", "SINE", "STAMP"]),
+    "models.matching.stamp": ("recbox_amd.rechub.models.matching", ["STAMP"]),
     "models.matching.sine": ("recbox_amd.rechub.models.matching", ["SINE"]),
     "models.matching.gru4rec": ("recbox_amd.rechub.models.matching", ["GRU4Rec"]),
     "models.matching.narm": ("recbox_amd.rechub.models.matching", ["NARM"]),

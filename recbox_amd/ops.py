@@ -123,6 +123,11 @@ class config(object):
     # (profiles/gru/INDEX.md): 51 x / 24 x / 16 x at B = 4096, 12 x / 12 x / 9 x at B = 65 536 (H = 16 / 64 / 128, L = 50, two layers),
     # 23 x at NARM's form (B = 512, L = 20, H = 100): no shape class loses, so there is no width threshold.
     gru_fused = os.environ.get("RECBOX_AMD_GRU_FUSED", "1") != "0"
+    # additive attention pooling (rechub's NARM Eq. 6-8, STAMP Eq. 7-8): x W^T on the MFMA with the sigmoid, the v product, exp,
+    # the mask, the normalisation and the weighted row sum on chip (additive_attn_pool: csrc/rbx_addattn.hip) instead of a
+    # [B, L, H] product that is written, re-read three times and kept by autograd.  Off, or for what additive_attn_supported
+    # refuses: that composition (additive_attn_pool_torch).  Measurements: profiles/addattn/INDEX.md.
+    addattn_fused = os.environ.get("RECBOX_AMD_ADDATTN_FUSED", "1") != "0"
     # multi-task ranking (rechub's MMOE, CGC / PLE, AITM): mixing the expert outputs under the per-task gates as one launch
     # forward and one backward that read every expert row once for all gates (expert_mix: csrc/rbx_mix.hip) instead of
     # torch.cat into [B, E, H], a [B, E, H] product per gate that autograd keeps, and a sum.  Off, or for what
@@ -4721,6 +4726,126 @@ def gru(x, w_ih, w_hh, b_ih=None, b_hh=None, h0=None, lengths=None):
     if B == 0 or not _gru_fused_ok(x, w_ih, w_hh, b_ih, b_hh, h0):
         return gru_torch(x, w_ih, w_hh, b_ih, b_hh, h0, lengths)
     return _Gru.apply(x, w_ih, w_hh, b_ih, b_hh, h0, _gru_lengths(lengths, B, x.device))
+
+
+# ---- additive attention pooling: NARM / STAMP (csrc/rbx_addattn.hip) ---------------------------------------------------------
+ADDATTN_MAX_DIM = 128
+
+
+def additive_attn_supported(dim, hidden, seq_len):
+    """Whether the fused op takes this shape (rbx_addattn_supported): ``dim`` and ``hidden`` multiples of 4 in 4 .. 128,
+    ``seq_len`` >= 1.  What it refuses runs ``additive_attn_pool_torch``."""
+    return bool(lib.rbx_addattn_supported(int(dim), int(hidden), int(seq_len)))
+
+
+def additive_attn_pool_torch(x, w, ctx, v, mask=None, eps=0.0):
+    """The composition, with the arithmetic of narm.py:61-68, in plain ATen on whatever device the tensors live on:
+    ``q = sigmoid(x W^T + ctx) v``, ``e = exp(q) * mask``, ``alpha = e / max(sum_l e, eps)`` (``eps = 0``: the plain division),
+    ``out = sum_l alpha x``.  ``x`` [B, L, D], ``w`` [H, D], ``ctx`` [B, H] or None, ``v`` [H], ``mask`` [B, L] (nonzero =
+    valid) or None -> ``(out [B, D], alpha [B, L])``; ``alpha`` is returned detached.  Serves what the fused op refuses and
+    is what it is measured against."""
+    pre = torch.matmul(x, w.t())
+    if ctx is not None:
+        pre = pre + ctx.unsqueeze(1)
+    q = torch.matmul(torch.sigmoid(pre), v.reshape(-1, 1))                     # [B, L, 1]
+    e = torch.exp(q)
+    if mask is not None:
+        e = e * (mask != 0).reshape(x.shape[0], x.shape[1], 1)
+    total = e.sum(dim=1, keepdim=True)
+    alpha = e / (total.clamp_min(eps) if eps > 0 else total)
+    return (alpha * x).sum(1), alpha.squeeze(-1).detach()
+
+
+def _addattn_fused_ok(x, w, ctx, v):
+    """The refusals of ``additive_attn_pool`` that run the composition: the switch, a shape outside the kernels' range, CPU or
+    non-float32 tensors, an empty batch, an input whose rows are not contiguous, 16-byte aligned and a multiple of 4 apart."""
+    if not config.addattn_fused or x.dim() != 3 or x.shape[0] == 0:
+        return False
+    if not additive_attn_supported(x.shape[2], w.shape[0], x.shape[1]):
+        return False
+    if any(t is not None and (not t.is_cuda or t.dtype != torch.float32) for t in (x, w, ctx, v)):
+        return False
+    return (x.stride(2) == 1 and x.data_ptr() % 16 == 0 and x.stride(1) % 4 == 0 and x.stride(1) >= x.shape[2]
+            and x.stride(0) % 4 == 0 and x.stride(0) > 0)
+
+
+class _AddAttn(torch.autograd.Function):
+    """(out [B, D], alpha [B, L]) as ONE launch (rbx_addattn_fwd); backward = rbx_addattn_bwd for dx, dctx and dv, with the
+    sigmoid recomputed on chip, then one dense-path GEMM for dW over the transient dpre [B, L, H].  Saved: the inputs and
+    alpha -- nothing of B L H elements."""
+
+    @staticmethod
+    def forward(ctx_, x, w, c, v, mask, eps):
+        B, L, D = x.shape
+        H = w.shape[0]
+        dev = x.device
+        w = w.contiguous()
+        c = c.contiguous() if c is not None else None
+        v_shape = v.shape
+        v = v.reshape(H).contiguous()
+        if mask is not None:
+            _require_cuda(mask, "additive_attn_pool mask")
+            mask = mask.reshape(B, L)
+            if mask.dtype not in _MASK_CODE:
+                mask = mask.float() if mask.is_floating_point() else mask.long()
+            mask = mask.contiguous()
+        out = torch.empty((B, D), dtype=torch.float32, device=dev)
+        alpha = torch.empty((B, L), dtype=torch.float32, device=dev)
+        code = _MASK_CODE[mask.dtype] if mask is not None else 0
+        check(_timed(("addattn_fwd", B, L, D, H),
+                     lambda: lib.rbx_addattn_fwd(_ptr(x), x.stride(0), x.stride(1), _ptr(w), _ptr(c), _ptr(v), _ptr(mask), code,
+                                                 float(eps), B, L, D, H, _lib.RBX_F32, _ptr(out), _ptr(alpha), _stream())))
+        ctx_.save_for_backward(x, w, c, v, mask, alpha)
+        ctx_.eps, ctx_.v_shape = float(eps), v_shape
+        ctx_.mark_non_differentiable(alpha)
+        return out, alpha
+
+    @staticmethod
+    def backward(ctx_, dout, _dalpha):
+        x, w, c, v, mask, alpha = ctx_.saved_tensors
+        B, L, D = x.shape
+        H = w.shape[0]
+        dev = x.device
+        need = ctx_.needs_input_grad
+        dout = dout.float()
+        if dout.stride(1) != 1 or dout.data_ptr() % 16 != 0 or dout.stride(0) % 4 != 0 or dout.stride(0) < D:
+            dout = dout.contiguous()
+        dx = torch.empty((B, L, D), dtype=torch.float32, device=dev)
+        dctx = torch.empty((B, H), dtype=torch.float32, device=dev)
+        dv = torch.empty(H, dtype=torch.float32, device=dev)
+        dpre = torch.empty((B * L, H), dtype=torch.float32, device=dev) if need[1] else None
+        ws_bytes = lib.rbx_addattn_bwd_workspace_size(B, H)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        code = _MASK_CODE[mask.dtype] if mask is not None else 0
+        check(_timed(("addattn_bwd", B, L, D, H),
+                     lambda: lib.rbx_addattn_bwd(_ptr(dout), dout.stride(0), _ptr(x), x.stride(0), x.stride(1), _ptr(w), _ptr(c),
+                                                 _ptr(v), _ptr(mask), code, _ptr(alpha), ctx_.eps, B, L, D, H, _lib.RBX_F32,
+                                                 _ptr(dx), _ptr(dctx), _ptr(dv), _ptr(dpre), _ptr(ws), ws_bytes, _stream())))
+        dw = None
+        if need[1]:
+            x2 = x.reshape(B * L, D)                     # a view when the samples are evenly spaced, else a copy
+            if x2.stride(1) != 1:
+                x2 = x2.contiguous()
+            dw = torch.empty((H, D), dtype=torch.float32, device=dev)
+            _lin_dwdb(x2, w, dpre, dw, None)
+        return (dx if need[0] else None, dw, dctx if (c is not None and need[2]) else None,
+                dv.view(ctx_.v_shape) if need[3] else None, None, None)
+
+
+def additive_attn_pool(x, w, ctx, v, mask=None, eps=0.0):
+    """Additive attention pooling (NARM Eq. 6-8, STAMP Eq. 7-8) as one autograd node over rbx_addattn_fwd / _bwd: ``x``
+    [B, L, D], ``w`` [H, D], ``ctx`` [B, H] or None, ``v`` [H], ``mask`` [B, L] (bool / int32 / int64 / float32, nonzero =
+    valid) or None -> ``(out [B, D], alpha [B, L])`` with ``alpha = e / max(sum_l e, eps)``, ``e = exp(v . sigmoid(x W^T +
+    ctx)) * mask``.  ``alpha`` carries no gradient.  A shape or layout the kernels refuse (``additive_attn_supported``,
+    non-float32, oddly strided ``x``), an empty batch, CPU tensors and ``config.addattn_fused = False`` run
+    ``additive_attn_pool_torch``."""
+    if x.dim() != 3 or w.dim() != 2 or w.shape[1] != x.shape[2] or v.numel() != w.shape[0] \
+            or (ctx is not None and tuple(ctx.shape) != (x.shape[0], w.shape[0])):
+        raise RuntimeError("additive_attn_pool: x %s, w %s, ctx %s, v %s do not fit"
+                           % (tuple(x.shape), tuple(w.shape), tuple(ctx.shape) if ctx is not None else None, tuple(v.shape)))
+    if not _addattn_fused_ok(x, w, ctx, v):
+        return additive_attn_pool_torch(x, w, ctx, v.reshape(-1), mask, eps)
+    return _AddAttn.apply(x, w, ctx, v, mask, eps)
 
 
 

@@ -559,8 +559,9 @@ class NARM(torch.nn.Module):
     ``gru.*``, ``a_1``, ``a_2``, ``v``, ``b``).  The session lengths (non-zero ids per row; sessions are left-aligned) are
     counted on the device and handed to ``ops.gru`` as ``lengths``: no packing and no host copy (narm.py:49-50), so a step is
     capturable.  The reference's additive attention broadcasts the last state against the padded states in a way that needs
-    one full-length session per batch; for every such batch the outputs agree.  The attention (Eq. 6-8) and the bilinear
-    scoring (Eq. 10) are ATen and ``ops.linear``; dropout is ``ops.dropout`` (its Philox mask differs from torch's)."""
+    one full-length session per batch; for every such batch the outputs agree.  The attention (Eq. 6-8) is one
+    ``ops.additive_attn_pool`` call, the bilinear scoring (Eq. 10) is ``ops.linear``; dropout is ``ops.dropout`` (its Philox
+    mask differs from torch's)."""
 
     def __init__(self, item_history_feature, hidden_dim, emb_dropout_p, session_rep_dropout_p):
         super(NARM, self).__init__()
@@ -586,13 +587,64 @@ class NARM(torch.nn.Module):
         h, h_t = ops.gru(embs, self.gru.weight_ih_l0, self.gru.weight_hh_l0, self.gru.bias_ih_l0, self.gru.bias_hh_l0,
                          None, lengths)
         c_g = h_t                                                                            # Eq. 5 [B, H]
-        # Eq. 8: similarity between the final state and every state
-        q = ops.linear(torch.sigmoid(ops.linear(h_t, self.a_1).unsqueeze(1) + ops.linear(h, self.a_2)), self.v.t())
-        # Eq. 7
-        alpha = torch.exp(q) * value_mask.unsqueeze(-1)
-        alpha = alpha / alpha.sum(dim=1, keepdim=True)
-        c_l = (alpha * h).sum(1)                                                             # Eq. 6
-        c = self._drop(self.session_rep_dropout, torch.cat((c_g, c_l), dim=1))               # Eq. 9
+        # Eq. 6-8: similarity between the final state and every state, the masked weights and the weighted sum, one op
+        c_l, _ = ops.additive_attn_pool(h, self.a_2, ops.linear(h_t, self.a_1), self.v[:, 0], value_mask, 0.0)
+        c =self._drop(self.session_rep_dropout, torch.cat((c_g, c_l), dim=1))               # Eq. 9
         # Eq. 10 [B, V].  The table is also read by the lookup above, so autograd adds two gradients for it on the current stream:
         # it goes in as a view (not a leaf), which keeps this Linear's dW off the side stream (ops.config.dw_beside_lookup)
         return ops.linear(ops.linear(c, self.b), self.item_emb.weight.view_as(self.item_emb.weight))
+
+
+class STAMP(torch.nn.Module):
+    """``torch_rechub.models.matching.STAMP`` (stamp.py:15-83): same constructor, initialisation order and ``state_dict`` keys
+    (``item_emb.weight``, ``w_0``, ``w_1_t``, ``w_2_t``, ``w_3_t``, ``b_a``, ``f_s.1.*``, ``f_t.1.*``); as there, the
+    ``normal_`` initialisation of the table overwrites its padding row.  The session lengths (non-zero ids per row; sessions
+    are left-aligned) are counted on the device; the last click is looked up at ``(lengths - 1).clamp_min(0)``, so an empty
+    session does not fault (the reference's gather index is -1 there; its scores here are unspecified).  The general
+    interest m_s (Eq. 2) is the masked pooling op, the attention (Eq. 7-8) one ``ops.additive_attn_pool`` call on the raw
+    embeddings with ``eps = 1e-12`` (``F.normalize(p=1)`` over non-negative terms): masked positions get alpha = 0, which is
+    the ``* value_mask`` of stamp.py:60.  ``f_s``, ``f_t`` and the catalogue scores are ``ops.linear``."""
+
+    def __init__(self, item_history_feature, weight_std, emb_std):
+        super(STAMP, self).__init__()
+        self.item_history_feature = item_history_feature
+        n_items, item_emb_dim = item_history_feature.vocab_size, item_history_feature.embed_dim
+        self.item_emb = nn.Embedding(n_items, item_emb_dim, padding_idx=0)
+        self.w_0 = nn.Parameter(torch.zeros(item_emb_dim, 1))
+        self.w_1_t = nn.Parameter(torch.zeros(item_emb_dim, item_emb_dim))
+        self.w_2_t = nn.Parameter(torch.zeros(item_emb_dim, item_emb_dim))
+        self.w_3_t = nn.Parameter(torch.zeros(item_emb_dim, item_emb_dim))
+        self.b_a = nn.Parameter(torch.zeros(item_emb_dim))
+        for p in (self.w_0, self.w_1_t, self.w_2_t, self.w_3_t):
+            nn.init.normal_(p, std=weight_std)
+        self.f_s = nn.Sequential(nn.Tanh(), nn.Linear(item_emb_dim, item_emb_dim))
+        self.f_t = nn.Sequential(nn.Tanh(), nn.Linear(item_emb_dim, item_emb_dim))
+        self.emb_std = emb_std
+        self.apply(self._init_module_weights)
+
+    def _init_module_weights(self, module):
+        if isinstance(module, nn.Linear):
+            module.weight.data.normal_(std=self.emb_std)
+            if module.bias is not None:
+                module.bias.data.zero_()
+        elif isinstance(module, nn.Embedding):
+            module.weight.data.normal_(std=self.emb_std)
+
+    def forward(self, input_dict):
+        ids = input_dict[self.item_history_feature.name]
+        ops._require_cuda(ids, "STAMP input")
+        value_mask = (ids != 0)
+        value_counts = value_mask.sum(dim=1, keepdim=True)                                   # [B, 1], stays on the device
+        embs = ops_position(self.item_emb, ids)                                              # [B, L, D], raw rows
+        # the latest click: its row is already among the looked-up ones (one lookup and one table gradient, not two)
+        last = (value_counts - 1).clamp_min(0).unsqueeze(-1).expand(-1, 1, embs.shape[2])
+        x_t = torch.gather(embs, 1, last).squeeze(1)                                         # [B, D]
+        m_s = ops.pool(embs, value_mask, True, ops.DENOM_MASK, 0.0)                          # Eq. 2 [B, D]
+        # Eq. 7-8: the context of the attention is what does not depend on the position
+        ctx = ops.linear(x_t, self.w_2_t.t(), self.b_a) + ops.linear(m_s, self.w_3_t.t())
+        m_a, _ = ops.additive_attn_pool(embs, self.w_1_t.t(), ctx, self.w_0[:, 0], value_mask, 1e-12)
+        m_a = m_a + m_s
+        h_s = ops.linear(torch.tanh(m_a), self.f_s[1].weight, self.f_s[1].bias)              # Eq. 3
+        h_t = ops.linear(torch.tanh(x_t), self.f_t[1].weight, self.f_t[1].bias)              # Eq. 9
+        # Eq. 4 [B, V]: the table goes in as a view, as in NARM (it is also read by the lookups above)
+        return ops.linear(h_s * h_t, self.item_emb.weight.view_as(self.item_emb.weight))
