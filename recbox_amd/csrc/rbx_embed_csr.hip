@@ -41,8 +41,10 @@
 // reads bag = map[position] and keeps dY[bag, c] where argpos[bag, c] names that position -- WeightedBagPolicy with a mask
 // instead of a factor.  argpos is only ever compared, never used as an address.
 // Host side.  classify_bags sorts a call's descriptors into (float4 | scalar) x (unweighted | weighted) launches and
-// refuses a dim no lane group holds before anything is written; csr_forward serves the four forward entry points and
-// csr_weight_grad the two weight-gradient ones, the long form being a parameter of both.
+// refuses a dim no lane group holds before anything is written; csr_forward serves the four sum / mean forward entry
+// points, csr_weight_grad the two weight-gradient ones and csr_forward_max the max forward: each keeps its own checks and
+// hands its launches to walk_phases (lane groups, segments, finish).  position_reduce is the shared body of _bwd_weighted
+// and _bwd_max.
 #include "rbx_bwd_common.h"
 #include "rbx_rowfrag.h"
 #include "rbx_segreduce.h"
@@ -879,11 +881,34 @@ static int launch_csr_keys(const CsrPlan& c, char* ws, int* status, hipStream_t 
   return check_launch("csr_keys_kernel");
 }
 
-// ---- weighted reduce: a lookup contributes w[position] * dY[map[position], slot] --------------------------------------
-// GenericPolicy for pairs whose value is a position (csr_keys_kernel<RB, true>): the bag comes from the lookup -> bag map
-// of the sort, the factor from the descriptor's weight array (NULL: 1).  prefetch / flush are GenericPolicy's.
-struct WeightedBagPolicy {
+// ---- the position-valued reduces -----------------------------------------------------------------------------------------
+// What GenericPolicy (rbx_embed_bwd.hip) does around its fetch, for the two policies whose pairs name a position
+// (csr_keys_kernel<RB, true>): no count, the factor as fetched, the old gradient row read when the call accumulates, one
+// store per row.  `A` is the policy's Args; only Args and fetch are a policy's own.
+struct BagPolicyBase {
   static constexpr bool kHasCount = false;
+  template <class A>
+  static __device__ __forceinline__ float weight(const A&, float w) { return w; }
+  template <class A, class F>
+  static __device__ __forceinline__ void prefetch(const A& a, const RedField& fd, unsigned row, int lane_g, F& pre) {
+    if (a.accumulate) pre.add_from(fd.grad + static_cast<size_t>(row) * fd.dim, fd.dim, lane_g);
+  }
+  template <class A, class F>
+  static __device__ __forceinline__ void prefetch_raw(const A& a, const RedField& fd, unsigned row, int lane_g, F& pre) {
+    if (a.accumulate) pre.load_from(fd.grad + static_cast<size_t>(row) * fd.dim, fd.dim, lane_g);
+  }
+  template <class A, class F>
+  static __device__ __forceinline__ void flush(const A&, const RedField& fd, unsigned row, const F& acc, float, const F& pre,
+                                               int lane_g) {
+    F out = acc;
+    frag_add(out, pre);
+    out.store_nt(fd.grad + static_cast<size_t>(row) * fd.dim, fd.dim, lane_g);
+  }
+};
+
+// weighted reduce: a lookup contributes w[position] * dY[map[position], slot] -- the bag comes from the lookup -> bag map of
+// the sort, the factor from the descriptor's weight array (NULL: 1)
+struct WeightedBagPolicy : BagPolicyBase {
   struct Args {
     const float* dout;
     long long stride_b;
@@ -899,31 +924,14 @@ struct WeightedBagPolicy {
     w = (wp != nullptr) ? wp[pos] : 1.0f;
     frag.load_from(a.dout + static_cast<long long>(bag) * a.stride_b + fd.out_off, fd.dim, lane_g);
   }
-  static __device__ __forceinline__ float weight(const Args&, float w) { return w; }
-  template <class F>
-  static __device__ __forceinline__ void prefetch(const Args& a, const RedField& fd, unsigned row, int lane_g, F& pre) {
-    if (a.accumulate) pre.add_from(fd.grad + static_cast<size_t>(row) * fd.dim, fd.dim, lane_g);
-  }
-  template <class F>
-  static __device__ __forceinline__ void prefetch_raw(const Args& a, const RedField& fd, unsigned row, int lane_g, F& pre) {
-    if (a.accumulate) pre.load_from(fd.grad + static_cast<size_t>(row) * fd.dim, fd.dim, lane_g);
-  }
-  template <class F>
-  static __device__ __forceinline__ void flush(const Args&, const RedField& fd, unsigned row, const F& acc, float, const F& pre,
-                                               int lane_g) {
-    F out = acc;
-    frag_add(out, pre);
-    out.store_nt(fd.grad + static_cast<size_t>(row) * fd.dim, fd.dim, lane_g);
-  }
 };
 
-// ---- max reduce: a lookup contributes dY[map[position], c] where argpos[that bag, c] names its position -------------------
-// WeightedBagPolicy with a mask instead of a factor.  The mask is applied in place, right behind the two loads: a second
+// max reduce: a lookup contributes dY[map[position], c] where argpos[that bag, c] names its position -- WeightedBagPolicy
+// with a mask instead of a factor.  The mask is applied in place, right behind the two loads: a second
 // per-lookup fragment for the argpos slice would hold U * NV * 4 more registers than RBX_REDUCE_WAVES leaves at the wide
 // forms, and this reduce is on no measured step.  argpos is compared with the position and never used as an address: no
 // content of that buffer makes a kernel read out of bounds.
-struct MaxBagPolicy {
-  static constexpr bool kHasCount = false;
+struct MaxBagPolicy : BagPolicyBase {
   struct Args {
     const float* dout;
     long long stride_b;
@@ -956,22 +964,6 @@ struct MaxBagPolicy {
         frag.a[u] = arg[e] == me ? frag.a[u] : 0.f;
       }
     }
-  }
-  static __device__ __forceinline__ float weight(const Args&, float w) { return w; }
-  template <class F>
-  static __device__ __forceinline__ void prefetch(const Args& a, const RedField& fd, unsigned row, int lane_g, F& pre) {
-    if (a.accumulate) pre.add_from(fd.grad + static_cast<size_t>(row) * fd.dim, fd.dim, lane_g);
-  }
-  template <class F>
-  static __device__ __forceinline__ void prefetch_raw(const Args& a, const RedField& fd, unsigned row, int lane_g, F& pre) {
-    if (a.accumulate) pre.load_from(fd.grad + static_cast<size_t>(row) * fd.dim, fd.dim, lane_g);
-  }
-  template <class F>
-  static __device__ __forceinline__ void flush(const Args&, const RedField& fd, unsigned row, const F& acc, float, const F& pre,
-                                               int lane_g) {
-    F out = acc;
-    frag_add(out, pre);
-    out.store_nt(fd.grad + static_cast<size_t>(row) * fd.dim, fd.dim, lane_g);
   }
 };
 // 16 floats per lane (D > 512): with 4 lookups in flight the masked fetch spilled 264 B per lane at RBX_REDUCE_WAVES; 2 fit
@@ -1196,6 +1188,30 @@ static int classify_bags(const rbx_bag_t* bags, const BagPack& all, int n, const
   return RBX_OK;
 }
 
+// The launch sequence of every walk, in its fixed order: the lane-group launches of the classes in ascending order (kWalk,
+// or kHandOff when `on`: some bag of the call can take the long form, and these launches fill the record list); with `on`
+// the classes' segment launches, over every descriptor of the call by index (LongRec::desc), and then `finish`.
+// launch(k, mode, pack, count, arrays, la) picks the op of class k and builds its Args.
+template <class T, class Launch, class Finish>
+static int walk_phases(const BagClasses<T>& c, const BagPack& all, int n_bags, LongArgs la, bool on, Launch launch, Finish finish) {
+  for (int phase = 0; phase < (on ? 2 : 1); ++phase) {
+    const int mode = phase == 1 ? kSegments : on ? kHandOff : kWalk;
+    for (int k = 0; k < 4; ++k) {
+      if (c.cnt[k] == 0) continue;
+      la.cls = k;
+      const int rc = mode == kSegments ? launch(k, mode, all, n_bags, c.whole, la) : launch(k, mode, c.pack[k], c.cnt[k], c.ptr[k], la);
+      if (rc != RBX_OK) return rc;
+    }
+  }
+  return on ? finish(la) : RBX_OK;
+}
+
+// the finish kernels' grid: a wave per record, grid-striding beyond two workgroups per CU
+static dim3 finish_grid(const LongPlan& lp) {
+  const long long fb = (static_cast<long long>(lp.cap_bags) + 3) / 4;
+  return dim3(static_cast<unsigned>(fb > kCUs * 2 ? kCUs * 2 : fb));
+}
+
 // The four forward entry points.  weighted_call: d_weights is looked at (NULL entries walk unweighted, without a row
 // scale: the caller passes none); has_long: the `_long` calls, whose bags of >= threshold ids go out in segments.
 static int csr_forward(const rbx_bag_t* bags, int n_bags, int64_t batch, bool has_long, int64_t threshold,
@@ -1224,32 +1240,19 @@ static int csr_forward(const rbx_bag_t* bags, int n_bags, int64_t batch, bool ha
     if (batch == 0) return RBX_OK;
     la = long_args(lp, d_workspace);
   }
-  // lane-group launches of every class first (they fill the list), then the classes' segment launches, then one finish
-  for (int k = 0; k < 4; ++k) {
-    if (c.cnt[k] == 0) continue;
-    la.cls = k;
-    const int mode = on ? kHandOff : kWalk;
-    rc = k < 2 ? bag_walk<PoolOp>(k % 2 == 0, mode, c.units[k], c.pack[k], c.cnt[k], batch, {d_out, out_stride_b, d_row_scale},
-                                  d_status, s, la)
-               : bag_walk<WeightedPoolOp>(k % 2 == 0, mode, c.units[k], c.pack[k], c.cnt[k], batch,
-                                          {c.ptr[k], d_out, out_stride_b}, d_status, s, la);
-    if (rc != RBX_OK) return rc;
-  }
-  if (!on) return RBX_OK;
-  for (int k = 0; k < 4; ++k) {                             // every descriptor by index (LongRec::desc); the finish scales
-    if (c.cnt[k] == 0) continue;
-    la.cls = k;
-    rc = k < 2 ? bag_walk<PoolOp>(k % 2 == 0, kSegments, c.units[k], all, n_bags, batch, {d_out, out_stride_b, nullptr}, d_status,
-                                  s, la)
-               : bag_walk<WeightedPoolOp>(k % 2 == 0, kSegments, c.units[k], all, n_bags, batch, {c.whole, d_out, out_stride_b},
-                                          d_status, s, la);
-    if (rc != RBX_OK) return rc;
-  }
-  long long fb = (static_cast<long long>(lp.cap_bags) + 3) / 4;
-  if (fb > kCUs * 2) fb = kCUs * 2;
-  hipLaunchKernelGGL(csr_long_finish_kernel, dim3(static_cast<unsigned>(fb)), dim3(256), 0, s, all, n_bags,
-                     static_cast<long long>(batch), d_out, static_cast<long long>(out_stride_b), d_row_scale, la);
-  return check_launch("csr_long_finish_kernel");
+  return walk_phases(
+      c, all, n_bags, la, on,
+      [&](int k, int mode, const BagPack& pack, int cnt, const BagWeights& w, const LongArgs& la) {
+        if (k < 2)                                          // (a segment stores no row scale: the finish scales)
+          return bag_walk<PoolOp>(k % 2 == 0, mode, c.units[k], pack, cnt, batch,
+                                  {d_out, out_stride_b, mode == kSegments ? nullptr : d_row_scale}, d_status, s, la);
+        return bag_walk<WeightedPoolOp>(k % 2 == 0, mode, c.units[k], pack, cnt, batch, {w, d_out, out_stride_b}, d_status, s, la);
+      },
+      [&](const LongArgs& la) {
+        hipLaunchKernelGGL(csr_long_finish_kernel, finish_grid(lp), dim3(256), 0, s, all, n_bags, static_cast<long long>(batch),
+                           d_out, static_cast<long long>(out_stride_b), d_row_scale, la);
+        return check_launch("csr_long_finish_kernel");
+      });
 }
 
 // Both weight-gradient entry points; a descriptor takes part when it has somewhere to put its gradient.
@@ -1283,21 +1286,12 @@ static int csr_weight_grad(const rbx_bag_t* bags, int n_bags, int64_t batch, boo
         hipMemsetAsync(d_dweights[i], 0, static_cast<size_t>(bags[i].nnz) * 4, s) != hipSuccess)
       return fail(RBX_ERR_LAUNCH, "clearing a weight gradient failed");
   if (batch == 0) return RBX_OK;
-  for (int k = 0; k < 2; ++k) {
-    if (c.cnt[k] == 0) continue;
-    la.cls = k;
-    rc = bag_walk<WeightGradOp>(k == 0, on ? kHandOff : kWalk, c.units[k], c.pack[k], c.cnt[k], batch,
-                                {c.ptr[k], d_dout, out_stride_b}, d_status, s, la);
-    if (rc != RBX_OK) return rc;
-  }
-  for (int k = 0; on && k < 2; ++k) {                      // the same segment tasks, nothing to combine
-    if (c.cnt[k] == 0) continue;
-    la.cls = k;
-    rc = bag_walk<WeightGradOp>(k == 0, kSegments, c.units[k], all, n_bags, batch, {c.whole, d_dout, out_stride_b}, d_status, s,
-                                la);
-    if (rc != RBX_OK) return rc;
-  }
-  return RBX_OK;
+  return walk_phases(
+      c, all, n_bags, la, on,
+      [&](int k, int mode, const BagPack& pack, int cnt, const BagWeightGrads& dw, const LongArgs& la) {
+        return bag_walk<WeightGradOp>(k == 0, mode, c.units[k], pack, cnt, batch, {dw, d_dout, out_stride_b}, d_status, s, la);
+      },
+      [](const LongArgs&) { return RBX_OK; });              // the same segment tasks, nothing to combine
 }
 
 // The max forward.  Its workspace is the long workspace with one int32 partial argpos row per segment slot behind it.
@@ -1319,7 +1313,7 @@ static int csr_forward_max(const rbx_bag_t* bags, int n_bags, int64_t batch, int
   if (batch == 0) return RBX_OK;
   if (d_out == nullptr) return fail(RBX_ERR_INVALID, "d_out is NULL");
   if (d_argpos == nullptr) return fail(RBX_ERR_INVALID, "d_argpos is NULL");
-  BagClasses<const float> c;
+  BagClasses<const float> c;                              // two launch classes here: float4 and scalar
   rc = classify_bags<const float>(bags, all, n_bags, d_out, out_stride_b, nullptr, false, &c);
   if (rc != RBX_OK) return rc;
   LongArgs la = {};
@@ -1336,25 +1330,48 @@ static int csr_forward_max(const rbx_bag_t* bags, int n_bags, int64_t batch, int
   }
   const int arg_vec = (arg_stride_b % 4 == 0 && (reinterpret_cast<uintptr_t>(d_argpos) & 15) == 0) ? 1 : 0;
   const MaxPoolOp::Args args = {d_out, out_stride_b, d_argpos, arg_stride_b, parg, arg_vec};
-  for (int k = 0; k < 2; ++k) {                            // two launch classes here: float4 and scalar
-    if (c.cnt[k] == 0) continue;
-    la.cls = k;
-    rc = bag_walk<MaxPoolOp>(k == 0, on ? kHandOff : kWalk, c.units[k], c.pack[k], c.cnt[k], batch, args, d_status, s, la);
-    if (rc != RBX_OK) return rc;
-  }
-  if (!on) return RBX_OK;
-  for (int k = 0; k < 2; ++k) {
-    if (c.cnt[k] == 0) continue;
-    la.cls = k;
-    rc = bag_walk<MaxPoolOp>(k == 0, kSegments, c.units[k], all, n_bags, batch, args, d_status, s, la);
-    if (rc != RBX_OK) return rc;
-  }
-  long long fb = (static_cast<long long>(lp.cap_bags) + 3) / 4;
-  if (fb > kCUs * 2) fb = kCUs * 2;
-  hipLaunchKernelGGL(csr_long_max_finish_kernel, dim3(static_cast<unsigned>(fb)), dim3(256), 0, s, all, n_bags,
-                     static_cast<long long>(batch), d_out, static_cast<long long>(out_stride_b), d_argpos,
-                     static_cast<long long>(arg_stride_b), parg, la);
-  return check_launch("csr_long_max_finish_kernel");
+  return walk_phases(
+      c, all, n_bags, la, on,
+      [&](int k, int mode, const BagPack& pack, int cnt, const BagWeights&, const LongArgs& la) {
+        return bag_walk<MaxPoolOp>(k == 0, mode, c.units[k], pack, cnt, batch, args, d_status, s, la);
+      },
+      [&](const LongArgs& la) {
+        hipLaunchKernelGGL(csr_long_max_finish_kernel, finish_grid(lp), dim3(256), 0, s, all, n_bags,
+                           static_cast<long long>(batch), d_out, static_cast<long long>(out_stride_b), d_argpos,
+                           static_cast<long long>(arg_stride_b), parg, la);
+        return check_launch("csr_long_max_finish_kernel");
+      });
+}
+
+// The epilogue of the two position-valued reduces (rbx_embed_csr_bwd_weighted, rbx_embed_csr_bwd_max), behind their NULL
+// checks: the plan, `pools_ok()` (which pools the call takes), the workspace test, the Args fields every such policy has,
+// then `fill(p, &args, &vec)` for the policy's own fields and its say on the float4 form.
+template <class Policy, class Check, class Fill>
+static int position_reduce(const rbx_bag_t* bags, int n_bags, int64_t batch, const float* d_dout, int64_t out_stride_b,
+                           int accumulate, void* d_workspace, size_t workspace_bytes, hipStream_t s, Check pools_ok, Fill fill) {
+  CsrPlan c;
+  int rc = csr_plan(bags, n_bags, batch, d_dout, out_stride_b, &c);
+  if (rc != RBX_OK) return rc;
+  rc = pools_ok();
+  if (rc != RBX_OK) return rc;
+  const BwdPlan& p = c.p;
+  if (p.n_lookups == 0 || batch == 0) return RBX_OK;
+  if (d_workspace == nullptr || workspace_bytes < c.bytes)
+    return fail(RBX_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, c.bytes);
+  char* ws = static_cast<char*>(d_workspace);
+  typename Policy::Args args = {};
+  args.dout = d_dout;
+  args.stride_b = out_stride_b;
+  args.map = reinterpret_cast<const int*>(ws + c.off_map);
+  args.accumulate = accumulate;
+  for (int k = 0; k < p.n_cat; ++k) args.lk_off[p.red.f[k].slot] = p.keys.f[k].lk_off;   // by the descriptor's index in `bags`
+  bool vec = p.vec;
+  rc = fill(p, &args, &vec);
+  if (rc != RBX_OK) return rc;
+  const int cur = p.passes & 1;
+  const unsigned* keys = reinterpret_cast<const unsigned*>(ws + p.off_keys[cur]);
+  const unsigned* vals = reinterpret_cast<const unsigned*>(ws + p.off_vals[cur]);
+  return vec ? dispatch_reduce<Policy, true>(p, args, keys, vals, ws, s) : dispatch_reduce<Policy, false>(p, args, keys, vals, ws, s);
 }
 
 }  // namespace rbx
@@ -1426,35 +1443,19 @@ extern "C" int rbx_embed_csr_bwd_weighted(const rbx_bag_t* bags, int32_t n_bags,
                                           size_t workspace_bytes, void* stream) {
   using namespace rbx;
   if (d_dout == nullptr) return fail(RBX_ERR_INVALID, "d_dout is NULL");
-  int rc = check_no_trained_mean(bags, n_bags, "rbx_embed_csr_bwd_weighted");
+  const int rc = check_no_trained_mean(bags, n_bags, "rbx_embed_csr_bwd_weighted");
   if (rc != RBX_OK) return rc;
-  CsrPlan c;
-  rc = csr_plan(bags, n_bags, batch, d_dout, out_stride_b, &c);
-  if (rc != RBX_OK) return rc;
-  rc = check_no_max(bags, n_bags, "rbx_embed_csr_bwd_weighted");
-  if (rc != RBX_OK) return rc;
-  rc = check_weighted_pools(bags, n_bags, reinterpret_cast<const void* const*>(d_weights), "a weight array");
-  if (rc != RBX_OK) return rc;
-  const BwdPlan& p = c.p;
-  if (p.n_lookups == 0 || batch == 0) return RBX_OK;
-  if (d_workspace == nullptr || workspace_bytes < c.bytes)
-    return fail(RBX_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, c.bytes);
-  char* ws = static_cast<char*>(d_workspace);
-  WeightedBagPolicy::Args args = {};
-  args.dout = d_dout;
-  args.stride_b = out_stride_b;
-  args.map = reinterpret_cast<const int*>(ws + c.off_map);
-  args.accumulate = accumulate;
-  for (int k = 0; k < p.n_cat; ++k) {
-    const int i = p.red.f[k].slot;                         // the descriptor's index in `bags`
-    args.lk_off[i] = p.keys.f[k].lk_off;
-    args.w[i] = d_weights != nullptr ? d_weights[i] : nullptr;
-  }
-  const int cur = p.passes & 1;
-  const unsigned* keys = reinterpret_cast<const unsigned*>(ws + p.off_keys[cur]);
-  const unsigned* vals = reinterpret_cast<const unsigned*>(ws + p.off_vals[cur]);
-  return p.vec ? dispatch_reduce<WeightedBagPolicy, true>(p, args, keys, vals, ws, as_stream(stream))
-               : dispatch_reduce<WeightedBagPolicy, false>(p, args, keys, vals, ws, as_stream(stream));
+  return position_reduce<WeightedBagPolicy>(
+      bags, n_bags, batch, d_dout, out_stride_b, accumulate, d_workspace, workspace_bytes, as_stream(stream),
+      [&] {
+        const int rc = check_no_max(bags, n_bags, "rbx_embed_csr_bwd_weighted");
+        if (rc != RBX_OK) return rc;
+        return check_weighted_pools(bags, n_bags, reinterpret_cast<const void* const*>(d_weights), "a weight array");
+      },
+      [&](const BwdPlan& p, WeightedBagPolicy::Args* args, bool*) {
+        for (int k = 0; d_weights != nullptr && k < p.n_cat; ++k) args->w[p.red.f[k].slot] = d_weights[p.red.f[k].slot];
+        return RBX_OK;
+      });
 }
 
 extern "C" int rbx_embed_csr_weight_grad(const rbx_bag_t* bags, int32_t n_bags, int64_t batch, const float* d_dout,
@@ -1513,32 +1514,17 @@ extern "C" int rbx_embed_csr_bwd_max(const rbx_bag_t* bags, int32_t n_bags, int6
   using namespace rbx;
   if (d_dout == nullptr) return fail(RBX_ERR_INVALID, "d_dout is NULL");
   if (d_argpos == nullptr) return fail(RBX_ERR_INVALID, "d_argpos is NULL");
-  CsrPlan c;
-  int rc = csr_plan(bags, n_bags, batch, d_dout, out_stride_b, &c);
-  if (rc != RBX_OK) return rc;
-  rc = check_all_max(bags, n_bags, "rbx_embed_csr_bwd_max");
-  if (rc != RBX_OK) return rc;
-  const BwdPlan& p = c.p;
-  if (p.n_lookups == 0 || batch == 0) return RBX_OK;
-  if (d_workspace == nullptr || workspace_bytes < c.bytes)
-    return fail(RBX_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, c.bytes);
-  char* ws = static_cast<char*>(d_workspace);
-  MaxBagPolicy::Args args = {};
-  args.dout = d_dout;
-  args.stride_b = out_stride_b;
-  args.argpos = d_argpos;
-  args.arg_stride = arg_stride_b;
-  args.map = reinterpret_cast<const int*>(ws + c.off_map);
-  args.accumulate = accumulate;
-  for (int k = 0; k < p.n_cat; ++k) args.lk_off[p.red.f[k].slot] = p.keys.f[k].lk_off;   // by the descriptor's index in `bags`
-  const int cur = p.passes & 1;
-  const unsigned* keys = reinterpret_cast<const unsigned*>(ws + p.off_keys[cur]);
-  const unsigned* vals = reinterpret_cast<const unsigned*>(ws + p.off_vals[cur]);
-  // the float4 form reads argpos in 16-byte vectors as well
-  const bool vec = p.vec && arg_stride_b % 4 == 0 && (reinterpret_cast<uintptr_t>(d_argpos) & 15) == 0;
-  if (!vec && pow2_ceil(p.max_dim) > 256)
-    return fail(RBX_ERR_UNSUPPORTED, "embedding dim %d too large for one lane group (scalar units: d_argpos is not 16-byte aligned "
-                "or arg_stride_b no multiple of 4)", p.max_dim);
-  return vec ? dispatch_reduce<MaxBagPolicy, true>(p, args, keys, vals, ws, as_stream(stream))
-             : dispatch_reduce<MaxBagPolicy, false>(p, args, keys, vals, ws, as_stream(stream));
+  return position_reduce<MaxBagPolicy>(
+      bags, n_bags, batch, d_dout, out_stride_b, accumulate, d_workspace, workspace_bytes, as_stream(stream),
+      [&] { return check_all_max(bags, n_bags, "rbx_embed_csr_bwd_max"); },
+      [&](const BwdPlan& p, MaxBagPolicy::Args* args, bool* vec) -> int {
+        args->argpos = d_argpos;
+        args->arg_stride = arg_stride_b;
+        // the float4 form reads argpos in 16-byte vectors as well
+        *vec = p.vec && arg_stride_b % 4 == 0 && (reinterpret_cast<uintptr_t>(d_argpos) & 15) == 0;
+        if (!*vec && pow2_ceil(p.max_dim) > 256)
+          return fail(RBX_ERR_UNSUPPORTED, "embedding dim %d too large for one lane group (scalar units: d_argpos is not 16-byte "
+                      "aligned or arg_stride_b no multiple of 4)", p.max_dim);
+        return RBX_OK;
+      });
 }

@@ -757,8 +757,7 @@ class BagPlan(object):
         self.width = int(width) if width is not None else max(s.out_off + s.dim for s in self.specs)
         self.arr = (_lib.rbx_bag_t * self.n)()
         self.needs_row_scale = any(s.pool in (POOL_MEAN_VALUE, POOL_MEAN_ID) for s in self.specs)
-        self._long_ws = None                               # workspace of the long-bag calls (long_workspace)
-        self._max_ws = None                                # ... and of the max forward (max_workspace)
+        self._long_ws = self._max_ws = None                # workspace("long"): of the long-bag calls, ("max"): of the max forward
         self.is_max = any(s.pool == POOL_MAX for s in self.specs)
         for s in self.specs:
             if self.is_max and s.pool != POOL_MAX:
@@ -778,10 +777,10 @@ class BagPlan(object):
         for f, s, g in zip(self.arr, self.specs, bags):
             if not isinstance(g, Bags):
                 raise TypeError("feature '%s': expected ops.Bags, got %s" % (s.name, type(g).__name__))
-            if getattr(g, "weights", None) is not None and s.pool == POOL_MAX:
+            if g.weights is not None and s.pool == POOL_MAX:
                 raise NotImplementedError("feature '%s': per_sample_weights was not None; per-sample weights go with the sum "
                                           "pools only, not with POOL_MAX" % s.name)
-            if getattr(g, "weights", None) is not None and self.needs_row_scale:
+            if g.weights is not None and self.needs_row_scale:
                 if s.pool in (POOL_MEAN_VALUE, POOL_MEAN_ID):
                     raise NotImplementedError("feature '%s': per-sample weights go with the sum pools only; weighted mean "
                                               "pools are not implemented" % s.name)
@@ -812,114 +811,101 @@ class BagPlan(object):
             g = grads[s.param] if grads is not None else None
             f.grad = g.data_ptr() if g is not None else None
 
-    def long_workspace(self, B, threshold, dev):
-        """(tensor, bytes) for the ``_long`` calls over the bags bound now: owned by the plan, regrown when nnz or B asks for
-        more (warm a plan up before a capture, as the capture tests do: a replay then uses the buffer of the warm-up)."""
-        need = lib.rbx_embed_csr_fwd_long_workspace_size(self.arr, self.n, B, threshold)
+    def workspace(self, which, B, threshold, dev):
+        """(tensor, bytes) of the plan's own workspace "long" (the ``_long`` calls) or "max" (rbx_embed_csr_fwd_max: partial argpos
+        rows behind it) for the bags bound now, regrown with headroom when nnz or B asks for more (warm a plan up before a
+        capture, as the capture tests do: a replay then uses the buffer of the warm-up)."""
+        need = (lib.rbx_embed_csr_fwd_max_workspace_size(self.arr, self.n, B, threshold) if which == "max" else
+                lib.rbx_embed_csr_fwd_long_workspace_size(self.arr, self.n, B, threshold))
         need = max(need, 256)                              # (0: descriptors the call itself refuses, with its own message)
-        ws = self._long_ws
+        ws = getattr(self, "_%s_ws" % which)
         if ws is None or ws.device != dev or ws.numel() < need:
-            ws = self._long_ws = torch.empty(need + need // 4, dtype=torch.uint8, device=dev)
-        return ws, ws.numel()
-
-    def max_workspace(self, B, threshold, dev):
-        """``long_workspace`` for rbx_embed_csr_fwd_max (the partial argpos rows behind it); owned by the plan the same way."""
-        need = max(lib.rbx_embed_csr_fwd_max_workspace_size(self.arr, self.n, B, threshold), 256)
-        ws = self._max_ws
-        if ws is None or ws.device != dev or ws.numel() < need:
-            ws = self._max_ws = torch.empty(need + need // 4, dtype=torch.uint8, device=dev)
+            ws = torch.empty(need + need // 4, dtype=torch.uint8, device=dev)
+            setattr(self, "_%s_ws" % which, ws)
         return ws, ws.numel()
 
 
 class _EmbedBags(torch.autograd.Function):
-    """out[B, width] = pooled gather over ragged bags (rbx_embed_csr_fwd); backward = the sorted segmented scatter-add
-    over the lookups that exist (rbx_embed_csr_sort in the forward, on the current stream; rbx_embed_csr_bwd).  Plain
-    autograd semantics: freshly zeroed dense gradients (or, for a table another lookup of the pass has already written,
-    that node's gradient: config.share_table_grads).  No host sync beyond the id check config.check_ids asks for.
+    """out[B, width] = pooled gather over ragged bags; backward = the sorted segmented scatter-add over the lookups that
+    exist.  Plain autograd semantics: freshly zeroed dense gradients (or, for a table another lookup of the pass has already
+    written, that node's gradient: config.share_table_grads).  No host sync beyond the id check config.check_ids asks for.
     With ``config.reuse_grad_buffers == "all"`` the node works as _EmbedLookup does: a _GradPool kept on the plan holds ONE
-    persistent dense gradient per table, the sort runs on the side stream behind rbx_embed_csr_rezero of the rows the
-    previous step stored, and the backward stores into the pool's views (every guard of the pool applies).  With
-    ``config.track_touched_rows`` a backward leaves a TouchedRows record of kind "bags" for recbox_amd.optim.
-    ``weights``: one entry per bag, a float32 [nnz] tensor or None.  With any of them set the three calls are the
-    ``_weighted`` ones, and rbx_embed_csr_weight_grad runs in the backward for the weights that want a gradient.
-    A plan of POOL_MAX specs: rbx_embed_csr_fwd_max, whose argpos stays on ``ctx``; the sort is the position-valued one of
-    the weighted path and the backward rbx_embed_csr_bwd_max; gradients, pool, re-zero and TouchedRows as for every plan."""
+    persistent dense gradient per table and every guard of the pool applies.  With ``config.track_touched_rows`` a backward
+    leaves a TouchedRows record of kind "bags" for recbox_amd.optim.  ``weights``: one entry per bag, float32 [nnz] or None."""
 
     @staticmethod
     def forward(ctx, plan, n_bags, train, *tensors):
         inputs, weights, params = tensors[:2 * n_bags], tensors[2 * n_bags:3 * n_bags], tensors[3 * n_bags:]
+        B, dev = _EmbedBags._bind(plan, inputs, params)
+        ctx.plan, ctx.inputs, ctx.B, ctx.params, ctx.weights = plan, inputs, B, params, weights
+        ctx.warr = _ptr_array(weights) if any(w is not None for w in weights) else None
+        ctx.positions = ctx.warr is not None or plan.is_max    # the pairs of the sort name positions, not bags
+        ctx.long_t = bag_long_threshold()                  # the backward's weight gradient takes the forward's setting
+        out = _EmbedBags._launch_forward(ctx, dev)
+        ctx.ws, ctx.ws_bytes, ctx.sort = None, 0, None
+        if train:
+            _note_readers(ctx, params)
+            if B > 0:
+                _EmbedBags._arrange_sort(ctx, dev)
+        return out
+
+    @staticmethod
+    def _bind(plan, inputs, params):                       # the plan at this batch and its tables; returns (B, device)
         for p in params:
             _require_cuda(p, "embedding parameter")
             if p.dtype != torch.float32 or not p.is_contiguous():
                 raise RuntimeError("recbox_amd: embedding parameters must be contiguous fp32")
         plan.bind_tensors(inputs)
         plan.bind_params(params)
-        B = inputs[1].numel() - 1
-        dev = params[0].device
+        return inputs[1].numel() - 1, params[0].device
+
+    @staticmethod
+    def _launch_forward(ctx, dev):                         # leaves ctx.row_scale (mean pools) and ctx.argpos (max pools)
+        plan, B, T, w = ctx.plan, ctx.B, ctx.long_t, ctx.warr
         out = torch.empty((B, plan.width), dtype=torch.float32, device=dev)
         status = _status_word(dev)
         stride = out.stride(0) if B > 1 else plan.width
-        ctx.warr = _ptr_array(weights) if any(w is not None for w in weights) else None
-        ctx.long_t = T = bag_long_threshold()              # the backward's weight gradient takes the forward's setting
-        lws, lws_bytes = plan.long_workspace(B, T, dev) if T > 0 and not plan.is_max else (None, 0)
-        ctx.argpos = None
-        if plan.is_max:
-            row_scale = None
-            ctx.argpos = argpos = torch.empty((B, plan.width), dtype=torch.int32, device=dev)
-            mws, mws_bytes = plan.max_workspace(B, T, dev) if T > 0 else (None, 0)
-            check(_timed(("embed_csr_fwd_max", plan.n, plan.width, B),
-                         lambda: lib.rbx_embed_csr_fwd_max(plan.arr, plan.n, B, T, _ptr(out), stride, _ptr(argpos), stride,
-                                                           _ptr(mws), mws_bytes, _ptr(status), _stream())))
-        elif ctx.warr is None:
-            row_scale = torch.empty((plan.n, B), dtype=torch.float32, device=dev) if plan.needs_row_scale else None
-            if T > 0:
-                check(_timed(("embed_csr_fwd_long", plan.n, plan.width, B),
-                             lambda: lib.rbx_embed_csr_fwd_long(plan.arr, plan.n, B, T, _ptr(out), stride, _ptr(row_scale),
-                                                                _ptr(lws), lws_bytes, _ptr(status), _stream())))
-            else:
-                check(_timed(("embed_csr_fwd", plan.n, plan.width, B),
-                             lambda: lib.rbx_embed_csr_fwd(plan.arr, plan.n, B, _ptr(out), stride, _ptr(row_scale), _ptr(status),
-                                                           _stream())))
+        ws, ws_bytes = plan.workspace("max" if plan.is_max else "long", B, T, dev) if T > 0 else (None, 0)
+        ctx.row_scale = scale = out.new_empty((plan.n, B)) if plan.needs_row_scale and w is None and not plan.is_max else None
+        ctx.argpos = argpos = out.new_empty((B, plan.width), dtype=torch.int32) if plan.is_max else None
+        head, dst, lws, tail = (plan.arr, plan.n, B), (_ptr(out), stride), (_ptr(ws), ws_bytes), (_ptr(status), _stream())
+        if plan.is_max:                                    # the ONE choice of the forward: its timer name and its call
+            name, call = "embed_csr_fwd_max", lambda: lib.rbx_embed_csr_fwd_max(*head, T, *dst, _ptr(argpos), stride, *lws, *tail)
+        elif w is not None and T > 0:
+            name, call = "embed_csr_fwd_weighted_long", lambda: lib.rbx_embed_csr_fwd_weighted_long(*head, T, w, *dst, *lws, *tail)
+        elif w is not None:
+            name, call = "embed_csr_fwd_weighted", lambda: lib.rbx_embed_csr_fwd_weighted(*head, w, *dst, *tail)
+        elif T > 0:
+            name, call = "embed_csr_fwd_long", lambda: lib.rbx_embed_csr_fwd_long(*head, T, *dst, _ptr(scale), *lws, *tail)
         else:
-            row_scale = None
-            if T > 0:
-                check(_timed(("embed_csr_fwd_weighted_long", plan.n, plan.width, B),
-                             lambda: lib.rbx_embed_csr_fwd_weighted_long(plan.arr, plan.n, B, T, ctx.warr, _ptr(out), stride,
-                                                                         _ptr(lws), lws_bytes, _ptr(status), _stream())))
-            else:
-                check(_timed(("embed_csr_fwd_weighted", plan.n, plan.width, B),
-                             lambda: lib.rbx_embed_csr_fwd_weighted(plan.arr, plan.n, B, ctx.warr, _ptr(out), stride,
-                                                                    _ptr(status), _stream())))
+            name, call = "embed_csr_fwd", lambda: lib.rbx_embed_csr_fwd(*head, *dst, _ptr(scale), *tail)
+        check(_timed((name, plan.n, plan.width, B), call))
         _check_status(status)
-        ctx.plan, ctx.inputs, ctx.row_scale, ctx.B, ctx.params, ctx.weights = plan, inputs, row_scale, B, params, weights
-        ctx.ws, ctx.ws_bytes, ctx.sort = None, 0, None
-        if train:
-            _note_readers(ctx, params)
-        if B > 0 and train:
-            placeholders = [p if p.requires_grad else None for p in params]
-            weighted = ctx.warr is not None or plan.is_max     # the sort whose pairs name positions
-            pool = _GradPool.claim(_EmbedBags._pool_for(plan, params, dev, weighted)
-                                   if config.reuse_grad_buffers == "all" else None)
-            if pool is None:
-                ctx.ws, ctx.ws_bytes = _EmbedBags._sort(plan, params, placeholders, B, dev, weighted)
-            else:
-                plan.bind_params(params, placeholders)
-                ws_bytes = _EmbedBags._workspace_size(plan, B)
-                sort_call = lib.rbx_embed_csr_sort_weighted if weighted else lib.rbx_embed_csr_sort
-
-                def sort(ws, nbytes, st):
-                    return sort_call(plan.arr, plan.n, B, _ptr(ws), nbytes, None, st)
-
-                def rezero(st):
-                    # the descriptors of the step whose rows are dirty: its nnz fix the layout of the pairs in the workspace
-                    rc = lib.rbx_embed_csr_rezero(pool.dirty_bags, plan.n, pool.dirty_batch, _ptr(pool.ws), pool.ws_bytes, st)
-                    pool.dirty_batch = 0
-                    return rc
-
-                if ws_bytes > 0:
-                    # (the size follows nnz, which differs from batch to batch: regrow with headroom, not at every new maximum)
-                    pool.early_sort(ctx, dev, ws_bytes if pool.ws_bytes >= ws_bytes else ws_bytes + ws_bytes // 4, rezero, sort)
         return out
+
+    @staticmethod
+    def _arrange_sort(ctx, dev):
+        """Fresh, on this stream; or -- persistent gradients -- on the side stream behind the re-zero of the previous step's rows."""
+        plan, params, B, positions = ctx.plan, ctx.params, ctx.B, ctx.positions
+        placeholders = [p if p.requires_grad else None for p in params]
+        pool = _GradPool.claim(_EmbedBags._pool_for(plan, params, dev, positions)
+                               if config.reuse_grad_buffers == "all" else None)
+        if pool is None:
+            ctx.ws, ctx.ws_bytes = _EmbedBags._sort(plan, params, placeholders, B, dev, positions)
+            return
+        plan.bind_params(params, placeholders)
+        ws_bytes = _EmbedBags._workspace_size(plan, B)
+
+        def rezero(st):
+            # the descriptors of the step whose rows are dirty: its nnz fix the layout of the pairs in the workspace
+            rc = lib.rbx_embed_csr_rezero(pool.dirty_bags, plan.n, pool.dirty_batch, _ptr(pool.ws), pool.ws_bytes, st)
+            pool.dirty_batch = 0
+            return rc
+
+        if ws_bytes > 0:
+            # (the size follows nnz, which differs from batch to batch: regrow with headroom, not at every new maximum)
+            pool.early_sort(ctx, dev, ws_bytes if pool.ws_bytes >= ws_bytes else ws_bytes + ws_bytes // 4, rezero,
+                            lambda ws, nbytes, st: _EmbedBags._sort_call(positions, plan.arr, plan.n, B, _ptr(ws), nbytes, None, st))
 
     @staticmethod
     def _pool_for(plan, params, dev, weighted):
@@ -945,14 +931,15 @@ class _EmbedBags(torch.autograd.Function):
         return ws_bytes
 
     @staticmethod
-    def _sort(plan, params, grads, B, dev, weighted=False):
+    def _sort_call(positions, *args):                      # the ONE choice of the sort: pairs that name positions, or bags
+        return lib.rbx_embed_csr_sort_weighted(*args) if positions else lib.rbx_embed_csr_sort(*args)
+
+    @staticmethod
+    def _sort(plan, params, grads, B, dev, positions):
         plan.bind_params(params, grads)
         ws_bytes = _EmbedBags._workspace_size(plan, B)
         ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-        if weighted:                                   # pairs that name the lookup's position: rbx_embed_csr_bwd_weighted's
-            check(lib.rbx_embed_csr_sort_weighted(plan.arr, plan.n, B, _ptr(ws), ws_bytes, None, _stream()))
-        else:
-            check(lib.rbx_embed_csr_sort(plan.arr, plan.n, B, _ptr(ws), ws_bytes, None, _stream()))
+        check(_EmbedBags._sort_call(positions, plan.arr, plan.n, B, _ptr(ws), ws_bytes, None, _stream()))
         return ws, ws_bytes
 
     @staticmethod
@@ -969,61 +956,68 @@ class _EmbedBags(torch.autograd.Function):
         if any(want_w):                                    # dw = <dY, row>: reads the tables, needs no sort
             plan.bind_params(params)
             dws = [torch.empty_like(w) if k else None for w, k in zip(ctx.weights, want_w)]
-            if ctx.long_t > 0:
-                lws, lws_bytes = plan.long_workspace(B, ctx.long_t, dout.device)
-                check(lib.rbx_embed_csr_weight_grad_long(plan.arr, plan.n, B, ctx.long_t, _ptr(dout), stride, _ptr_array(dws),
-                                                         _ptr(lws), lws_bytes, None, _stream()))
-            else:
-                check(lib.rbx_embed_csr_weight_grad(plan.arr, plan.n, B, _ptr(dout), stride, _ptr_array(dws), None, _stream()))
+            lws, lws_bytes = plan.workspace("long", B, ctx.long_t, dout.device) if ctx.long_t > 0 else (None, 0)
+            check(lib.rbx_embed_csr_weight_grad_long(plan.arr, plan.n, B, ctx.long_t, _ptr(dout), stride, _ptr_array(dws), _ptr(lws),
+                                                     lws_bytes, None, _stream()) if ctx.long_t > 0 else
+                  lib.rbx_embed_csr_weight_grad(plan.arr, plan.n, B, _ptr(dout), stride, _ptr_array(dws), None, _stream()))
         head = (None, None, None) + (None,) * len(ctx.inputs) + tuple(dws)
         if not any(want):                                  # frozen tables
             return head + (None,) * len(params)
-        want_now = [p.requires_grad for p in params]
+        as_sorted = [p.requires_grad for p in params] == list(want)   # False: e.g. torch.autograd.grad on a subset
+        adopted, pool, grads = _EmbedBags._pick_grads(ctx, want, as_sorted, dout.device)
+        if B == 0:
+            return head + tuple(grads)
+        if as_sorted and (ctx.sort is not None or ctx.ws is not None):
+            if ctx.sort is not None:                       # the pool's sort, on the side stream
+                ctx.sort.join()
+            plan.bind_params(params, grads)
+            ws, ws_bytes = (ctx.sort.ws, ctx.sort.ws_bytes) if ctx.sort is not None else (ctx.ws, ctx.ws_bytes)
+        else:
+            ws, ws_bytes = _EmbedBags._sort(plan, params, grads, B, dout.device, ctx.positions)
+        _EmbedBags._reduce(ctx, dout, stride, 1 if adopted is not None else 0, ws, ws_bytes)
+        return head + _EmbedBags._publish(ctx, want, adopted, pool, grads, ws, ws_bytes)
+
+    @staticmethod
+    def _pick_grads(ctx, want, as_sorted, dev):            # (adopted, pool, grads): adopted, else the pool's, else fresh zeros
+        params, B = ctx.params, ctx.B
         adopted = _adopt_grads(ctx, params, want) if B > 0 else None
         pool, grads = None, adopted
         if adopted is None and getattr(ctx, "pool", None) is not None:
-            pool, grads = ctx.pool.backward_grads(ctx, params, want, want_now == list(want) and B > 0)
-        if grads is None:
-            grads = _flat_zero_grads(params, want, dout.device)
-        if B == 0:
-            return head + tuple(grads)
-        weighted = ctx.warr is not None or plan.is_max
-        if ctx.sort is not None and want_now == list(want):        # the pool's sort, on the side stream
-            ctx.sort.join()
-            plan.bind_params(params, grads)
-            ws, ws_bytes = ctx.sort.ws, ctx.sort.ws_bytes
-        elif ctx.ws is not None and want_now == list(want):
-            plan.bind_params(params, grads)
-            ws, ws_bytes = ctx.ws, ctx.ws_bytes
-        else:                                          # e.g. torch.autograd.grad on a subset: sort now
-            ws, ws_bytes = _EmbedBags._sort(plan, params, grads, B, dout.device, weighted)
-        accumulate = 1 if adopted is not None else 0
+            pool, grads = ctx.pool.backward_grads(ctx, params, want, as_sorted and B > 0)
+        return adopted, pool, grads if grads is not None else _flat_zero_grads(params, want, dev)
+
+    @staticmethod
+    def _reduce(ctx, dout, stride, accumulate, ws, ws_bytes):   # the ONE choice of the table-gradient call
+        plan, B = ctx.plan, ctx.B
+        head, tail = (plan.arr, plan.n, B), (accumulate, _ptr(ws), ws_bytes, _stream())
         if plan.is_max:
-            check(lib.rbx_embed_csr_bwd_max(plan.arr, plan.n, B, _ptr(dout), stride, _ptr(ctx.argpos), ctx.argpos.stride(0)
-                                            if B > 1 else plan.width, accumulate, _ptr(ws), ws_bytes, _stream()))
-        elif weighted:
-            check(lib.rbx_embed_csr_bwd_weighted(plan.arr, plan.n, B, ctx.warr, _ptr(dout), stride, accumulate, _ptr(ws),
-                                                 ws_bytes, _stream()))
+            astride = ctx.argpos.stride(0) if B > 1 else plan.width
+            check(lib.rbx_embed_csr_bwd_max(*head, _ptr(dout), stride, _ptr(ctx.argpos), astride, *tail))
+        elif ctx.warr is not None:
+            check(lib.rbx_embed_csr_bwd_weighted(*head, ctx.warr, _ptr(dout), stride, *tail))
         else:
-            check(lib.rbx_embed_csr_bwd(plan.arr, plan.n, B, _ptr(dout), stride, _ptr(ctx.row_scale), accumulate, _ptr(ws),
-                                        ws_bytes, _stream()))
+            check(lib.rbx_embed_csr_bwd(*head, _ptr(dout), stride, _ptr(ctx.row_scale), *tail))
+
+    @staticmethod
+    def _publish(ctx, want, adopted, pool, grads, ws, ws_bytes):
+        """Tell the pool, the touched-row records and the tables' other readers; returns the node's table gradients."""
+        plan, params, B = ctx.plan, ctx.params, ctx.B
         if pool is not None:
             pool.done(B)
             pool.dirty_bags = type(plan.arr).from_buffer_copy(plan.arr)
         _forget_sort(ws)
         if config.track_touched_rows:
-            ids = ctx.inputs[0::2]
             _note_ids(plan, ctx.inputs, params, grads, want,
-                      ids_of=lambda k: [t for sp, t in zip(plan.specs, ids) if sp.param == k])
+                      ids_of=lambda k: [t for sp, t in zip(plan.specs, ctx.inputs[0::2]) if sp.param == k])
         if adopted is not None:                        # the rows went into the gradient another node of this pass returned
             for p, w in zip(params, want):
                 if w:
                     touched.pop(id(p), None)           # (its touched-row record names that node's rows only)
-            return head + (None,) * len(params)
+            return (None,) * len(params)
         if config.track_touched_rows:
             _note_touched("bags", (plan,), ctx.inputs, (list(params),), (list(grads),), ws, ws_bytes, B, pool=pool)
         _publish_grads(ctx, params, grads)
-        return head + tuple(grads)
+        return tuple(grads)
 
 
 def _ptr_array(tensors):
@@ -1046,7 +1040,7 @@ def embed_bags(plan_or_specs, bags, params):
     for p in params:
         _require_cuda(p, "embedding parameter")
     _, tensors = plan.bind_inputs(bags)
-    weights = [getattr(g, "weights", None) for g in bags]
+    weights = [g.weights for g in bags]
     train = torch.is_grad_enabled() and any(p.requires_grad for p in params)   # grad mode is off inside forward()
     return _EmbedBags.apply(plan, plan.n, train, *tensors, *weights, *params)
 
