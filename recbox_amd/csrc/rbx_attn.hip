@@ -214,6 +214,7 @@ __global__ __launch_bounds__(kAttnThreads) void attn_bwd_dq_kernel(const float* 
     }
     const float* mrow = (mask != nullptr && live) ? mask + row * Lk : nullptr;
     unsigned dc[4] = {0u, 0u, 0u, 0u};
+    int nfill = 0;                       // visible keys of this row whose score the mask replaced
     const int last = causal ? ((i0 + kAttnThreads - 1 < Lk - 1) ? i0 + kAttnThreads - 1 : Lk - 1) : Lk - 1;
     for (int c0 = 0; c0 <= last; c0 += C) {
     stage(c0);
@@ -233,9 +234,13 @@ __global__ __launch_bounds__(kAttnThreads) void attn_bwd_dq_kernel(const float* 
                      (i & 3) >> 1, dk0, dk1, dc);
         dp = drop_keep(dc, i & 1, j & 3, drop.thr16) ? dp * drop.scale : 0.f;
       }
-      if (mrow != nullptr && j <= jmax && mrow[j] == 0.f) s = fill;
+      // a masked entry's score is the constant `fill`: nothing flows back through it (masked_fill), which matters in a row
+      // that is masked entirely -- elsewhere p is zero there anyway
+      const bool filled = mrow != nullptr && j <= jmax && mrow[j] == 0.f;
+      if (filled) { s = fill; ++nfill; }
       const float p = (j <= jmax) ? __expf(s - lse) : 0.f;
-      const float ds = p * (dp - Di);
+      // (nor through a key the row does not see: p is 0 there, but D is NaN in a row that -inf hides entirely)
+      const float ds = (filled || j > jmax) ? 0.f : p * (dp - Di);
 #pragma unroll
       for (int d = 0; d < HD; ++d) dq[d] += ds * kr[d];
     }
@@ -243,7 +248,10 @@ __global__ __launch_bounds__(kAttnThreads) void attn_bwd_dq_kernel(const float* 
     if (live) {
 #pragma unroll
       for (int d = 0; d < HD; ++d) dQ[row * HD + d] = dq[d] * scale;
-      Dv[row] = Di;
+      // A row whose every visible key is masked (finite fill) is uniform over them, and phase B cannot recompute that from
+      // lse: with a fill like -1e9, lse = fill + log n and float32 cannot hold the log n beside it.  Such a row has dS == 0
+      // everywhere, so phase B never reads its D: the slot carries a NaN that tells phase B to take p = 1 / n.
+      Dv[row] = (nfill == jmax + 1 && fill > -INFINITY) ? __builtin_nanf("") : Di;
     }
   }
 }
@@ -318,8 +326,13 @@ __global__ __launch_bounds__(kAttnThreads) void attn_bwd_dkv_kernel(const float*
         dp += gr[d] * vx[d];
       }
       const bool vis = live && (!causal || j <= i);
-      if (mask != nullptr && vis && mask[(bh * Lq + i) * Lk + j] == 0.f) s = fill;
-      const float p = vis ? __expf(s - Ls[i - c0]) : 0.f;
+      const bool filled = mask != nullptr && vis && mask[(bh * Lq + i) * Lk + j] == 0.f;
+      if (filled) s = fill;
+      float p = vis ? __expf(s - Ls[i - c0]) : 0.f;
+      // a row that phase A found masked entirely (NaN in its D slot, finite fill): uniform over its visible keys, whatever
+      // the size of the fill -- exp(fill - lse) is 1, not 1 / n, once float32 cannot hold log n beside the fill
+      if (filled && fill > -INFINITY && Ds[i - c0] != Ds[i - c0])
+        p = 1.0f / static_cast<float>(causal ? (i < Lk - 1 ? i : Lk - 1) + 1 : Lk);
       float pd = p;
       if (drop.thr16 != 0) {
         if ((i >> 1) != dc_for) {                  // a block covers two consecutive queries
@@ -331,7 +344,7 @@ __global__ __launch_bounds__(kAttnThreads) void attn_bwd_dkv_kernel(const float*
         pd = keep ? p * drop.scale : 0.f;
         dp = keep ? dp * drop.scale : 0.f;
       }
-      const float ds = p * (dp - Ds[i - c0]);
+      const float ds = (filled || !vis) ? 0.f : p * (dp - Ds[i - c0]);     // (D of a row masked entirely is NaN)
 #pragma unroll
       for (int d = 0; d < HD; ++d) {
         dv[d] += pd * gr[d];
