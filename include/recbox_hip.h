@@ -985,7 +985,9 @@ int rbx_attn_packed_bwd(const float* d_q, int64_t ldq, const float* d_k, int64_t
  *                           backward, which writes d_dlogits [rows, n_classes] contiguous.
  *   rbx_pair_logsigmoid_*   scale * sum_i -w_i (log sigmoid(pos_i) + log sigmoid(-neg_i)): the pos/neg objective over
  *                           the [B, L] logit blocks of third_party/rechub/models/matching/sasrec.py:100-107 (w = 1 on
- *                           real positions, 0 on padding; NULL = all ones). */
+ *                           real positions, 0 on padding; NULL = all ones).  A position with w_i == 0 is never evaluated:
+ *                           it adds nothing to the loss and rbx_pair_logsigmoid_bwd writes exactly 0 to d_dpos[i] and
+ *                           d_dneg[i], whatever pos_i / neg_i hold (inf and NaN included). */
 size_t rbx_loss_workspace_size(int64_t n);
 int rbx_softmax_ce_fwd(const float* d_logits, int64_t stride, int64_t rows, int32_t n_classes, const int64_t* d_target,
                        float* d_loss, float* d_lse, int32_t* d_status, void* d_workspace, size_t workspace_bytes,

@@ -110,7 +110,13 @@ __global__ __launch_bounds__(256) void pair_logsig_bwd_kernel(const float* __res
   const float g = gloss[0] * scale;
   const long long step = static_cast<long long>(gridDim.x) * blockDim.x;
   for (long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += step) {
-    const float wi = g * ((w != nullptr) ? w[i] : 1.f);
+    const float w0 = (w != nullptr) ? w[i] : 1.f;
+    if (w0 == 0.f) {                                  // masked positions cost nothing, whatever they hold (as the forward)
+      dpos[i] = 0.f;
+      dneg[i] = 0.f;
+      continue;
+    }
+    const float wi = g * w0;
     const float sp = 1.f / (1.f + expf(-pos[i])), sn = 1.f / (1.f + expf(-neg[i]));
     dpos[i] = -wi * (1.f - sp);                       // d/dx -log sigmoid(x) = -(1 - sigmoid(x))
     dneg[i] = wi * sn;                                // d/dx -log sigmoid(-x) = sigmoid(x)
