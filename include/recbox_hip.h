@@ -513,12 +513,15 @@ int rbx_embed_rezero(const rbx_field_t* fields, int32_t n_fields, int64_t batch,
  * whose summed gradient sits in fields[i].grad.  These calls apply ONE optimiser step to exactly those rows of
  * fields[i].table (written in place) and of the state tensors -- same shape as the gradient, d_state1[i] / d_state2[i] per
  * feature i (HOST arrays of DEVICE pointers; features that share a table pass the same pointers):
- *   RBX_OPT_SGD      w -= lr (g + weight_decay w)
+ * with g = fields[i].grad's row + weight_decay * w for ALL three rules (L2 on the touched rows),
+ *   RBX_OPT_SGD      w -= lr g
  *   RBX_OPT_ADAGRAD  state1 += g^2; w -= lr g / (sqrt(state1) + eps)          (torch.optim.Adagrad's sparse branch; the
  *                    caller folds lr_decay into lr)
  *   RBX_OPT_ADAM     state1 = beta1 state1 + (1 - beta1) g; state2 = beta2 state2 + (1 - beta2) g^2;
  *                    w -= lr state1 / (sqrt(state2) + eps)   with lr = lr0 sqrt(1 - beta2^t) / (1 - beta1^t) folded in by
  *                    the caller (torch.optim.SparseAdam: the moments of untouched rows do not decay)
+ * Every row the batch looked up is stepped exactly once, whatever its summed gradient (a zero gradient still decays Adam's
+ * moments and moves w by the decayed first moment, as torch.optim.SparseAdam on a coalesced gradient does).
  * Rows the batch did not touch, padding_idx rows and masked lookups are neither read nor written.  The tier-A tables of
  * the fused FM body (every row written by every backward) count a row as touched when some block's presence bitmap has it.
  * Call between the backward and the next sort on that workspace. */
@@ -528,7 +531,7 @@ typedef struct rbx_opt {
   float   lr;                /* effective step size (bias correction / decay folded in) */
   float   beta1, beta2;      /* Adam */
   float   eps;
-  float   weight_decay;      /* L2 on the touched rows: g += weight_decay * w (0 for torch's sparse rules) */
+  float   weight_decay;      /* L2 on the touched rows, every rule: g += weight_decay * w (0 for torch's sparse rules) */
   const float* d_step_size;  /* NULL, or a DEVICE float that overrides lr: a step captured into a hipGraph bakes every
                               * by-value argument in, so a rule whose step size depends on the step count (Adam's bias
                               * correction, Adagrad's lr_decay) reads it from memory that rbx_opt_advance updates in-graph */

@@ -8,7 +8,8 @@
 // path: the sorted (row, lookup) pairs that drove the backward's segmented reduce are still in its workspace and name
 // every touched row exactly once (the head of each run of equal keys); the summed gradient of such a row sits in the
 // dense gradient buffer the backward stored into.  One launch walks the pairs; a lane group per run head applies
-//   SGD      w -= lr (g + wd w)
+// (g: the summed gradient + wd w, for all three rules)
+//   SGD      w -= lr g
 //   Adagrad  s += g^2;  w -= lr g / (sqrt(s) + eps)                         (torch.optim.Adagrad, sparse branch)
 //   Adam     m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;  w -= lr m / (sqrt(v) + eps)
 //            with lr = lr0 sqrt(1 - b2^t) / (1 - b1^t) folded in by the caller   (torch.optim.SparseAdam: "lazy", the
@@ -371,6 +372,19 @@ extern "C" int rbx_fm_sparse_update(const rbx_field_t* emb, const rbx_field_t* l
       return fail(RBX_ERR_INVALID, "fm_sparse_update: feature %d has no second moment", i);
     return RBX_OK;
   };
+  // every refusal comes before the first launch: a call that fails has written nothing (the tier-A tables are described
+  // only after tier B has been stepped)
+  {
+    UpdField probe;
+    for (int c = 0; p.n_lookups > 0 && c < p.n_cat; ++c) {
+      rc = fill(probe, src_of_key[c]);
+      if (rc != RBX_OK) return rc;
+    }
+    for (int t = 0; t < ta.n_tab; ++t) {
+      rc = fill(probe, src_of_tab[t]);
+      if (rc != RBX_OK) return rc;
+    }
+  }
   // ---- tier B: run heads of the sorted pairs ----
   if (p.n_lookups > 0) {
     UpdField upd[RBX_MAX_FIELDS];

@@ -23,6 +23,19 @@ A table that several lookups of one step feed (SASRec's item table: the sequence
 stepped with the same rule over the union of their rows (the lookups leave their id tensors: ``ops.touched_ids``); a
 parameter that got its gradient from something else than ``embed_lookup`` / ``embed_bags`` / ``gather_dot`` / ``fm_fused`` is
 stepped over the non-zero rows of its dense gradient.
+
+Which rows a step touches.  The contract is the record path's: EVERY row the batch looked up is stepped once, whatever its
+summed gradient -- a looked-up row whose gradient is exactly zero still decays SparseAdam's moments and moves by the
+decayed first moment, as torch.optim.SparseAdam does on a coalesced sparse gradient (oracle/optim64.py restates it,
+tests/test_gpu_optim_forms.py pins it).  The dense fallback, its union form included, has no descriptors to tell a padding
+id from such a row: it selects rows by ``g != 0`` and leaves a zero-gradient row alone.  The two agree for SGD without
+weight decay and wherever no looked-up row has an all-zero gradient.
+``weight_decay`` (g += weight_decay * w on the stepped rows) applies to all three rules.
+
+Step sizes.  The C ABI carries lr, the betas and lr_decay as floats, and rbx_opt_advance (capturable=True) derives the step
+size from those floats.  ``_step_size`` therefore rounds them to float32 before it evaluates the rule in double: with the
+double 0.999 in place of float32(0.999) the by-value step size of SparseAdam was off the captured one by 50 float32 eps
+(6e-6 relative) -- more than the error bound of the device's own arithmetic.  One optimiser, one trajectory, captured or not.
 """
 import ctypes
 import math
@@ -33,6 +46,11 @@ from . import _lib, ops
 from ._lib import check, lib
 
 __all__ = ["SparseSGD", "SparseAdagrad", "SparseAdam", "split_parameters"]
+
+
+def _f32(v):
+    """``v`` as the C ABI carries it: rounded to float32 (returned as a Python float)."""
+    return ctypes.c_float(v).value
 
 
 def split_parameters(model):
@@ -78,7 +96,7 @@ class _SparseRows(object):
     n_state = 0
 
     def _step_size(self, t):
-        return self.lr
+        return _f32(self.lr)
 
     def _betas_eps(self):
         return 0.0, 0.0, 0.0
@@ -279,7 +297,7 @@ class SparseAdagrad(_SparseRows):
         return st
 
     def _step_size(self, t):
-        return self.lr / (1.0 + (t - 1) * self.lr_decay)
+        return _f32(self.lr) / (1.0 + (t - 1) * _f32(self.lr_decay))
 
     def _betas_eps(self):
         return 0.0, 0.0, self.eps
@@ -307,7 +325,8 @@ class SparseAdam(_SparseRows):
         self.b1, self.b2, self.eps = float(betas[0]), float(betas[1]), float(eps)
 
     def _step_size(self, t):
-        return self.lr * math.sqrt(1.0 - self.b2 ** t) / (1.0 - self.b1 ** t)
+        b1, b2 = _f32(self.b1), _f32(self.b2)
+        return _f32(self.lr) * math.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t)
 
     def _betas_eps(self):
         return self.b1, self.b2, self.eps
@@ -316,14 +335,15 @@ class SparseAdam(_SparseRows):
         step = self._step_size(t)
         g = g + self.weight_decay * p if self.weight_decay else g
         m, v = st["s"]
+        b1, b2 = _f32(self.b1), _f32(self.b2)          # (1 - float32(0.999) is not float32(1 - 0.999): the kernels' coefficients)
         if rows is None:
-            m.mul_(self.b1).add_(g, alpha=1 - self.b1)
-            v.mul_(self.b2).addcmul_(g, g, value=1 - self.b2)
+            m.mul_(b1).add_(g, alpha=1 - b1)
+            v.mul_(b2).addcmul_(g, g, value=1 - b2)
             p.addcdiv_(m, v.sqrt().add_(self.eps), value=-step)
         else:
             gr = g.index_select(0, rows)
-            mr = m.index_select(0, rows).mul_(self.b1).add_(gr, alpha=1 - self.b1)
-            vr = v.index_select(0, rows).mul_(self.b2).addcmul_(gr, gr, value=1 - self.b2)
+            mr = m.index_select(0, rows).mul_(b1).add_(gr, alpha=1 - b1)
+            vr = v.index_select(0, rows).mul_(b2).addcmul_(gr, gr, value=1 - b2)
             m.index_copy_(0, rows, mr)
             v.index_copy_(0, rows, vr)
             p.index_add_(0, rows, mr / (vr.sqrt() + self.eps), alpha=-step)
