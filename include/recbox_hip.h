@@ -800,7 +800,10 @@ int rbx_cross_bwd(const float* d_x0, const float* d_h, const float* d_dout, int6
                   float* d_dx0, float* d_dh, void* stream);
 /* out[r, :] = (alpha * x[r, :] + add[r, :]) * scale[r]   (add optional): SASRec's embedding prologue `e *= sqrt(D);
  * e += position_emb(...); e *= ~timeline_mask.unsqueeze(-1)` and its per-block mask (third_party/rechub/models/matching/
- * sasrec.py:68-77, 92) in one pass; its backward is the same call on the incoming gradient. */
+ * sasrec.py:68-77, 92) in one pass; its backward is the same call on the incoming gradient.  No alignment is required:
+ * the float4 form runs when dim % 4 == 0 and d_x, d_add and d_out are 16-byte aligned, the scalar form otherwise (a
+ * contiguous view one float into its storage), with the same values.  rows % add_rows != 0 and a NULL d_add of
+ * rbx_rowscale_seq are RBX_ERR_INVALID. */
 int rbx_rowscale(const float* d_x, const float* d_add, const float* d_scale, int64_t rows, int32_t dim, float alpha,
                  float* d_out, void* stream);
 /* The same prologue with the position rows read in place: sasrec.py:68-77 looks up positions = tile(arange(L), [B, 1]), i.e.
@@ -818,7 +821,13 @@ int rbx_seq_colsum(const float* d_g, const float* d_scale, int64_t batch, int32_
  * strides in floats.  The input gradient of a row block that one consumer reads whole and two more read through its
  * leading columns: DeepFM feeds the same embeddings to the tower (embeddings | dense values), to FM and to the
  * first-order Linear (third_party/rechub/models/ranking/deepfm.py:34-39; autograd's glue for it is a fill, a strided
- * copy and two adds). */
+ * copy and two adds).
+ * Only out[r, 0 .. cols) is written, in every form: columns at or beyond `cols` of a row -- the padding of a stride
+ * rounded up to a float4 included -- keep what they held, and nothing at or beyond `cols` (`prefix_cols` for a, b) is
+ * read, so every operand may be a column view of a wider buffer.  The float4 form needs 16-byte aligned pointers,
+ * prefix_cols % 4 == 0 and strides that are multiples of 4 and at least cols rounded up to 4 (out, base); anything else
+ * runs the scalar form with the same values.  A stride shorter than its row, prefix_cols > cols and negative sizes are
+ * RBX_ERR_INVALID; rows == 0 or cols == 0 returns at once. */
 int rbx_sum_prefix(const float* d_base, int64_t base_stride, const float* d_a, int64_t a_stride, const float* d_b,
                    int64_t b_stride, int64_t rows, int32_t cols, int32_t prefix_cols, float* d_out, int64_t out_stride,
                    void* stream);

@@ -571,6 +571,8 @@ extern "C" int rbx_cross_bwd(const float* d_x0, const float* d_h, const float* d
 // broadcast one over [B, L, 1] x [B, L, D] un-vectorised (159 us at [819200, 64] against 64 us for a plain pass); here one.
 namespace rbx {
 // add_period > 0: `add` holds add_period floats that repeat (the position rows [L, D] of every sequence of a [B, L, D] block)
+// VEC: dim % 4 == 0 and x / add / out 16-byte aligned; else the scalar walk of the same four elements per thread
+template <bool VEC>
 __global__ __launch_bounds__(256) void rowscale_kernel(const float* __restrict__ x, const float* __restrict__ add,
                                                        const float* __restrict__ s, const long long rows, const int dim,
                                                        const float alpha, float* __restrict__ out,
@@ -578,7 +580,7 @@ __global__ __launch_bounds__(256) void rowscale_kernel(const float* __restrict__
   const long long total = rows * dim;
   const long long step = static_cast<long long>(gridDim.x) * blockDim.x * 4;
   for (long long i = (static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x) * 4; i < total; i += step) {
-    if ((dim & 3) == 0) {                                  // a float4 never straddles two rows
+    if constexpr (VEC) {                                   // a float4 never straddles two rows
       const float sc = s[i / dim];
       typedef float v4f __attribute__((ext_vector_type(4)));
       const v4f vv = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(x + i));       // streamed once
@@ -593,6 +595,23 @@ __global__ __launch_bounds__(256) void rowscale_kernel(const float* __restrict__
     }
   }
 }
+
+// the float4 form when dim % 4 == 0 and every tensor is 16-byte aligned (NULL add counts as aligned), else the scalar form:
+// a contiguous view one float into its storage computes, as it does in the interaction and gather_dot kernels
+static void launch_rowscale(const float* x, const float* add, const float* s, long long rows, int dim, float alpha, float* out,
+                            long long add_period, hipStream_t stream) {
+  const bool vec = (dim & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out) |
+                                       reinterpret_cast<uintptr_t>(add)) & 15) == 0;
+  long long blocks = (rows * dim / 4 + 255) / 256;
+  if (blocks > kCUs * 32) blocks = kCUs * 32;
+  if (blocks < 1) blocks = 1;
+  if (vec)
+    hipLaunchKernelGGL(rowscale_kernel<true>, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, stream, x, add, s, rows, dim,
+                       alpha, out, add_period);
+  else
+    hipLaunchKernelGGL(rowscale_kernel<false>, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, stream, x, add, s, rows, dim,
+                       alpha, out, add_period);
+}
 }  // namespace rbx
 
 extern "C" int rbx_rowscale(const float* d_x, const float* d_add, const float* d_scale, int64_t rows, int32_t dim, float alpha,
@@ -601,14 +620,7 @@ extern "C" int rbx_rowscale(const float* d_x, const float* d_add, const float* d
   if (rows == 0 || dim == 0) return RBX_OK;
   if (rows < 0 || dim < 0) return fail(RBX_ERR_INVALID, "rowscale: negative sizes");
   if (!d_x || !d_scale || !d_out) return fail(RBX_ERR_INVALID, "rowscale: NULL tensor");
-  if ((dim & 3) == 0 && (((reinterpret_cast<uintptr_t>(d_x) | reinterpret_cast<uintptr_t>(d_out) |
-                           reinterpret_cast<uintptr_t>(d_add)) & 15) != 0))
-    return fail(RBX_ERR_INVALID, "rowscale: tensors must be 16-byte aligned when dim is a multiple of 4");
-  long long blocks = (rows * dim / 4 + 255) / 256;
-  if (blocks > kCUs * 32) blocks = kCUs * 32;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(rowscale_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, as_stream(stream), d_x, d_add, d_scale,
-                     static_cast<long long>(rows), dim, alpha, d_out, 0LL);
+  launch_rowscale(d_x, d_add, d_scale, rows, dim, alpha, d_out, 0LL, as_stream(stream));
   return check_launch("rowscale_kernel");
 }
 
@@ -684,14 +696,7 @@ extern "C" int rbx_rowscale_seq(const float* d_x, const float* d_add, int64_t ad
   if (rows < 0 || dim < 0 || add_rows <= 0 || rows % add_rows != 0)
     return fail(RBX_ERR_INVALID, "rowscale_seq: rows must be a multiple of add_rows > 0");
   if (!d_x || !d_add || !d_scale || !d_out) return fail(RBX_ERR_INVALID, "rowscale_seq: NULL tensor");
-  if ((dim & 3) == 0 && (((reinterpret_cast<uintptr_t>(d_x) | reinterpret_cast<uintptr_t>(d_out) |
-                           reinterpret_cast<uintptr_t>(d_add)) & 15) != 0))
-    return fail(RBX_ERR_INVALID, "rowscale_seq: tensors must be 16-byte aligned when dim is a multiple of 4");
-  long long blocks = (rows * dim / 4 + 255) / 256;
-  if (blocks > kCUs * 32) blocks = kCUs * 32;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(rowscale_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, as_stream(stream), d_x, d_add, d_scale,
-                     static_cast<long long>(rows), dim, alpha, d_out, static_cast<long long>(add_rows) * dim);
+  launch_rowscale(d_x, d_add, d_scale, rows, dim, alpha, d_out, static_cast<long long>(add_rows) * dim, as_stream(stream));
   return check_launch("rowscale_kernel (periodic add)");
 }
 
@@ -750,6 +755,17 @@ __global__ __launch_bounds__(256) void sum_prefix_kernel(const float* __restrict
     if (total < (1LL << 32)) r = static_cast<unsigned>(i) / per_row;       // 32-bit division whenever it fits
     else r = i / per_row;
     const int c = static_cast<int>(i - r * per_row) * W;
+    if (VEC && c + W > cols) {     // the ragged last group of a row, element by element: columns >= cols are not touched
+      for (int k = c; k < cols; ++k) {
+        float t = base != nullptr ? base[r * base_stride + k] : 0.f;
+        if (k < prefix_cols) {
+          if (a != nullptr) t += a[r * a_stride + k];
+          if (b != nullptr) t += b[r * b_stride + k];
+        }
+        out[r * out_stride + k] = t;
+      }
+      continue;
+    }
     float v[W];
 #pragma unroll
     for (int k = 0; k < W; ++k) v[k] = 0.f;
@@ -796,7 +812,8 @@ extern "C" int rbx_sum_prefix(const float* d_base, int64_t base_stride, const fl
   if (out_stride < cols || (d_base && base_stride < cols) || (d_a && a_stride < prefix_cols) || (d_b && b_stride < prefix_cols))
     return fail(RBX_ERR_INVALID, "sum_prefix: a row stride is shorter than its row");
   // float4 sweep when every row starts 16-byte aligned, the prefix ends on a float4 and the padded tail of the last
-  // float4 of a row lies inside the row stride of the tensors that hold whole rows
+  // float4 of a row lies inside the row stride of the tensors that hold whole rows (that last group is walked element by
+  // element all the same: nothing at or beyond `cols` is read or written)
   const int padded = (cols + 3) / 4 * 4;
   const uintptr_t bits = reinterpret_cast<uintptr_t>(d_base) | reinterpret_cast<uintptr_t>(d_a) |
                          reinterpret_cast<uintptr_t>(d_b) | reinterpret_cast<uintptr_t>(d_out);
