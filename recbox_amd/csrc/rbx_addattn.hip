@@ -163,14 +163,20 @@ __global__ __launch_bounds__(16 * KS) void addattn_bwd_kernel(
     const float cj = (ctx != nullptr && jok) ? ctx[b * H + j] : 0.f;
     if (threadIdx.x < D) dd[threadIdx.x] = dout[b * ds_b + threadIdx.x];
     __syncthreads();
-    // G = sum_l alpha_l (dout . x_l): wave w takes positions w, w + nw, ...; the waves are added in order
+    // G = sum_l alpha_l g_l: quad q of wave w takes positions 4 w + q, 4 (w + nw) + q, ...; the quads, then the waves, are
+    // added in order.  g_l = dout . x_l is summed exactly as the tile loop below sums it (this lane's columns col, col + 16,
+    // ..., then the 16 lanes), so g_l - G cancels to the bit where one position holds all the weight: its dq is 0, not the
+    // rounding of two summation orders
     float gpart = 0.f;
-    for (int l = wv; l < L; l += nw) {
+    for (int l0 = wv * 4; l0 < L; l0 += 4 * nw) {
+      const int l = l0 + quad;
       float p = 0.f;
-      for (int c = lane; c < D; c += 64) p = fma_rn(dd[c], xb[l * xs_l + c], p);
-      p = group_sum<64>(p);
-      gpart = fma_rn(ab[l], p, gpart);
+      if (l < L)
+        for (int c = col; c < D; c += 16) p = fma_rn(dd[c], xb[l * xs_l + c], p);
+      gpart = fma_rn(l < L ? ab[l] : 0.f, aa_sum16(p), gpart);
     }
+    gpart += __shfl_xor(gpart, 16, 64);
+    gpart += __shfl_xor(gpart, 32, 64);
     if (lane == 0) gw[wv] = gpart;
     __syncthreads();
     float G = 0.f;
