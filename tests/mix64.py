@@ -17,21 +17,29 @@ def ple_select(n_task, n_specific, n_shared, with_shared_gate=True):
     return sel
 
 
-def make_case(seed, B, H, E, select, scale=1.0):
-    """{"x": E x [B, H], "z": T x [B, n_t], "up": T x [B, H] (upstream gradients), "select"} in float32 on the CPU."""
+def make_case(seed, B, H, E, select, scale=1.0, up=1.0, x_scale=1.0):
+    """{"x": E x [B, H] at std ``x_scale``, "z": T x [B, n_t] at std ``scale``, "up": T x [B, H] (upstream gradients at std
+    ``up``), "select"} in float32 on the CPU."""
     g = torch.Generator().manual_seed(seed)
-    return {"x": [torch.randn(B, H, generator=g) for _ in range(E)],
+    return {"x": [torch.randn(B, H, generator=g) * x_scale for _ in range(E)],
             "z": [torch.randn(B, len(s), generator=g) * scale for s in select],
-            "up": [torch.randn(B, H, generator=g) for _ in select],
+            "up": [torch.randn(B, H, generator=g) * up for _ in select],
             "select": [list(s) for s in select]}
 
 
-def forward(x, z, select, softmax=True):
-    """(outs, ps) in float64."""
-    x = [t.double() for t in x]
+def small_wrap_case(H, B=37):
+    """The small-gradient case of tests/test_gpu_mix_forms.py and tests/test_fp32_bar_host.py: 16 experts, two gates over all
+    of them (n_t = 16 > G at H = 8, 12, 32), expert outputs and logits of size 0.1, upstream gradients of size 1e-3 -- every
+    dz is below 1e-4 there, where an absolute 1e-4 checks nothing."""
+    return make_case(40 + H, B, H, 16, full_select(16, 2), scale=0.1, up=1e-3, x_scale=0.1)
+
+
+def forward(x, z, select, softmax=True, dtype=torch.float64):
+    """(outs, ps) in ``dtype``: float64 for the bound, float32 for the bar of tests/fp32_bar.py."""
+    x = [t.to(dtype) for t in x]
     outs, ps = [], []
     for zt, sel in zip(z, select):
-        zt = zt.double()
+        zt = zt.to(dtype)
         if softmax:
             e = torch.exp(zt - zt.max(dim=1, keepdim=True).values)
             p = e / e.sum(dim=1, keepdim=True)
@@ -45,30 +53,50 @@ def forward(x, z, select, softmax=True):
     return outs, ps
 
 
-def backward(x, ps, select, douts, softmax=True):
-    """(dx: E tensors, dz: T tensors) in float64; an entry of ``douts`` may be None (no gradient = zeros)."""
-    x = [t.double() for t in x]
+def backward(x, ps, select, douts, softmax=True, dtype=torch.float64, bug=None):
+    """(dx: E tensors, dz: T tensors) in ``dtype``; an entry of ``douts`` may be None (no gradient = zeros).  ``bug``: one
+    deliberately wrong term for tests/test_fp32_bar_host.py -- ("s_t over the first G entries", G): the sum s_t = sum_i p_i dp_i
+    stops after G entries (a lane group of G lanes that does not wrap); "dz without - s_t"; "dX_e without the last gate"."""
+    x = [t.to(dtype) for t in x]
     dx = [torch.zeros_like(t) for t in x]
     dz = []
-    for p, sel, d in zip(ps, select, douts):
+    last_gate = {}
+    for t, (sel, d) in enumerate(zip(select, douts)):
+        if d is not None:
+            for e_idx in sel:
+                last_gate[e_idx] = t
+    for t, (p, sel, d) in enumerate(zip(ps, select, douts)):
         if d is None:
             dz.append(torch.zeros_like(p))
             continue
-        d = d.double()
+        d = d.to(dtype)
         dp = torch.zeros_like(p)
         for j, e_idx in enumerate(sel):
-            dx[e_idx] = dx[e_idx] + p[:, j:j + 1] * d
+            if not (bug == "dX_e without the last gate" and last_gate[e_idx] == t and t > 0):
+                dx[e_idx] = dx[e_idx] + p[:, j:j + 1] * d
             dp[:, j] = (d * x[e_idx]).sum(dim=1)
-        dz.append(p * (dp - (p * dp).sum(dim=1, keepdim=True)) if softmax else dp)
+        if not softmax:
+            dz.append(dp)
+            continue
+        pd = p * dp
+        if isinstance(bug, tuple) and bug[0] == "s_t over the first G entries":
+            pd = pd[:, :bug[1]]
+        s = pd.sum(dim=1, keepdim=True)
+        dz.append(p * dp if bug == "dz without - s_t" else p * (dp - s))
     return dx, dz
 
 
-def reference(case, softmax=True, used=None):
-    """{"out", "p", "dx", "dz"} of a case in float64; ``used``: the outputs that enter the loss (None = all)."""
-    outs, ps = forward(case["x"], case["z"], case["select"], softmax)
+def reference(case, softmax=True, used=None, dtype=torch.float64, bug=None):
+    """{"out", "p", "dx", "dz"} of a case in ``dtype``; ``used``: the outputs that enter the loss (None = all)."""
+    outs, ps = forward(case["x"], case["z"], case["select"], softmax, dtype)
     ups = [u if (used is None or t in used) else None for t, u in enumerate(case["up"])]
-    dx, dz = backward(case["x"], ps, case["select"], ups, softmax)
+    dx, dz = backward(case["x"], ps, case["select"], ups, softmax, dtype, bug)
     return {"out": outs, "p": ps, "dx": dx, "dz": dz}
+
+
+def reference32(case, softmax=True, used=None):
+    """The same restatement in float32 on the CPU: the ``ref32`` of fp32_bar.assert_bar."""
+    return reference(case, softmax, used, torch.float32)
 
 
 def run(fn, case, device, softmax=True, used=None, grad_x=True, grad_z=True, x_override=None):

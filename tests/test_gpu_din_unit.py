@@ -10,6 +10,7 @@ import torch
 from torch import nn
 
 from conftest import GOLDEN, assert_close
+from din64 import ref_pairs as _ref_pairs, ref_pool as _ref_pool
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -44,15 +45,6 @@ def test_default_routing_follows_the_measurement():
         assert gates(64) == (False, False)
     finally:
         ops.config.din_fused = True
-
-
-def _ref_pairs(h, t, w, b, act):
-    tt = t.unsqueeze(1).expand(-1, h.shape[1], -1)
-    pairs = torch.cat([tt, h, tt - h, tt * h], dim=-1)
-    y = pairs.reshape(-1, pairs.shape[-1]) @ w.t()
-    if b is not None:
-        y = y + b
-    return torch.relu(y) if act else y
 
 
 def _parent_pairs(h, t, w, b, act):
@@ -149,17 +141,6 @@ def test_strided_operands_are_read_in_place_and_give_the_same_bits():
     assert torch.equal(block, block0) and torch.equal(tblock, tblock0)
     assert bool((block[:, 0] == sentinel).all()) and bool((block[:, 2] == sentinel).all())
     assert bool((tblock[:, :2] == sentinel).all())
-
-
-def _ref_pool(score, h, mask, softmax):
-    w = score
-    if mask is not None:
-        w = w * mask
-    if softmax:
-        if mask is not None:
-            w = w + -1.e9 * (1 - mask)
-        w = w.softmax(dim=-1)
-    return (w.unsqueeze(-1) * h).sum(dim=1)
 
 
 @pytest.mark.parametrize("softmax", [False, True])
