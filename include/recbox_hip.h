@@ -1273,6 +1273,54 @@ int rbx_addattn_bwd(const float* d_dout, int64_t dout_stride_b, const float* d_x
                     const float* d_alpha, float eps, int64_t batch, int32_t seq_len, int32_t dim, int32_t hidden,
                     int32_t dtype, float* d_dx, float* d_dctx, float* d_dv, float* d_dpre, void* d_workspace,
                     size_t workspace_bytes, void* stream);
+
+/* ---- FiBiNet: SENET gate and bilinear pair interaction (csrc/rbx_bilinear.hip; additions only, the version stays) -----------
+ * Replaces, under third_party/rechub/basic/layers.py (SENETLayer, BiLinearInteractionLayer) and models/ranking/fibinet.py:31-38,
+ * P = F (F - 1) / 2 nn.Linear calls on [B, 1, D] slices run twice per step, a torch.cat of 2 P pieces and a flatten.  B = batch,
+ * F = fields, D = dim, R = reduced.  d_x is read at x[b x_stride_b + f x_stride_f + d], d < D.
+ *   z[b, f] = mean_d x[b, f, d]    h = relu(w1 z)    a = act(w2 h)        d_w1 [R, F], d_w2 [F, R] contiguous (nn.Linear.weight,
+ *                                                                         no bias); act: 0 = relu, 1 = sigmoid
+ *   rbx_senet_gate_fwd  one launch, x read once; writes d_a [B, F] and d_h [B, R] (for the backward).
+ *   rbx_senet_gate_bwd  from d_da [B, F], d_a and d_h as the forward wrote them: d_dx [B, F, D] contiguous = dz_f / D, written
+ *                       (accumulate = 0) or added into what d_dx holds (accumulate != 0: a dx that rbx_bilinear_pairs_bwd
+ *                       wrote); d_dw1 [R, F], d_dw2 [F, R]: one row per workgroup in the workspace
+ *                       (rbx_senet_gate_bwd_workspace_size), added in ascending order by a second launch.
+ *   out[b, p, :] = (x[b, i] W_m(p)) * x[b, j] for the pairs p = (i, j), i < j, in itertools.combinations order (i outer);
+ *   out[b, P + p, :] = (a[b, i] a[b, j]) * out[b, p, :] when d_a [B, F] is not NULL -- the bilinear of x * a[..., None].
+ *   kind: 0 = field_all (m = 0, M = 1 matrix), 1 = field_each (m = i, M = F), 2 = field_interaction (m = p, M = P); d_w
+ *   [M, D, D] contiguous, a matrix stored [in, out] (transposed = 0) or [out, in] (transposed != 0: nn.Linear.weight).
+ *   rbx_bilinear_pairs_fwd  one launch.  16 samples of x are staged in LDS once per workgroup, x_i W runs on
+ *                           v_mfma_f32_16x16x4_f32 (exact fp32), W is read through L2.  Row r of sample b is written at
+ *                           d_out[b out_stride_b + r D + d]: P rows, or 2 P with d_a.
+ *   rbx_bilinear_pairs_bwd  d_dout addressed like d_out (dout_stride_b).  With g = dout1 + a_i a_j dout2 and L = x_i W
+ *                           recomputed: dx_j += g L, dx_i += (g x_j) W^T, da_i += s a_j, da_j += s a_i with
+ *                           s = sum_d dout2 L x_j, dW_m += x_i^T (g x_j).  Writes d_dx [B, F, D] and d_dw [M, D, D] (laid out as
+ *                           d_w) in full and, with d_a and a non-NULL d_da, d_da [B, F].  Three launches: dx / da per tile of
+ *                           16 samples; dW per (sample chunk, pair group) into the workspace
+ *                           (rbx_bilinear_pairs_bwd_workspace_size: [chunks, P, D, D]); a tail that folds chunks and pairs onto
+ *                           their matrix in ascending order.  Nothing of size [B, P, D] is allocated or expected.
+ * Supported (rbx_senet_gate_supported / rbx_bilinear_pairs_supported; dtype = the RBX_* code of every float tensor): RBX_F32,
+ * 2 <= F <= 64, D in {4, 8, 16, 32}, 1 <= R <= 32; x and dx 16-byte aligned, x strides multiples of 4.  Anything else:
+ * RBX_ERR_UNSUPPORTED before any launch.  batch = 0 launches nothing.  No atomics, every sum in a fixed order: two runs give the
+ * same bits.  Every launch goes to `stream`; no call allocates, clears, copies or reads back: capturable. */
+int rbx_senet_gate_supported(int32_t fields, int32_t dim, int32_t reduced, int32_t dtype);
+int rbx_senet_gate_fwd(const float* d_x, int64_t x_stride_b, int64_t x_stride_f, const float* d_w1, const float* d_w2,
+                       int64_t batch, int32_t fields, int32_t dim, int32_t reduced, int32_t act, int32_t dtype, float* d_a,
+                       float* d_h, void* stream);
+size_t rbx_senet_gate_bwd_workspace_size(int64_t batch, int32_t fields, int32_t reduced);
+int rbx_senet_gate_bwd(const float* d_da, const float* d_x, int64_t x_stride_b, int64_t x_stride_f, const float* d_w1,
+                       const float* d_w2, const float* d_a, const float* d_h, int64_t batch, int32_t fields, int32_t dim,
+                       int32_t reduced, int32_t act, int32_t dtype, int32_t accumulate, float* d_dx, float* d_dw1, float* d_dw2,
+                       void* d_workspace, size_t workspace_bytes, void* stream);
+int rbx_bilinear_pairs_supported(int32_t fields, int32_t dim, int32_t dtype);
+int rbx_bilinear_pairs_fwd(const float* d_x, int64_t x_stride_b, int64_t x_stride_f, const float* d_w, const float* d_a,
+                           int64_t batch, int32_t fields, int32_t dim, int32_t kind, int32_t transposed, int32_t dtype,
+                           float* d_out, int64_t out_stride_b, void* stream);
+size_t rbx_bilinear_pairs_bwd_workspace_size(int64_t batch, int32_t fields, int32_t dim);
+int rbx_bilinear_pairs_bwd(const float* d_dout, int64_t dout_stride_b, const float* d_x, int64_t x_stride_b, int64_t x_stride_f,
+                           const float* d_w, const float* d_a, int64_t batch, int32_t fields, int32_t dim, int32_t kind,
+                           int32_t transposed, int32_t dtype, float* d_dx, float* d_da, float* d_dw, void* d_workspace,
+                           size_t workspace_bytes, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -101,6 +101,7 @@ _RECHUB = {
     "models.ranking.din": ("recbox_amd.rechub.models.ranking", ["DIN", "ActivationUnit"]),
     "models.ranking.deepfm": ("recbox_amd.rechub.models.ranking", ["DeepFM"]),
     "models.ranking.deepffm": ("recbox_amd.rechub.models.ranking", ["DeepFFM", "FatDeepFFM"]),
+    "models.ranking.fibinet": ("recbox_amd.rechub.models.ranking", ["FiBiNet"]),
     "models.multi_task": ("recbox_amd.rechub.models.multi_task", ["SharedBottom", "ESMM", "MMOE", "PLE", "AITM", "CGC"]),
     "models.multi_task.shared_bottom": ("recbox_amd.rechub.models.multi_task", ["SharedBottom"]),
     "models.multi_task.esmm": ("recbox_amd.rechub.models.multi_task", ["ESMM"]),
@@ -112,7 +113,7 @@ _RECHUB = {
 
 # Names a path gained after its entry was published.  ``alias_table()`` keeps an entry as it was first listed (callers compare
 # entries); ``install()`` binds these as well.
-_RECHUB_ALSO = {"models.matching.comirec": ["ComirecSA"]}
+_RECHUB_ALSO = {"models.matching.comirec": ["ComirecSA"], "models.ranking": ["FiBiNet"]}
 
 
 def alias_also():

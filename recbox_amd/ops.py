@@ -133,6 +133,12 @@ class config(object):
     # torch.cat into [B, E, H], a [B, E, H] product per gate that autograd keeps, and a sum.  Off, or for what
     # expert_mix_supported refuses: that composition (expert_mix_torch).  Measurements: profiles/expert_mix/INDEX.md.
     expert_mix_fused = os.environ.get("RECBOX_AMD_EXPERT_MIX_FUSED", "1") != "0"
+    # FiBiNet (rechub's SENETLayer + BiLinearInteractionLayer): the gate as one launch and the P = F(F-1)/2 bilinear pairs of x
+    # and of the gated x as one launch that writes the MLP's [B, 2P, D] input in place, x_i W on the fp32 MFMA (senet_gate,
+    # bilinear_pairs: csrc/rbx_bilinear.hip) instead of left products, an indexed multiply per branch and a torch.cat that
+    # autograd keeps.  Off, or for what bilinear_pairs_supported refuses: that composition (bilinear_pairs_torch).
+    # Measurements: profiles/fibinet/INDEX.md.
+    bilinear_fused = os.environ.get("RECBOX_AMD_BILINEAR_FUSED", "1") != "0"
 
 
 def _require_cuda(t, what):
@@ -5010,3 +5016,215 @@ def expert_mix(experts, gates, select=None, softmax=True):
     if not _expert_mix_fused_ok(experts, gates, select):
         return expert_mix_torch(experts, gates, select, softmax)
     return _ExpertMix.apply(select, bool(softmax), len(experts), *(experts + gates))
+
+
+# ---- FiBiNet: SENET gate and bilinear pair interaction (csrc/rbx_bilinear.hip) ------------------------------------------------
+BILINEAR_KINDS = ("field_all", "field_each", "field_interaction")
+BILINEAR_DIMS = (4, 8, 16, 32)
+BILINEAR_MAX_FIELDS, SENET_MAX_REDUCED = 64, 32
+_SENET_ACTS = {"relu": 0, "sigmoid": 1}
+_pair_index_cache = {}
+
+
+def _bilinear_kind(kind):
+    if kind not in BILINEAR_KINDS:
+        raise NotImplementedError("bilinear_pairs: kind %r is none of %s" % (kind, ", ".join(BILINEAR_KINDS)))
+    return BILINEAR_KINDS.index(kind)
+
+
+def bilinear_matrices(kind, n_fields):
+    """How many [D, D] matrices ``kind`` has over ``n_fields`` fields: 1, F or P = F (F - 1) / 2."""
+    F = int(n_fields)
+    return (1, F, F * (F - 1) // 2)[_bilinear_kind(kind)]
+
+
+def _pair_index(F, device):
+    """(i, j) index tensors of the P pairs in ``itertools.combinations`` order (i outer), cached per device."""
+    key = (F, str(device))
+    if key not in _pair_index_cache:
+        ii, jj = torch.triu_indices(F, F, offset=1)
+        _pair_index_cache[key] = (ii.to(device), jj.to(device))
+    return _pair_index_cache[key]
+
+
+def senet_gate_supported(n_fields, dim, reduced, dtype=torch.float32):
+    """Whether the fused gate takes this shape (rbx_senet_gate_supported): float32, 2 .. 64 fields, dim 4 / 8 / 16 / 32, a
+    hidden layer of 1 .. 32 units."""
+    if dtype not in _DTYPE_CODE:
+        return False
+    return bool(lib.rbx_senet_gate_supported(int(n_fields), int(dim), int(reduced), _DTYPE_CODE[dtype]))
+
+
+def bilinear_pairs_supported(n_fields, dim, dtype=torch.float32):
+    """Whether the fused pair op takes this shape (rbx_bilinear_pairs_supported): float32, 2 .. 64 fields, dim 4 / 8 / 16 / 32.
+    What it refuses (a wider dim among it) runs ``bilinear_pairs_torch``."""
+    if dtype not in _DTYPE_CODE:
+        return False
+    return bool(lib.rbx_bilinear_pairs_supported(int(n_fields), int(dim), _DTYPE_CODE[dtype]))
+
+
+def senet_gate_torch(x, w1, w2, act="relu"):
+    """The reference's composition (rechub basic/layers.py, SENETLayer): ``mean`` over the embedding, two bias-free Linears with
+    a ReLU between them and ``act`` after them.  Same signature and result as ``senet_gate``."""
+    if act not in _SENET_ACTS:
+        raise ValueError("senet_gate: act %r is neither 'relu' nor 'sigmoid'" % (act,))
+    z = torch.mean(x, dim=-1)
+    y = torch.nn.functional.linear(torch.relu(torch.nn.functional.linear(z, w1)), w2)
+    return torch.relu(y) if act == "relu" else torch.sigmoid(y)
+
+
+def _bilinear_left(x, W, k, transposed, ii):
+    """x_i W_m(p) for every pair: [B, P, D]."""
+    Wm = W.transpose(1, 2) if transposed else W                                     # [M, in, out]
+    if k == 0:
+        return torch.matmul(x, Wm[0])[:, ii]
+    if k == 1:
+        return torch.einsum("bfd,fde->bfe", x, Wm)[:, ii]
+    return torch.einsum("bpd,pde->bpe", x[:, ii], Wm)
+
+
+def bilinear_pairs_torch(x, W, kind, transposed=False, scale=None):
+    """The composition: the left products as one GEMM per kind, an indexed multiply per branch, and with ``scale`` the second
+    branch over ``x * scale[..., None]`` and a ``torch.cat`` -- the reference's arithmetic (BiLinearInteractionLayer run on x and
+    on SENETLayer's output) without its P small Linears.  Same signature and result as ``bilinear_pairs``."""
+    k = _bilinear_kind(kind)
+    ii, jj = _pair_index(x.shape[1], x.device)
+    out = _bilinear_left(x, W, k, transposed, ii) * x[:, jj]
+    if scale is None:
+        return out
+    v = x * scale.unsqueeze(-1)
+    return torch.cat([out, _bilinear_left(v, W, k, transposed, ii) * v[:, jj]], dim=1)
+
+
+def _fields_in_place(x):
+    """Whether the kernels can read x [B, F, D] where it lies: unit inner stride, strides multiples of 4 floats, a 16-byte
+    aligned base (a column block of a wider tensor qualifies)."""
+    return (x.stride(2) == 1 and x.data_ptr() % 16 == 0 and x.stride(1) % 4 == 0 and x.stride(1) >= x.shape[2]
+            and x.stride(0) % 4 == 0 and x.stride(0) >= 0)
+
+
+class _SenetGate(torch.autograd.Function):
+    """a [B, F] of ``senet_gate``: ONE launch forward (rbx_senet_gate_fwd); the backward (rbx_senet_gate_bwd) is one launch
+    plus the tail that adds the per-workgroup rows of dw1 / dw2.  Saved: x, w1, w2, a and h [B, R]."""
+
+    @staticmethod
+    def forward(ctx, x, w1, w2, act):
+        w1, w2 = w1.contiguous(), w2.contiguous()
+        B, F, D = x.shape
+        R = w1.shape[0]
+        a = torch.empty((B, F), dtype=torch.float32, device=x.device)
+        h = torch.empty((B, R), dtype=torch.float32, device=x.device)
+        check(_timed(("senet_gate_fwd", B, F, D, R),
+                     lambda: lib.rbx_senet_gate_fwd(_ptr(x), x.stride(0), x.stride(1), _ptr(w1), _ptr(w2), B, F, D, R, act,
+                                                    _lib.RBX_F32, _ptr(a), _ptr(h), _stream())))
+        ctx.save_for_backward(x, w1, w2, a, h)
+        ctx.act = act
+        return a
+
+    @staticmethod
+    def backward(ctx, da):
+        x, w1, w2, a, h = ctx.saved_tensors
+        B, F, D = x.shape
+        R = w1.shape[0]
+        da = da.float().contiguous()
+        dx = torch.empty((B, F, D), dtype=torch.float32, device=x.device)
+        dw1, dw2 = torch.empty_like(w1), torch.empty_like(w2)
+        nbytes = lib.rbx_senet_gate_bwd_workspace_size(B, F, R)
+        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+        check(_timed(("senet_gate_bwd", B, F, D, R),
+                     lambda: lib.rbx_senet_gate_bwd(_ptr(da), _ptr(x), x.stride(0), x.stride(1), _ptr(w1), _ptr(w2), _ptr(a),
+                                                    _ptr(h), B, F, D, R, ctx.act, _lib.RBX_F32, 0, _ptr(dx), _ptr(dw1),
+                                                    _ptr(dw2), _ptr(ws), nbytes, _stream())))
+        return dx, dw1, dw2, None
+
+
+def _senet_fused_ok(x, w1, w2):
+    """The refusals of ``senet_gate`` that run the composition: the switch, CPU or non-float32 tensors, shapes that do not fit
+    each other, an empty batch, strides the kernels cannot read in place, what ``senet_gate_supported`` refuses."""
+    if not config.bilinear_fused or x.dim() != 3 or x.shape[0] == 0 or w1.dim() != 2 or w2.dim() != 2:
+        return False
+    if any((not t.is_cuda) or t.dtype != torch.float32 for t in (x, w1, w2)):
+        return False
+    F, D, R = x.shape[1], x.shape[2], w1.shape[0]
+    if tuple(w1.shape) != (R, F) or tuple(w2.shape) != (F, R) or not senet_gate_supported(F, D, R):
+        return False
+    return _fields_in_place(x)
+
+
+def senet_gate(x, w1, w2, act="relu"):
+    """SENET's field gate (FiBiNet): ``x`` [B, F, D], ``w1`` [R, F], ``w2`` [F, R] (``nn.Linear.weight``, bias-free) ->
+    ``a`` [B, F] = ``act(w2 relu(w1 mean_d x))``, ``act`` 'relu' (rechub) or 'sigmoid'.  One autograd node, x read once per
+    pass.  CPU or non-float32 tensors, ``B == 0``, strides that cannot be read in place, what ``senet_gate_supported`` refuses
+    and ``config.bilinear_fused = False`` run ``senet_gate_torch``."""
+    if act not in _SENET_ACTS:
+        raise ValueError("senet_gate: act %r is neither 'relu' nor 'sigmoid'" % (act,))
+    if not _senet_fused_ok(x, w1, w2):
+        return senet_gate_torch(x, w1, w2, act)
+    return _SenetGate.apply(x, w1, w2, _SENET_ACTS[act])
+
+
+class _BilinearPairs(torch.autograd.Function):
+    """out [B, P or 2 P, D] of ``bilinear_pairs``: ONE launch forward (rbx_bilinear_pairs_fwd); the backward
+    (rbx_bilinear_pairs_bwd) recomputes x_i W.  Saved: x, W and scale -- nothing of the size of out."""
+
+    @staticmethod
+    def forward(ctx, x, W, scale, kind, transposed):
+        W = W.contiguous()
+        scale = scale.contiguous() if scale is not None else None
+        B, F, D = x.shape
+        P = F * (F - 1) // 2
+        rows = 2 * P if scale is not None else P
+        out = torch.empty((B, rows, D), dtype=torch.float32, device=x.device)
+        check(_timed(("bilinear_pairs_fwd", B, F, D, kind),
+                     lambda: lib.rbx_bilinear_pairs_fwd(_ptr(x), x.stride(0), x.stride(1), _ptr(W), _ptr(scale), B, F, D, kind,
+                                                        int(transposed), _lib.RBX_F32, _ptr(out), rows * D, _stream())))
+        ctx.save_for_backward(x, W, scale)
+        ctx.kind, ctx.transposed = kind, bool(transposed)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, W, scale = ctx.saved_tensors
+        B, F, D = x.shape
+        if dout.dtype != torch.float32 or not dout.is_contiguous():
+            dout = dout.float().contiguous()
+        dx = torch.empty((B, F, D), dtype=torch.float32, device=x.device)
+        dW = torch.empty_like(W)
+        da = torch.empty((B, F), dtype=torch.float32, device=x.device) if scale is not None else None
+        nbytes = lib.rbx_bilinear_pairs_bwd_workspace_size(B, F, D)
+        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+        check(_timed(("bilinear_pairs_bwd", B, F, D, ctx.kind),
+                     lambda: lib.rbx_bilinear_pairs_bwd(_ptr(dout), dout.stride(0), _ptr(x), x.stride(0), x.stride(1), _ptr(W),
+                                                        _ptr(scale), B, F, D, ctx.kind, int(ctx.transposed), _lib.RBX_F32,
+                                                        _ptr(dx), _ptr(da), _ptr(dW), _ptr(ws), nbytes, _stream())))
+        return dx, dW, da, None, None
+
+
+def _bilinear_fused_ok(x, W, k, scale):
+    """The refusals of ``bilinear_pairs`` that run the composition (see ``_senet_fused_ok``)."""
+    if not config.bilinear_fused or x.dim() != 3 or x.shape[0] == 0 or W.dim() != 3:
+        return False
+    tensors = (x, W) if scale is None else (x, W, scale)
+    if any((not t.is_cuda) or t.dtype != torch.float32 for t in tensors):
+        return False
+    B, F, D = x.shape
+    if not bilinear_pairs_supported(F, D) or tuple(W.shape) != ((1, F, F * (F - 1) // 2)[k], D, D):
+        return False
+    if scale is not None and tuple(scale.shape) != (B, F):
+        return False
+    return _fields_in_place(x)
+
+
+def bilinear_pairs(x, W, kind, transposed=False, scale=None):
+    """FiBiNet's bilinear interaction over all field pairs: ``x`` [B, F, D], ``W`` [M, D, D] with ``kind`` 'field_all' (M = 1),
+    'field_each' (M = F) or 'field_interaction' (M = P = F (F - 1) / 2), each matrix [in, out] or, ``transposed``, [out, in]
+    (``nn.Linear.weight``) -> [B, P, D], ``out[:, p] = (x[:, i] @ W_m(p)) * x[:, j]`` for the pairs i < j in
+    ``itertools.combinations`` order.  With ``scale`` [B, F] (SENET's gate) the result is [B, 2 P, D]: rows P .. 2 P - 1 are the
+    same interaction of ``x * scale[..., None]``, formed as ``scale_i scale_j`` times rows 0 .. P - 1 -- no second GEMM, no
+    concatenation; ``scale`` takes part in autograd.  One autograd node that saves x, W and scale only.  CPU or non-float32
+    tensors, ``B == 0``, strides that cannot be read in place, what ``bilinear_pairs_supported`` refuses (a dim above 32) and
+    ``config.bilinear_fused = False`` run ``bilinear_pairs_torch``."""
+    k = _bilinear_kind(kind)
+    if not _bilinear_fused_ok(x, W, k, scale):
+        return bilinear_pairs_torch(x, W, kind, transposed, scale)
+    return _BilinearPairs.apply(x, W, scale, k, bool(transposed))

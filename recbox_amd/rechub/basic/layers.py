@@ -469,3 +469,51 @@ class GRU(nn.Module):
                              h0[k] if h0 is not None else None, lengths)
             finals.append(h_n)
         return (x if self.batch_first else x.transpose(0, 1)), torch.stack(finals, dim=0)
+
+
+class SENETLayer(nn.Module):
+    """FiBiNet's field gate (layers.py SENETLayer): ``mlp`` = Linear(F, R), ReLU, Linear(R, F), ReLU without biases,
+    R = max(1, int(F / reduction_ratio)); parameters ``mlp.0.weight`` and ``mlp.2.weight``.  ``gate(x)`` [B, F] is one
+    ``ops.senet_gate`` call; ``forward(x)`` returns ``x * gate(x)[..., None]`` as the reference does."""
+
+    def __init__(self, num_fields, reduction_ratio=3):
+        super(SENETLayer, self).__init__()
+        reduced_size = max(1, int(num_fields / reduction_ratio))
+        self.mlp = nn.Sequential(nn.Linear(num_fields, reduced_size, bias=False), nn.ReLU(),
+                                 nn.Linear(reduced_size, num_fields, bias=False), nn.ReLU())
+
+    def gate(self, x):
+        return ops.senet_gate(x, self.mlp[0].weight, self.mlp[2].weight, "relu")
+
+    def forward(self, x):
+        return x * self.gate(x).unsqueeze(-1)
+
+
+class BiLinearInteractionLayer(nn.Module):
+    """FiBiNet's bilinear interaction (layers.py BiLinearInteractionLayer): ``bilinear_layer`` is one bias-free Linear(D, D)
+    ('field_all': ``bilinear_layer.weight``) or a ModuleList of F ('field_each') or P = F (F - 1) / 2 ('field_interaction')
+    of them (``bilinear_layer.<k>.weight``); any other type raises NotImplementedError.  ``forward(x)`` -> [B, P, D] is one
+    ``ops.bilinear_pairs`` call over the stacked ``nn.Linear`` weights, read as [out, in]; ``forward(x, scale)`` -> [B, 2 P, D]
+    appends the interaction of ``x * scale[..., None]`` (FiBiNet's second branch)."""
+
+    def __init__(self, input_dim, num_fields, bilinear_type="field_interaction"):
+        super(BiLinearInteractionLayer, self).__init__()
+        self.bilinear_type = bilinear_type
+        if self.bilinear_type == "field_all":
+            self.bilinear_layer = nn.Linear(input_dim, input_dim, bias=False)
+        elif self.bilinear_type == "field_each":
+            self.bilinear_layer = nn.ModuleList([nn.Linear(input_dim, input_dim, bias=False) for _ in range(num_fields)])
+        elif self.bilinear_type == "field_interaction":
+            self.bilinear_layer = nn.ModuleList([nn.Linear(input_dim, input_dim, bias=False)
+                                                 for _ in range(num_fields * (num_fields - 1) // 2)])
+        else:
+            raise NotImplementedError()
+
+    def stacked_weight(self):
+        """[M, D, D]: the matrices as ``nn.Linear`` stores them ([out, in])."""
+        if self.bilinear_type == "field_all":
+            return self.bilinear_layer.weight.unsqueeze(0)
+        return torch.stack([m.weight for m in self.bilinear_layer], dim=0)
+
+    def forward(self, x, scale=None):
+        return ops.bilinear_pairs(x, self.stacked_weight(), self.bilinear_type, transposed=True, scale=scale)

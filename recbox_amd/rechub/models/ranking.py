@@ -6,7 +6,7 @@ import torch
 
 from ... import dense, ops
 from ..basic.features import DenseFeature, SparseFeature
-from ..basic.layers import CEN, FFM, FM, LR, MLP, EmbeddingLayer
+from ..basic.layers import CEN, FFM, FM, LR, MLP, BiLinearInteractionLayer, EmbeddingLayer, SENETLayer
 
 
 class DeepFM(torch.nn.Module):
@@ -99,6 +99,32 @@ class DIN(torch.nn.Module):
         pooled = [unit(history[:, i], target[:, i]) for i, unit in enumerate(self.attention_layers)]
         mlp_in = torch.cat(pooled + [target.flatten(start_dim=1), profile.flatten(start_dim=1)], dim=1)
         return torch.sigmoid(self.mlp(mlp_in).squeeze(1))
+
+
+class FiBiNet(torch.nn.Module):
+    """FiBiNET (fibinet.py): the bilinear interactions of the field embeddings and of their SENET-gated copies feed an MLP.
+    ``num_fields`` counts the unshared ``SparseFeature``s, the embedding width is the largest ``embed_dim``, the MLP reads
+    ``F (F - 1) D`` columns.  The forward is one lookup, one ``ops.senet_gate`` and one ``ops.bilinear_pairs(..., scale=a)``
+    whose [B, 2 P, D] result is the MLP's input viewed flat: no gated copy of x, no second interaction, no concatenation."""
+
+    def __init__(self, features, mlp_params, reduction_ratio=3, bilinear_type="field_interaction", **kwargs):
+        super(FiBiNet, self).__init__()
+        self.features = features
+        self.embedding = EmbeddingLayer(features)
+        embedding_dim = max([fea.embed_dim for fea in features])
+        num_fields = len([fea.embed_dim for fea in features if isinstance(fea, SparseFeature) and fea.shared_with is None])
+        self.senet_layer = SENETLayer(num_fields, reduction_ratio)
+        self.bilinear_interaction = BiLinearInteractionLayer(embedding_dim, num_fields, bilinear_type)
+        self.dims = num_fields * (num_fields - 1) * embedding_dim
+        self.mlp = MLP(self.dims, **mlp_params)
+
+    def forward(self, x):
+        from .multi_task import _embed, _mlp                            # the lookup and the MLP for CPU tensors as well
+        embed_x = _embed(self.embedding, x, self.features, False)       # [B, F, D]
+        a = self.senet_layer.gate(embed_x)                              # [B, F]
+        shallow_part = self.bilinear_interaction(embed_x, a)            # [B, 2 P, D]: rows of x, then rows of x * a
+        mlp_out = _mlp(self.mlp, shallow_part.flatten(start_dim=1))
+        return torch.sigmoid(mlp_out.squeeze(1))
 
 
 class _DeepFFMBase(torch.nn.Module):
