@@ -1321,6 +1321,36 @@ int rbx_bilinear_pairs_bwd(const float* d_dout, int64_t dout_stride_b, const flo
                            const float* d_w, const float* d_a, int64_t batch, int32_t fields, int32_t dim, int32_t kind,
                            int32_t transposed, int32_t dtype, float* d_dx, float* d_da, float* d_dw, void* d_workspace,
                            size_t workspace_bytes, void* stream);
+
+/* ---- DCN-V2: mixture of low-rank cross experts, one layer per call (csrc/rbx_crossmix.hip; additions only, the version stays) --
+ * Replaces, under third_party/rechub/basic/layers.py (CrossNetMix) and models/ranking/dcn_v2.py, four matmuls and a Hadamard
+ * product per expert, a torch.stack into [B, n, E] and a matmul with the softmax.  B = batch, E = experts, r = rank.  d_x0 and
+ * d_xl are read at x[b stride + k], k < n; d_u, d_v [E, n, r], d_c [E, r, r], d_g [E, n] (the gates' Linear(n, 1) weights, one row
+ * per expert), d_b [n], all contiguous.
+ *   z_e = x_l . G_e    p = softmax_e(z)    h1_e = tanh(x_l V_e)    h2_e = tanh(h1_e C_e^T)
+ *   mix = sum_e p_e (h2_e U_e^T) + b       out = x_l + x0 * mix
+ *   rbx_crossmix_fwd  one launch: 16 rows of x_l staged in LDS once, [V | G^T] and U on v_mfma_f32_16x16x4_f32 (exact fp32), the
+ *                     tanh / C / softmax stages in LDS; row b is written at d_out[b out_stride + k].  Nothing of size [B, E r] is
+ *                     written.
+ *   rbx_crossmix_bwd  d_dout addressed with dout_stride.  Recomputes h1, h2, p, mix from x_l.  Writes d_dxl (dxl_stride) = dout +
+ *                     sum_e da1_e V_e^T + dz G, d_dx0 (dx0_stride) = dout * mix, d_du, d_dv, d_dc, d_db in full and d_dg; with
+ *                     accumulate != 0, d_dx0 and d_dg are added to instead (the layers of a stack share x0 and G).  One row
+ *                     launch, then per weight gradient a chunked batch reduction on the MFMA and a tail that adds the chunks in
+ *                     ascending order; their [B, E r] operands live in the workspace (rbx_crossmix_bwd_workspace_size).
+ * Supported (rbx_crossmix_supported; dtype = the RBX_* code of every tensor): RBX_F32, 1 <= n <= 640, 1 <= E <= 8, r in {4, 8, 16,
+ * 32, 64}, E r <= 256.  Anything else: RBX_ERR_UNSUPPORTED before any launch.  batch = 0 launches nothing.  No atomics, every sum
+ * in a fixed order: two runs give the same bits.  Every launch goes to `stream`; no call allocates, clears, copies or reads back:
+ * capturable. */
+int rbx_crossmix_supported(int32_t n, int32_t experts, int32_t rank, int32_t dtype);
+int rbx_crossmix_fwd(const float* d_x0, int64_t x0_stride, const float* d_xl, int64_t xl_stride, const float* d_u,
+                     const float* d_v, const float* d_c, const float* d_g, const float* d_b, int64_t batch, int32_t n,
+                     int32_t experts, int32_t rank, int32_t dtype, float* d_out, int64_t out_stride, void* stream);
+size_t rbx_crossmix_bwd_workspace_size(int64_t batch, int32_t n, int32_t experts, int32_t rank);
+int rbx_crossmix_bwd(const float* d_dout, int64_t dout_stride, const float* d_x0, int64_t x0_stride, const float* d_xl,
+                     int64_t xl_stride, const float* d_u, const float* d_v, const float* d_c, const float* d_g, const float* d_b,
+                     int64_t batch, int32_t n, int32_t experts, int32_t rank, int32_t dtype, int32_t accumulate, float* d_dxl,
+                     int64_t dxl_stride, float* d_dx0, int64_t dx0_stride, float* d_du, float* d_dv, float* d_dc, float* d_dg,
+                     float* d_db, void* d_workspace, size_t workspace_bytes, void* stream);
 #ifdef __cplusplus
 }
 #endif

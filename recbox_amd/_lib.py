@@ -302,6 +302,11 @@ SIGNATURES = {
     "rbx_bilinear_pairs_bwd_workspace_size": (_sz, [_i64, _i32, _i32]),
     "rbx_bilinear_pairs_bwd": (ctypes.c_int, [_P, _i64, _P, _i64, _i64, _P, _P, _i64, _i32, _i32, _i32, _i32, _i32, _P, _P, _P,
                                               _P, _sz, _P]),
+    "rbx_crossmix_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32]),
+    "rbx_crossmix_fwd": (ctypes.c_int, [_P, _i64, _P, _i64, _P, _P, _P, _P, _P, _i64, _i32, _i32, _i32, _i32, _P, _i64, _P]),
+    "rbx_crossmix_bwd_workspace_size": (_sz, [_i64, _i32, _i32, _i32]),
+    "rbx_crossmix_bwd": (ctypes.c_int, [_P, _i64, _P, _i64, _P, _i64, _P, _P, _P, _P, _P, _i64, _i32, _i32, _i32, _i32, _i32, _P,
+                                        _i64, _P, _i64, _P, _P, _P, _P, _P, _P, _sz, _P]),
 }
 
 

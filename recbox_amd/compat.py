@@ -102,6 +102,10 @@ _RECHUB = {
     "models.ranking.deepfm": ("recbox_amd.rechub.models.ranking", ["DeepFM"]),
     "models.ranking.deepffm": ("recbox_amd.rechub.models.ranking", ["DeepFFM", "FatDeepFFM"]),
     "models.ranking.fibinet": ("recbox_amd.rechub.models.ranking", ["FiBiNet"]),
+    "models.ranking.dcn": ("recbox_amd.rechub.models.ranking", ["DCN"]),
+    "models.ranking.dcn_v2": ("recbox_amd.rechub.models.ranking", ["DCNv2"]),
+    "models.ranking.edcn": ("recbox_amd.rechub.models.ranking", ["EDCN", "BridgeModule", "RegulationModule"]),
+    "models.ranking.widedeep": ("recbox_amd.rechub.models.ranking", ["WideDeep"]),
     "models.multi_task": ("recbox_amd.rechub.models.multi_task", ["SharedBottom", "ESMM", "MMOE", "PLE", "AITM", "CGC"]),
     "models.multi_task.shared_bottom": ("recbox_amd.rechub.models.multi_task", ["SharedBottom"]),
     "models.multi_task.esmm": ("recbox_amd.rechub.models.multi_task", ["ESMM"]),
@@ -113,7 +117,7 @@ _RECHUB = {
 
 # Names a path gained after its entry was published.  ``alias_table()`` keeps an entry as it was first listed (callers compare
 # entries); ``install()`` binds these as well.
-_RECHUB_ALSO = {"models.matching.comirec": ["ComirecSA"], "models.ranking": ["FiBiNet"]}
+_RECHUB_ALSO = {"models.matching.comirec": ["ComirecSA"], "models.ranking": ["FiBiNet", "DCN", "DCNv2", "EDCN", "WideDeep"]}
 
 
 def alias_also():

@@ -139,6 +139,11 @@ class config(object):
     # autograd keeps.  Off, or for what bilinear_pairs_supported refuses: that composition (bilinear_pairs_torch).
     # Measurements: profiles/fibinet/INDEX.md.
     bilinear_fused = os.environ.get("RECBOX_AMD_BILINEAR_FUSED", "1") != "0"
+    # DCN-V2 (rechub's CrossNetMix): a layer of the low-rank cross expert mixture as one launch forward that keeps the row tile
+    # on chip (cross_mix: csrc/rbx_crossmix.hip) and saves no activation, instead of the batched-GEMM composition whose
+    # [B, E r] and [B, n] intermediates autograd keeps per layer.  Off, or for what cross_mix_supported refuses: that
+    # composition (cross_mix_torch).  Measurements: profiles/crossmix/INDEX.md.
+    crossmix_fused = os.environ.get("RECBOX_AMD_CROSSMIX_FUSED", "1") != "0"
 
 
 def _require_cuda(t, what):
@@ -5228,3 +5233,133 @@ def bilinear_pairs(x, W, kind, transposed=False, scale=None):
     if not _bilinear_fused_ok(x, W, k, scale):
         return bilinear_pairs_torch(x, W, kind, transposed, scale)
     return _BilinearPairs.apply(x, W, scale, k, bool(transposed))
+
+
+# ---- DCN-V2: mixture of low-rank cross experts (csrc/rbx_crossmix.hip) --------------------------------------------------------
+CROSSMIX_RANKS = (4, 8, 16, 32, 64)
+CROSSMIX_MAX_N, CROSSMIX_MAX_EXPERTS, CROSSMIX_MAX_ER = 640, 8, 256
+# Where the fused route was measured at least level with the composition (profiles/crossmix/INDEX.md): batches up to 4096 rows
+# and B n E r up to 2^28.  Above either, the kernels (whose time grows with B while the composition is still bound by its
+# launches at 4096) measured 4-5 x slower at B = 65 536, so cross_mix runs the composition there.
+CROSSMIX_MAX_BATCH, CROSSMIX_MAX_WORK = 4096, 1 << 28
+
+
+def cross_mix_supported(n, experts, rank, dtype=torch.float32):
+    """Whether the fused layer takes this shape (rbx_crossmix_supported): float32, 1 <= n <= 640, 1 .. 8 experts, rank 4 / 8 /
+    16 / 32 / 64, experts * rank <= 256.  What it refuses runs ``cross_mix_torch``."""
+    if dtype not in _DTYPE_CODE:
+        return False
+    return bool(lib.rbx_crossmix_supported(int(n), int(experts), int(rank), _DTYPE_CODE[dtype]))
+
+
+def cross_mix_torch(x0, U_list, V_list, C_list, gate_w, bias_list):
+    """The composition: per layer one GEMM for every V_e, one batched [r, r] product, one GEMM for every U_e applied to the
+    gate-scaled h_e (sum_e p_e = 1, so the mixture of the reference's per-expert ``x0 * (U_e h_e + b)`` is
+    ``x0 * (sum_e p_e U_e h_e + b)``), a softmax and two tanh passes -- plain torch ops, so it runs on CPU tensors.  Same
+    signature and result as ``cross_mix``."""
+    x_l = x0
+    for U, V, C, b in zip(U_list, V_list, C_list, bias_list):
+        E, n, r = V.shape
+        p = torch.softmax(torch.matmul(x_l, gate_w.t()), dim=1)                                # [B, E]
+        h = torch.tanh(torch.matmul(x_l, V.permute(1, 0, 2).reshape(n, E * r)))                # every x_l V_e: [B, E r]
+        h = torch.tanh(torch.einsum("bej,eij->bei", h.view(h.shape[0], E, r), C))              # h1_e C_e^T: [B, E, r]
+        h = (h * p.unsqueeze(2)).reshape(h.shape[0], E * r)
+        mix = torch.matmul(h, U.permute(0, 2, 1).reshape(E * r, n)) + b.reshape(-1)
+        x_l = x_l + x0 * mix
+    return x_l
+
+
+class _CrossMix(torch.autograd.Function):
+    """The layer stack of ``cross_mix``: ONE launch per layer forward (rbx_crossmix_fwd); the backward (rbx_crossmix_bwd) walks
+    the layers in reverse, recomputes every activation from x_l and adds dx0 and dG up in place.  Saved: x0, the weights and the
+    L layer outputs -- nothing of size [B, E r]."""
+
+    @staticmethod
+    def forward(ctx, x0, gate_w, L, *weights):
+        weights = [w.contiguous() for w in weights]
+        U, V, C = weights[:L], weights[L:2 * L], weights[2 * L:3 * L]
+        bias = [b.reshape(-1) for b in weights[3 * L:]]
+        gate_w = gate_w.contiguous()
+        B, n = x0.shape
+        E, r = V[0].shape[0], V[0].shape[2]
+        xs = [x0]
+        for l in range(L):
+            x_l, out = xs[-1], torch.empty((B, n), dtype=torch.float32, device=x0.device)
+            check(_timed(("crossmix_fwd", B, n, E, r),
+                         lambda: lib.rbx_crossmix_fwd(_ptr(x0), x0.stride(0), _ptr(x_l), x_l.stride(0), _ptr(U[l]), _ptr(V[l]),
+                                                      _ptr(C[l]), _ptr(gate_w), _ptr(bias[l]), B, n, E, r, _lib.RBX_F32,
+                                                      _ptr(out), n, _stream())))
+            xs.append(out)
+        ctx.save_for_backward(gate_w, *(xs[:L] + U + V + C + bias))
+        ctx.L, ctx.bias_shapes = L, [tuple(w.shape) for w in weights[3 * L:]]
+        return xs[-1]
+
+    @staticmethod
+    def backward(ctx, dout):
+        L = ctx.L
+        saved = ctx.saved_tensors
+        gate_w, xs = saved[0], saved[1:1 + L]
+        U, V, C, bias = (saved[1 + k * L:1 + (k + 1) * L] for k in range(1, 5))
+        x0 = xs[0]
+        B, n = x0.shape
+        E, r = V[0].shape[0], V[0].shape[2]
+        if dout.dtype != torch.float32 or dout.stride(1) != 1 or dout.stride(0) < n:
+            dout = dout.float().contiguous()
+        dev = x0.device
+        dx0 = torch.empty((B, n), dtype=torch.float32, device=dev)
+        dG = torch.empty_like(gate_w)
+        nbytes = lib.rbx_crossmix_bwd_workspace_size(B, n, E, r)
+        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+        dU, dV, dC, db = [None] * L, [None] * L, [None] * L, [None] * L
+        for l in range(L - 1, -1, -1):
+            dxl = torch.empty((B, n), dtype=torch.float32, device=dev)
+            dU[l], dV[l], dC[l] = torch.empty_like(U[l]), torch.empty_like(V[l]), torch.empty_like(C[l])
+            db[l] = torch.empty(n, dtype=torch.float32, device=dev)
+            x_l, d = xs[l], dout
+            check(_timed(("crossmix_bwd", B, n, E, r),
+                         lambda: lib.rbx_crossmix_bwd(_ptr(d), d.stride(0), _ptr(x0), x0.stride(0), _ptr(x_l), x_l.stride(0),
+                                                      _ptr(U[l]), _ptr(V[l]), _ptr(C[l]), _ptr(gate_w), _ptr(bias[l]), B, n, E,
+                                                      r, _lib.RBX_F32, int(l != L - 1), _ptr(dxl), n, _ptr(dx0), n, _ptr(dU[l]),
+                                                      _ptr(dV[l]), _ptr(dC[l]), _ptr(dG), _ptr(db[l]), _ptr(ws), nbytes,
+                                                      _stream())))
+            dout = dxl
+        dx0.add_(dout)                                            # layer 0 reads x0 as its x_l
+        db = [g.view(s) for g, s in zip(db, ctx.bias_shapes)]
+        return (dx0, dG, None) + tuple(dU + dV + dC + db)
+
+
+def _crossmix_fused_ok(x0, U_list, V_list, C_list, gate_w, bias_list):
+    """The refusals of ``cross_mix`` that run the composition: the switch, CPU or non-float32 tensors, shapes that do not fit
+    each other, an empty batch or stack, a view without a unit inner stride, what ``cross_mix_supported`` refuses, and the
+    shape classes that measured slower than the composition (``CROSSMIX_MAX_BATCH``, ``CROSSMIX_MAX_WORK``)."""
+    L = len(V_list)
+    if not config.crossmix_fused or L == 0 or x0.dim() != 2 or x0.shape[0] == 0 or gate_w.dim() != 2:
+        return False
+    if not (len(U_list) == len(C_list) == len(bias_list) == L) or V_list[0].dim() != 3:
+        return False
+    tensors = [x0, gate_w] + list(U_list) + list(V_list) + list(C_list) + list(bias_list)
+    if any((not t.is_cuda) or t.dtype != torch.float32 for t in tensors):
+        return False
+    n = x0.shape[1]
+    E, r = V_list[0].shape[0], V_list[0].shape[2]
+    if not cross_mix_supported(n, E, r) or tuple(gate_w.shape) != (E, n):
+        return False
+    if x0.shape[0] > CROSSMIX_MAX_BATCH or x0.shape[0] * n * E * r > CROSSMIX_MAX_WORK:
+        return False
+    for U, V, C, b in zip(U_list, V_list, C_list, bias_list):
+        if tuple(U.shape) != (E, n, r) or tuple(V.shape) != (E, n, r) or tuple(C.shape) != (E, r, r) or b.numel() != n:
+            return False
+    return x0.stride(1) == 1 and x0.stride(0) >= n
+
+
+def cross_mix(x0, U_list, V_list, C_list, gate_w, bias_list):
+    """DCN-V2's mixture of low-rank cross experts over a stack of layers: ``x0`` [B, n]; per layer ``U``, ``V`` [E, n, r], ``C``
+    [E, r, r] and a bias of n elements; ``gate_w`` [E, n], the E bias-free Linear(n, 1) gates shared by the layers -> [B, n]:
+    ``x_{l+1} = x_l + x0 * (sum_e p_e U_e tanh(C_e tanh(V_e^T x_l)) + b)`` with ``p = softmax_e(x_l G^T)``.  One autograd node
+    for the stack, one launch per layer forward, no activation saved.  CPU or non-float32 tensors, ``B == 0``, a view without
+    a unit inner stride, what ``cross_mix_supported`` refuses (a rank of 6, n above 640), more than 4096 rows or
+    ``B n E r > 2^28`` (measured slower than the composition) and ``config.crossmix_fused = False`` run ``cross_mix_torch``."""
+    if not _crossmix_fused_ok(x0, U_list, V_list, C_list, gate_w, bias_list):
+        return cross_mix_torch(x0, U_list, V_list, C_list, gate_w, bias_list)
+    L = len(V_list)
+    return _CrossMix.apply(x0, gate_w, L, *(list(U_list) + list(V_list) + list(C_list) + list(bias_list)))

@@ -517,3 +517,89 @@ class BiLinearInteractionLayer(nn.Module):
 
     def forward(self, x, scale=None):
         return ops.bilinear_pairs(x, self.stacked_weight(), self.bilinear_type, transposed=True, scale=scale)
+
+
+def _project(x, layer):
+    """``layer(x)`` for a bias-free nn.Linear: the dense GEMM on the GPU, the module itself for CPU tensors."""
+    return ops.linear(x, layer.weight) if x.is_cuda else layer(x)
+
+
+def _cross(x0, xi, h, bias):
+    """``xi + x0 * h + bias``: one pass (``ops.cross``) on the GPU."""
+    return ops.cross(x0, xi, h, bias) if x0.is_cuda else x0 * h + bias + xi
+
+
+class CrossLayer(nn.Module):
+    """One DCN cross term without its residual (layers.py CrossLayer, used by EDCN): ``w(x_i) * x_0 + b`` with ``w`` a bias-free
+    Linear(input_dim, 1) and ``b`` [input_dim].  ``residual(x_0, x_i)`` is ``x_i + forward(x_0, x_i)`` in one pass."""
+
+    def __init__(self, input_dim):
+        super(CrossLayer, self).__init__()
+        self.w = torch.nn.Linear(input_dim, 1, bias=False)
+        self.b = torch.nn.Parameter(torch.zeros(input_dim))
+
+    def forward(self, x_0, x_i):
+        return _project(x_i, self.w) * x_0 + self.b
+
+    def residual(self, x_0, x_i):
+        return _cross(x_0, x_i, _project(x_i, self.w), self.b)
+
+
+class CrossNetwork(nn.Module):
+    """DCN's cross network (layers.py CrossNetwork): ``x = x0 * w_i(x) + b_i + x`` per layer, ``w`` a ModuleList of bias-free
+    Linear(input_dim, 1), ``b`` a ParameterList of [input_dim]; over ``ops.linear`` + ``ops.cross``."""
+
+    def __init__(self, input_dim, num_layers):
+        super().__init__()
+        self.num_layers = num_layers
+        self.w = torch.nn.ModuleList([torch.nn.Linear(input_dim, 1, bias=False) for _ in range(num_layers)])
+        self.b = torch.nn.ParameterList([torch.nn.Parameter(torch.zeros((input_dim,))) for _ in range(num_layers)])
+
+    def forward(self, x):
+        x0 = x
+        for i in range(self.num_layers):
+            x = _cross(x0, x, _project(x, self.w[i]), self.b[i])
+        return x
+
+
+class CrossNetV2(nn.Module):
+    """DCN-V2's full-rank cross network (layers.py CrossNetV2): ``x = x0 * w_i(x) + b_i + x`` with ``w`` bias-free
+    Linear(input_dim, input_dim) and a separate ``b``; over ``ops.linear`` + ``ops.cross``."""
+
+    def __init__(self, input_dim, num_layers):
+        super().__init__()
+        self.num_layers = num_layers
+        self.w = torch.nn.ModuleList([torch.nn.Linear(input_dim, input_dim, bias=False) for _ in range(num_layers)])
+        self.b = torch.nn.ParameterList([torch.nn.Parameter(torch.zeros((input_dim,))) for _ in range(num_layers)])
+
+    def forward(self, x):
+        x0 = x
+        for i in range(self.num_layers):
+            x = _cross(x0, x, _project(x, self.w[i]), self.b[i])
+        return x
+
+
+class CrossNetMix(nn.Module):
+    """DCN-V2's mixture of low-rank cross experts (layers.py CrossNetMix): per layer ``u_list`` / ``v_list`` [experts, input_dim,
+    low_rank], ``c_list`` [experts, low_rank, low_rank] (xavier-normal) and ``bias`` [input_dim, 1]; ``gating`` is one bias-free
+    Linear(input_dim, 1) per expert, shared by the layers.  The stack is one ``ops.cross_mix`` call.  The reference ends with
+    ``x_l.squeeze()``, so a batch of one returns [input_dim]; so does this."""
+
+    def __init__(self, input_dim, num_layers=2, low_rank=32, num_experts=4):
+        super(CrossNetMix, self).__init__()
+        self.num_layers = num_layers
+        self.num_experts = num_experts
+        self.u_list = torch.nn.ParameterList([nn.Parameter(nn.init.xavier_normal_(
+            torch.empty(num_experts, input_dim, low_rank))) for i in range(self.num_layers)])
+        self.v_list = torch.nn.ParameterList([nn.Parameter(nn.init.xavier_normal_(
+            torch.empty(num_experts, input_dim, low_rank))) for i in range(self.num_layers)])
+        self.c_list = torch.nn.ParameterList([nn.Parameter(nn.init.xavier_normal_(
+            torch.empty(num_experts, low_rank, low_rank))) for i in range(self.num_layers)])
+        self.gating = nn.ModuleList([nn.Linear(input_dim, 1, bias=False) for i in range(self.num_experts)])
+        self.bias = torch.nn.ParameterList([nn.Parameter(nn.init.zeros_(
+            torch.empty(input_dim, 1))) for i in range(self.num_layers)])
+
+    def forward(self, x):
+        gate_w = torch.cat([g.weight for g in self.gating], dim=0)                     # [E, input_dim]
+        x_l = ops.cross_mix(x, list(self.u_list), list(self.v_list), list(self.c_list), gate_w, list(self.bias))
+        return x_l.unsqueeze(2).squeeze()

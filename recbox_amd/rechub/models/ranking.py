@@ -1,12 +1,15 @@
 """DeepFM (drop-in for ``torch_rechub.models.ranking.DeepFM``,
 /root/reference/recbox/third_party/rechub/models/ranking/deepfm.py:14-42), DIN with its ActivationUnit
 (``torch_rechub.models.ranking.din``, rechub/models/ranking/din.py:16-91), and DeepFFM / FatDeepFFM
-(``torch_rechub.models.ranking.deepffm``, rechub/models/ranking/deepffm.py:15-123)."""
+(``torch_rechub.models.ranking.deepffm``, rechub/models/ranking/deepffm.py:15-123), FiBiNet, and the Deep & Cross family: DCN,
+DCNv2, EDCN with its BridgeModule / RegulationModule, and WideDeep (rechub/models/ranking/dcn.py, dcn_v2.py, edcn.py,
+widedeep.py)."""
 import torch
 
 from ... import dense, ops
 from ..basic.features import DenseFeature, SparseFeature
-from ..basic.layers import CEN, FFM, FM, LR, MLP, BiLinearInteractionLayer, EmbeddingLayer, SENETLayer
+from ..basic.layers import (CEN, FFM, FM, LR, MLP, BiLinearInteractionLayer, CrossLayer, CrossNetMix, CrossNetV2, CrossNetwork,
+                            EmbeddingLayer, SENETLayer)
 
 
 class DeepFM(torch.nn.Module):
@@ -196,3 +199,191 @@ class FatDeepFFM(_DeepFFMBase):
         y_ffm = self.mlp_out(aem)
         y = y_linear + y_ffm
         return torch.sigmoid(y.squeeze(1) + self.b)
+
+
+# ---- Deep & Cross family (dcn.py, dcn_v2.py, edcn.py, widedeep.py) ------------------------------------------------------------
+def _seq(seq, x):
+    """An ``nn.Sequential`` over the dense kernels on the GPU, as it stands for CPU tensors."""
+    return dense.run_sequential(seq, x) if x.is_cuda else seq(x)
+
+
+def _lr(lr, x):
+    from .multi_task import _linear
+    y = _linear(x, lr.fc)
+    return torch.sigmoid(y) if lr.sigmoid else y
+
+
+class WideDeep(torch.nn.Module):
+    """Wide & Deep (widedeep.py): an LR over the flattened ``wide_features`` plus an MLP over the ``deep_features``."""
+
+    def __init__(self, wide_features, deep_features, mlp_params):
+        super(WideDeep, self).__init__()
+        self.wide_features = wide_features
+        self.deep_features = deep_features
+        self.wide_dims = sum([fea.embed_dim for fea in wide_features])
+        self.deep_dims = sum([fea.embed_dim for fea in deep_features])
+        self.linear = LR(self.wide_dims)
+        self.embedding = EmbeddingLayer(wide_features + deep_features)
+        self.mlp = MLP(self.deep_dims, **mlp_params)
+
+    def forward(self, x):
+        from .multi_task import _embed, _mlp
+        input_wide = _embed(self.embedding, x, self.wide_features, True)
+        input_deep = _embed(self.embedding, x, self.deep_features, True)
+        y = _lr(self.linear, input_wide) + _mlp(self.mlp, input_deep)
+        return torch.sigmoid(y.squeeze(1))
+
+
+class DCN(torch.nn.Module):
+    """Deep & Cross Network (dcn.py): ``CrossNetwork`` and an MLP without output layer read the flattened embeddings side by
+    side; an LR over [cross | mlp] gives the logit."""
+
+    def __init__(self, features, n_cross_layers, mlp_params):
+        super().__init__()
+        self.features = features
+        self.dims = sum([fea.embed_dim for fea in features])
+        self.embedding = EmbeddingLayer(features)
+        self.cn = CrossNetwork(self.dims, n_cross_layers)
+        self.mlp = MLP(self.dims, output_layer=False, **mlp_params)
+        self.linear = LR(self.dims + mlp_params["dims"][-1])
+
+    def forward(self, x):
+        from .multi_task import _embed, _mlp
+        embed_x = _embed(self.embedding, x, self.features, True)
+        x_stack = torch.cat([self.cn(embed_x), _mlp(self.mlp, embed_x)], dim=1)
+        return torch.sigmoid(_lr(self.linear, x_stack).squeeze(1))
+
+
+class DCNv2(torch.nn.Module):
+    """DCN-V2 (dcn_v2.py): ``CrossNetMix`` (``use_low_rank_mixture``, the default: one ``ops.cross_mix`` call for the stack) or
+    ``CrossNetV2``; ``model_structure`` 'parallel' (cross beside ``parallel_dnn``), 'stacked' (``stacked_dnn`` after the cross
+    net) or 'crossnet_only'; an LR gives the logit."""
+
+    def __init__(self, features, n_cross_layers, mlp_params, model_structure="parallel", use_low_rank_mixture=True, low_rank=32,
+                 num_experts=4, **kwargs):
+        super(DCNv2, self).__init__()
+        self.features = features
+        self.dims = sum([fea.embed_dim for fea in features])
+        self.embedding = EmbeddingLayer(features)
+        if use_low_rank_mixture:
+            self.crossnet = CrossNetMix(self.dims, n_cross_layers, low_rank=low_rank, num_experts=num_experts)
+        else:
+            self.crossnet = CrossNetV2(self.dims, n_cross_layers)
+        self.model_structure = model_structure
+        assert self.model_structure in ["crossnet_only", "stacked", "parallel"], \
+            "model_structure={} not supported!".format(self.model_structure)
+        if self.model_structure == "stacked":
+            self.stacked_dnn = MLP(self.dims, output_layer=False, **mlp_params)
+            final_dim = mlp_params["dims"][-1]
+        if self.model_structure == "parallel":
+            self.parallel_dnn = MLP(self.dims, output_layer=False, **mlp_params)
+            final_dim = mlp_params["dims"][-1] + self.dims
+        if self.model_structure == "crossnet_only":
+            final_dim = self.dims
+        self.linear = LR(final_dim)
+
+    def forward(self, x):
+        from .multi_task import _embed, _mlp
+        embed_x = _embed(self.embedding, x, self.features, True)
+        cross_out = self.crossnet(embed_x)
+        if self.model_structure == "crossnet_only":
+            final_out = cross_out
+        elif self.model_structure == "stacked":
+            final_out = _mlp(self.stacked_dnn, cross_out)
+        else:
+            final_out = torch.cat([cross_out, _mlp(self.parallel_dnn, embed_x)], dim=1)
+        return torch.sigmoid(_lr(self.linear, final_out).squeeze(1))
+
+
+class BridgeModule(torch.nn.Module):
+    """EDCN's bridge between the cross and the deep branch (edcn.py BridgeModule): 'hadamard_product', 'pointwise_addition',
+    'concatenation' (``concat_pooling``: Linear(2 n, n), ReLU) or 'attention_pooling' (``attention_x`` / ``attention_h``:
+    Linear, ReLU, bias-free Linear, Softmax)."""
+
+    def __init__(self, input_dim, bridge_type):
+        super(BridgeModule, self).__init__()
+        assert bridge_type in ["hadamard_product", "pointwise_addition", "concatenation",
+                               "attention_pooling"], 'bridge_type= is not supported'.format(bridge_type)
+        self.bridge_type = bridge_type
+        if bridge_type == "concatenation":
+            self.concat_pooling = torch.nn.Sequential(torch.nn.Linear(input_dim * 2, input_dim), torch.nn.ReLU())
+        elif bridge_type == "attention_pooling":
+            self.attention_x = torch.nn.Sequential(torch.nn.Linear(input_dim, input_dim), torch.nn.ReLU(),
+                                                   torch.nn.Linear(input_dim, input_dim, bias=False), torch.nn.Softmax(dim=-1))
+            self.attention_h = torch.nn.Sequential(torch.nn.Linear(input_dim, input_dim), torch.nn.ReLU(),
+                                                   torch.nn.Linear(input_dim, input_dim, bias=False), torch.nn.Softmax(dim=-1))
+
+    def forward(self, x, h):
+        if self.bridge_type == "hadamard_product":
+            out = x * h
+        elif self.bridge_type == "pointwise_addition":
+            out = x + h
+        elif self.bridge_type == "concatenation":
+            out = _seq(self.concat_pooling, torch.cat([x, h], dim=-1))
+        elif self.bridge_type == "attention_pooling":
+            out = _seq(self.attention_x, x) * x + _seq(self.attention_h, h) * h
+        return out
+
+
+class RegulationModule(torch.nn.Module):
+    """EDCN's field-wise gates (edcn.py RegulationModule), as written there: ``g1`` / ``g2`` [num_fields], each entry soft-maxed
+    on its own (a softmax over one element: 1) and repeated over its field's columns."""
+
+    def __init__(self, num_fields, dims, tau, use_regulation=True):
+        super(RegulationModule, self).__init__()
+        self.use_regulation = use_regulation
+        if self.use_regulation:
+            self.num_fields = num_fields
+            self.dims = dims
+            self.tau = tau
+            self.g1 = torch.nn.Parameter(torch.ones(num_fields))
+            self.g2 = torch.nn.Parameter(torch.ones(num_fields))
+
+    def forward(self, x):
+        if self.use_regulation:
+            g1 = torch.cat([(self.g1[i] / self.tau).softmax(dim=-1).unsqueeze(-1).repeat(1, self.dims[i])
+                            for i in range(self.num_fields)], dim=-1)
+            g2 = torch.cat([(self.g2[i] / self.tau).softmax(dim=-1).unsqueeze(-1).repeat(1, self.dims[i])
+                            for i in range(self.num_fields)], dim=-1)
+            out1, out2 = g1 * x, g2 * x
+        else:
+            out1, out2 = x, x
+        return out1, out2
+
+
+class EDCN(torch.nn.Module):
+    """Enhanced DCN (edcn.py): per layer a ``CrossLayer`` with its residual and an MLP of dims [n, n] run side by side, joined by
+    a ``BridgeModule`` and split again by a ``RegulationModule``; an LR over [cross | deep | bridge].  As in the reference, the
+    caller's ``mlp_params["dims"]`` is overwritten with [n, n]."""
+
+    def __init__(self, features, n_cross_layers, mlp_params, bridge_type="hadamard_product", use_regulation_module=True,
+                 temperature=1):
+        super().__init__()
+        self.features = features
+        self.n_cross_layers = n_cross_layers
+        self.num_fields = len(features)
+        self.dims = sum([fea.embed_dim for fea in features])
+        self.fea_dims = [fea.embed_dim for fea in features]
+        self.embedding = EmbeddingLayer(features)
+        self.cross_layers = torch.nn.ModuleList([CrossLayer(self.dims) for _ in range(n_cross_layers)])
+        self.bridge_modules = torch.nn.ModuleList([BridgeModule(self.dims, bridge_type) for _ in range(n_cross_layers)])
+        self.regulation_modules = torch.nn.ModuleList([RegulationModule(self.num_fields, self.fea_dims, tau=temperature,
+                                                                        use_regulation=use_regulation_module)
+                                                       for _ in range(n_cross_layers)])
+        mlp_params["dims"] = [self.dims, self.dims]
+        self.mlps = torch.nn.ModuleList([MLP(self.dims, output_layer=False, **mlp_params) for _ in range(n_cross_layers)])
+        self.linear = LR(self.dims * 3)
+
+    def forward(self, x):
+        from .multi_task import _embed, _mlp
+        embed_x = _embed(self.embedding, x, self.features, True)
+        cross_i, deep_i = self.regulation_modules[0](embed_x)
+        cross_0 = cross_i
+        for i in range(self.n_cross_layers):
+            if i > 0:
+                cross_i, deep_i = self.regulation_modules[i](bridge_i)
+            cross_i = self.cross_layers[i].residual(cross_0, cross_i)
+            deep_i = _mlp(self.mlps[i], deep_i)
+            bridge_i = self.bridge_modules[i](cross_i, deep_i)
+        x_stack = torch.cat([cross_i, deep_i, bridge_i], dim=1)
+        return torch.sigmoid(_lr(self.linear, x_stack).squeeze(1))
