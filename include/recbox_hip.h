@@ -1351,6 +1351,34 @@ int rbx_crossmix_bwd(const float* d_dout, int64_t dout_stride, const float* d_x0
                      int64_t batch, int32_t n, int32_t experts, int32_t rank, int32_t dtype, int32_t accumulate, float* d_dxl,
                      int64_t dxl_stride, float* d_dx0, int64_t dx0_stride, float* d_du, float* d_dv, float* d_dc, float* d_dg,
                      float* d_db, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ---- In-batch negatives: the band of the [B, B] cosine matrix (csrc/rbx_inbatch.hip; additions only, the version stays) ------
+ * Replaces, under third_party/rechub/models/matching/youtube_sbc.py, torch.cosine_similarity(user.unsqueeze(1), item, dim=2) (a
+ * [B, B, D] broadcast), "- log(sample_weight)" on the [B, B] result and the [index0, index1] gather that keeps B (n_neg + 1) of
+ * its entries.  d_u, d_v are read at x[b stride + c], c < dim (16-byte aligned base, stride a multiple of 4); d_w [batch] or
+ * NULL (no correction).  With j = (i + k) mod batch, k = 0 .. n_neg:
+ *   ru_i = 1 / max(|u_i|, eps)    rv_j = 1 / max(|v_j|, eps)    scores[i, k] = (<u_i, v_j> ru_i rv_j - log w_j) inv_temperature
+ *   rbx_inbatch_band_fwd  one launch: a workgroup stages 16 user rows and the 16 + n_neg item rows of their band in LDS once
+ *                         (wrapped through mod batch), a lane group of 16 per row.  Writes d_scores[i scores_stride + k] and
+ *                         d_ru, d_rv [batch] for the backward.
+ *   rbx_inbatch_band_bwd  d_g read at g[i g_stride + k].  One launch: the same tile writes du_i (over the row's own band), dv_j and
+ *                         dw_j = -inv_temperature sum_k g[(j - k) mod batch, k] / w_j (over the mirrored band); the cosines are
+ *                         recomputed, a norm under eps is a constant denominator.  Any of d_du, d_dv, d_dw may be NULL (not
+ *                         wanted); d_dw needs d_w.
+ * Supported (rbx_inbatch_band_supported; dtype = the RBX_* code of every tensor): RBX_F32, dim a multiple of 4 in [4, 512],
+ * 1 <= n_neg <= rbx_inbatch_band_max_neg(dim) = the largest n_neg <= 64 whose backward image, (16 + n_neg) (2 dim + 2 n_neg + 4)
+ * floats, fits 160 KB of LDS (64 up to dim 128, 50 at 256, 22 at 512), and n_neg < batch.  Anything else: RBX_ERR_UNSUPPORTED
+ * before any launch.  batch = 0 launches nothing.  No atomics, every sum in a fixed order: two runs give the same bits.  Every
+ * launch goes to `stream`; no call allocates, clears, copies or reads back: capturable. */
+int rbx_inbatch_band_max_neg(int32_t dim);
+int rbx_inbatch_band_supported(int32_t dim, int32_t n_neg, int32_t dtype);
+int rbx_inbatch_band_fwd(const float* d_u, int64_t u_stride, const float* d_v, int64_t v_stride, const float* d_w, int64_t batch,
+                         int32_t dim, int32_t n_neg, float eps, float inv_temperature, int32_t dtype, float* d_scores,
+                         int64_t scores_stride, float* d_ru, float* d_rv, void* stream);
+int rbx_inbatch_band_bwd(const float* d_g, int64_t g_stride, const float* d_u, int64_t u_stride, const float* d_v,
+                         int64_t v_stride, const float* d_w, const float* d_ru, const float* d_rv, int64_t batch, int32_t dim,
+                         int32_t n_neg, float eps, float inv_temperature, int32_t dtype, float* d_du, int64_t du_stride,
+                         float* d_dv, int64_t dv_stride, float* d_dw, void* stream);
 #ifdef __cplusplus
 }
 #endif

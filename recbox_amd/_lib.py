@@ -307,6 +307,11 @@ SIGNATURES = {
     "rbx_crossmix_bwd_workspace_size": (_sz, [_i64, _i32, _i32, _i32]),
     "rbx_crossmix_bwd": (ctypes.c_int, [_P, _i64, _P, _i64, _P, _i64, _P, _P, _P, _P, _P, _i64, _i32, _i32, _i32, _i32, _i32, _P,
                                         _i64, _P, _i64, _P, _P, _P, _P, _P, _P, _sz, _P]),
+    "rbx_inbatch_band_max_neg": (ctypes.c_int, [_i32]),
+    "rbx_inbatch_band_supported": (ctypes.c_int, [_i32, _i32, _i32]),
+    "rbx_inbatch_band_fwd": (ctypes.c_int, [_P, _i64, _P, _i64, _P, _i64, _i32, _i32, _f32, _f32, _i32, _P, _i64, _P, _P, _P]),
+    "rbx_inbatch_band_bwd": (ctypes.c_int, [_P, _i64, _P, _i64, _P, _i64, _P, _P, _P, _i64, _i32, _i32, _f32, _f32, _i32, _P, _i64,
+                                            _P, _i64, _P, _P]),
 }
 
 

@@ -88,6 +88,9 @@ _RECHUB = {
     "basic.activation": ("recbox_amd.rechub.basic.layers", ["Dice", "activation_layer"]),
     "models.matching": ("recbox_amd.rechub.models.matching", ["DSSM", "YoutubeDNN", "SASRec", "MIND", "ComirecDR", "GRU4Rec",
                                                               "NARM", "ComirecSA", "SINE", "STAMP"]),
+    "models.matching.youtube_sbc": ("recbox_amd.rechub.models.matching", ["YoutubeSBC"]),
+    "models.matching.dssm_facebook": ("recbox_amd.rechub.models.matching", ["FaceBookDSSM"]),
+    "basic.loss_func": ("recbox_amd.rechub.basic.loss_func", ["HingeLoss", "BPRLoss"]),
     "models.matching.stamp": ("recbox_amd.rechub.models.matching", ["STAMP"]),
     "models.matching.sine": ("recbox_amd.rechub.models.matching", ["SINE"]),
     "models.matching.gru4rec": ("recbox_amd.rechub.models.matching", ["GRU4Rec"]),
@@ -117,7 +120,8 @@ _RECHUB = {
 
 # Names a path gained after its entry was published.  ``alias_table()`` keeps an entry as it was first listed (callers compare
 # entries); ``install()`` binds these as well.
-_RECHUB_ALSO = {"models.matching.comirec": ["ComirecSA"], "models.ranking": ["FiBiNet", "DCN", "DCNv2", "EDCN", "WideDeep"]}
+_RECHUB_ALSO = {"models.matching.comirec": ["ComirecSA"], "models.ranking": ["FiBiNet", "DCN", "DCNv2", "EDCN", "WideDeep"],
+                "models.matching": ["YoutubeSBC", "FaceBookDSSM"]}
 
 
 def alias_also():

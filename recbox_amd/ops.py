@@ -144,6 +144,11 @@ class config(object):
     # [B, E r] and [B, n] intermediates autograd keeps per layer.  Off, or for what cross_mix_supported refuses: that
     # composition (cross_mix_torch).  Measurements: profiles/crossmix/INDEX.md.
     crossmix_fused = os.environ.get("RECBOX_AMD_CROSSMIX_FUSED", "1") != "0"
+    # In-batch negatives (rechub's YoutubeSBC): the n_neg + 1 wide band of the [B, B] cosine matrix, with the sampling-bias
+    # correction, as one launch each way that stages every tower row once per tile (inbatch_band_scores: csrc/rbx_inbatch.hip)
+    # instead of the gather composition whose [B, n_neg + 1, D] copy of the item rows autograd keeps.  Off, or for what
+    # inbatch_band_supported refuses: that composition (inbatch_band_scores_torch).  Measurements: profiles/inbatch/INDEX.md.
+    inbatch_fused = os.environ.get("RECBOX_AMD_INBATCH_FUSED", "1") != "0"
 
 
 def _require_cuda(t, what):
@@ -5363,3 +5368,117 @@ def cross_mix(x0, U_list, V_list, C_list, gate_w, bias_list):
         return cross_mix_torch(x0, U_list, V_list, C_list, gate_w, bias_list)
     L = len(V_list)
     return _CrossMix.apply(x0, gate_w, L, *(list(U_list) + list(V_list) + list(C_list) + list(bias_list)))
+
+
+# ---- in-batch negatives: the band of the [B, B] cosine matrix (csrc/rbx_inbatch.hip) ------------------------------------------
+INBATCH_MAX_DIM = 512
+
+
+def inbatch_band_max_neg(dim):
+    """The largest ``n_neg`` the fused band kernels take at this ``dim`` (rbx_inbatch_band_max_neg): at most 64, and what the
+    backward's LDS image -- (16 + n_neg) (2 dim + 2 n_neg + 4) floats -- fits into 160 KB: 64 up to dim 128, 50 at 256, 22 at
+    512.  0 for a ``dim`` the kernels refuse."""
+    return int(lib.rbx_inbatch_band_max_neg(int(dim)))
+
+
+def inbatch_band_supported(batch, dim, n_neg, dtype=torch.float32):
+    """Whether the fused band kernels take this shape (rbx_inbatch_band_supported): float32, ``dim`` a multiple of 4 up to 512,
+    ``1 <= n_neg <= inbatch_band_max_neg(dim)`` and ``n_neg < batch``.  What it refuses runs ``inbatch_band_scores_torch``."""
+    if dtype not in _DTYPE_CODE:
+        return False
+    return int(n_neg) < int(batch) and bool(lib.rbx_inbatch_band_supported(int(dim), int(n_neg), _DTYPE_CODE[dtype]))
+
+
+def _inbatch_check(u, v, n_neg, weight):
+    if u.dim() != 2 or v.dim() != 2 or tuple(u.shape) != tuple(v.shape):
+        raise ValueError("inbatch_band_scores: u and v must both be [B, D] (got %s and %s)" % (tuple(u.shape), tuple(v.shape)))
+    if int(n_neg) < 0 or (int(n_neg) >= u.shape[0] and u.shape[0] > 0):
+        raise ValueError("inbatch_band_scores: n_neg = %d needs a batch above it (got %d rows)" % (int(n_neg), u.shape[0]))
+    if weight is not None and weight.numel() != u.shape[0]:
+        raise ValueError("inbatch_band_scores: weight must hold one value per row")
+
+
+def inbatch_band_scores_torch(u, v, n_neg, weight=None, temperature=1.0, eps=1e-8):
+    """The composition: the band's item rows gathered with ``(i + k) mod B`` indices into [B, n_neg + 1, D] -- never [B, B] or
+    [B, B, D] --, each norm clamped on its own as ``torch.cosine_similarity`` does.  Plain torch ops, so it runs on CPU and
+    float64 tensors.  Same signature and result as ``inbatch_band_scores``."""
+    _inbatch_check(u, v, n_neg, weight)
+    B = u.shape[0]
+    if B == 0:
+        return u.new_zeros((0, int(n_neg) + 1))
+    idx = (torch.arange(B, device=u.device).unsqueeze(1) + torch.arange(int(n_neg) + 1, device=u.device)) % B      # [B, n + 1]
+    ru = 1.0 / u.norm(dim=1).clamp_min(eps)
+    rv = 1.0 / v.norm(dim=1).clamp_min(eps)
+    scores = (u.unsqueeze(1) * v[idx]).sum(2) * ru.unsqueeze(1) * rv[idx]
+    if weight is not None:
+        scores = scores - torch.log(weight.reshape(-1))[idx]
+    return scores / temperature
+
+
+def _inbatch_rows(t):
+    """[B, D] as the kernels read it: float32, unit inner stride, 16-byte aligned rows (a column view of a wider block whose
+    offset and row stride are multiples of 4 is read in place)."""
+    if t.stride(1) != 1 or t.stride(0) < t.shape[1] or t.stride(0) % 4 != 0 or t.data_ptr() % 16 != 0:
+        t = t.contiguous()
+    return t
+
+
+class _InbatchBand(torch.autograd.Function):
+    """``inbatch_band_scores``: one launch forward (rbx_inbatch_band_fwd), one backward (rbx_inbatch_band_bwd).  Saved: u, v, the
+    weights and the two [B] inverse norms -- nothing of the band's size; the backward recomputes the cosines."""
+
+    @staticmethod
+    def forward(ctx, u, v, weight, n_neg, inv_t, eps):
+        u, v = _inbatch_rows(u), _inbatch_rows(v)
+        w = weight.reshape(-1).contiguous() if weight is not None else None
+        B, D = u.shape
+        scores = torch.empty((B, n_neg + 1), dtype=torch.float32, device=u.device)
+        ru = torch.empty(B, dtype=torch.float32, device=u.device)
+        rv = torch.empty(B, dtype=torch.float32, device=u.device)
+        check(_timed(("inbatch_band_fwd", B, D, n_neg),
+                     lambda: lib.rbx_inbatch_band_fwd(_ptr(u), u.stride(0), _ptr(v), v.stride(0), _ptr(w), B, D, n_neg, eps, inv_t,
+                                                      _lib.RBX_F32, _ptr(scores), n_neg + 1, _ptr(ru), _ptr(rv), _stream())))
+        ctx.save_for_backward(u, v, w, ru, rv)
+        ctx.meta = (n_neg, inv_t, eps, None if weight is None else tuple(weight.shape))
+        return scores
+
+    @staticmethod
+    def backward(ctx, g):
+        u, v, w, ru, rv = ctx.saved_tensors
+        n_neg, inv_t, eps, wshape = ctx.meta
+        B, D = u.shape
+        if g.dtype != torch.float32 or g.stride(1) != 1 or g.stride(0) < n_neg + 1:
+            g = g.float().contiguous()
+        du = torch.empty((B, D), dtype=torch.float32, device=u.device) if ctx.needs_input_grad[0] else None
+        dv = torch.empty((B, D), dtype=torch.float32, device=u.device) if ctx.needs_input_grad[1] else None
+        dw = torch.empty(B, dtype=torch.float32, device=u.device) if (w is not None and ctx.needs_input_grad[2]) else None
+        check(_timed(("inbatch_band_bwd", B, D, n_neg),
+                     lambda: lib.rbx_inbatch_band_bwd(_ptr(g), g.stride(0), _ptr(u), u.stride(0), _ptr(v), v.stride(0), _ptr(w),
+                                                      _ptr(ru), _ptr(rv), B, D, n_neg, eps, inv_t, _lib.RBX_F32, _ptr(du), D,
+                                                      _ptr(dv), D, _ptr(dw), _stream())))
+        return du, dv, (dw.view(wshape) if dw is not None else None), None, None, None
+
+
+def _inbatch_fused_ok(u, v, n_neg, weight):
+    """The refusals of ``inbatch_band_scores`` that run the composition: the switch, CPU or non-float32 tensors, an empty batch
+    and what ``inbatch_band_supported`` refuses."""
+    if not config.inbatch_fused or u.shape[0] == 0:
+        return False
+    if any(t is not None and ((not t.is_cuda) or t.dtype != torch.float32) for t in (u, v, weight)):
+        return False
+    return inbatch_band_supported(u.shape[0], u.shape[1], n_neg)
+
+
+def inbatch_band_scores(u, v, n_neg, weight=None, temperature=1.0, eps=1e-8):
+    """In-batch negatives with the sampling-bias correction: ``u``, ``v`` [B, D] (the two towers' outputs; column views of a
+    wider block are read in place), ``weight`` [B] or None -> ``scores`` [B, n_neg + 1] with
+    ``scores[i, k] = (cos(u_i, v_j) - log weight_j) / temperature``, ``j = (i + k) mod B`` -- the entries rechub's YoutubeSBC keeps
+    of its [B, B] matrix, with ``torch.cosine_similarity``'s norms (each clamped at ``eps`` on its own).  One launch each way;
+    nothing of size [B, B] or [B, n_neg + 1, D] is formed.  ``n_neg >= B`` raises ``ValueError``.  CPU or non-float32 tensors,
+    ``B == 0``, what ``inbatch_band_supported`` refuses (D = 6, D above 512, n_neg above ``inbatch_band_max_neg(D)``) and
+    ``config.inbatch_fused = False`` run ``inbatch_band_scores_torch``."""
+    _inbatch_check(u, v, n_neg, weight)
+    n_neg = int(n_neg)
+    if n_neg < 1 or not _inbatch_fused_ok(u, v, n_neg, weight):
+        return inbatch_band_scores_torch(u, v, n_neg, weight, temperature, eps)
+    return _InbatchBand.apply(u, v, weight, n_neg, 1.0 / float(temperature), float(eps))

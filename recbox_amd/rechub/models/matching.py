@@ -5,6 +5,7 @@ outputs and parameter names.  Compute: embedding + pooling in one gather launch,
 layers on the fp32 matrix cores, ``F.normalize`` and the pairwise dot as HIP kernels
 (``rbx_l2norm_*``, ``rbx_pairdot_*``), SASRec's causal attention as the fused LDS-resident
 kernel (``rbx_attn_*``)."""
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -12,6 +13,8 @@ import torch.nn.functional as F
 from ... import ops
 from ..basic.features import DenseFeature, SequenceFeature, SparseFeature
 from ..basic.layers import GRU, MLP, CapsuleNetwork, EmbeddingLayer, MultiInterestSA
+# a lookup / a tower of YoutubeSBC and FaceBookDSSM: the shared layers on the GPU, the reference's lines in ATen for CPU tensors
+from .multi_task import _embed as _embed_any, _mlp
 
 
 class DSSM(torch.nn.Module):
@@ -648,3 +651,127 @@ class STAMP(torch.nn.Module):
         h_t = ops.linear(torch.tanh(x_t), self.f_t[1].weight, self.f_t[1].bias)              # Eq. 9
         # Eq. 4 [B, V]: the table goes in as a view, as in NARM (it is also read by the lookups above)
         return ops.linear(h_s * h_t, self.item_emb.weight.view_as(self.item_emb.weight))
+
+
+class YoutubeSBC(torch.nn.Module):
+    """Sampling-bias-corrected in-batch softmax (drop-in for ``torch_rechub.models.matching.youtube_sbc.YoutubeSBC``): same
+    constructor, ``mode`` switch, ``index0`` / ``index1`` and parameter names.  The towers are the shared lookup and MLP; the
+    scores -- user i against items i, i + 1, .., i + n_neg (mod B), cosine minus log(sample weight), over the temperature -- are
+    one ``ops.inbatch_band_scores`` call: the reference's [B, B, D] broadcast of ``torch.cosine_similarity`` and its [B, B]
+    matrix are never formed.
+
+    A last batch of b < batch_size rows: the reference folds its stored ``index1`` twice, at batch_size when it is built and at
+    b when the short batch arrives, so user i meets item ``fold_b(fold_batch_size(i + k))``.  While ``b + n_neg <= batch_size``
+    that is ``(i + k) mod b`` and the band op serves it; beyond (the second fold then repeats an item) the same columns are
+    gathered with plain torch ops, as a freshly built reference model returns them.  The reference also writes that fold back
+    into ``index1`` through the slice view, which corrupts every later full batch; ``index0`` / ``index1`` are never changed
+    here."""
+
+    def __init__(self, user_features, item_features, sample_weight_feature, user_params, item_params, batch_size, n_neg=3,
+                 temperature=1.0):
+        super().__init__()
+        self.user_features = user_features
+        self.item_features = item_features
+        self.sample_weight_feature = sample_weight_feature
+        self.n_neg = n_neg
+        self.temperature = temperature
+        self.user_dims = sum([fea.embed_dim for fea in user_features])
+        self.item_dims = sum([fea.embed_dim for fea in item_features])
+        self.batch_size = batch_size
+        self.embedding = EmbeddingLayer(user_features + item_features + sample_weight_feature)
+        self.user_mlp = MLP(self.user_dims, output_layer=False, **user_params)
+        self.item_mlp = MLP(self.item_dims, output_layer=False, **item_params)
+        self.mode = None
+        # in-batch sampling index, kept as the reference builds it (the scores do not read it on a full batch)
+        self.index0 = np.repeat(np.arange(batch_size), n_neg + 1)
+        self.index1 = np.concatenate([np.arange(i, i + n_neg + 1) for i in range(batch_size)])
+        self.index1[np.where(self.index1 >= batch_size)] -= batch_size
+
+    def forward(self, x):
+        user_embedding = self.user_tower(x)
+        item_embedding = self.item_tower(x)
+        if self.mode == "user":
+            return user_embedding
+        if self.mode == "item":
+            return item_embedding
+        if all(isinstance(f, DenseFeature) for f in self.sample_weight_feature):
+            # dense values need no lookup launch: the columns the squeezed gather would lay out
+            sample_weight = torch.cat([x[f.name].float().unsqueeze(1) for f in self.sample_weight_feature], dim=1).squeeze(1)
+        else:
+            sample_weight = _embed_any(self.embedding, x, self.sample_weight_feature, True).squeeze(1)       # [B]
+        b = user_embedding.shape[0]
+        if b == self.batch_size or b + self.n_neg <= self.batch_size:
+            return ops.inbatch_band_scores(user_embedding, item_embedding, self.n_neg, weight=sample_weight,
+                                           temperature=self.temperature)
+        if b > self.batch_size:
+            raise ValueError("YoutubeSBC: a batch of %d rows, the model was built for batch_size = %d" % (b, self.batch_size))
+        # the short batch whose band crosses batch_size: the reference's doubly folded columns, on a copy
+        index1 = self.index1[:b * (self.n_neg + 1)].copy()
+        index1[np.where(index1 >= b)] -= b
+        cols = torch.as_tensor(index1, device=user_embedding.device).view(b, self.n_neg + 1)
+        items = item_embedding[cols]                                                                        # [b, n_neg + 1, D]
+        pred = torch.cosine_similarity(user_embedding.unsqueeze(1), items, dim=2)
+        return (pred - torch.log(sample_weight)[cols]) / self.temperature
+
+    def user_tower(self, x):
+        if self.mode == "item":
+            return None
+        return _mlp(self.user_mlp, _embed_any(self.embedding, x, self.user_features, True))
+
+    def item_tower(self, x):
+        if self.mode == "user":
+            return None
+        return _mlp(self.item_mlp, _embed_any(self.embedding, x, self.item_features, True))
+
+
+def _normalize_rows(x):
+    return ops.l2_normalize(x) if x.is_cuda else F.normalize(x, p=2, dim=1)
+
+
+def _row_dot(u, v):
+    return ops.pair_dot(u, v).squeeze(1) if u.is_cuda else torch.mul(u, v).sum(dim=1)
+
+
+class FaceBookDSSM(torch.nn.Module):
+    """Pair-wise two-tower trained with a hinge loss (drop-in for ``torch_rechub.models.matching.dssm_facebook.FaceBookDSSM``):
+    same constructor, ``mode`` switch, outputs ``(pos_score, neg_score)`` and parameter names.  Both towers end in
+    ``ops.l2_normalize``, the two scores are ``ops.pair_dot``; ``mode="item"`` returns the positive item's embedding before the
+    normalisation, as the reference does."""
+
+    def __init__(self, user_features, pos_item_features, neg_item_features, user_params, item_params, temperature=1.0):
+        super().__init__()
+        self.user_features = user_features
+        self.pos_item_features = pos_item_features
+        self.neg_item_features = neg_item_features
+        self.temperature = temperature
+        self.user_dims = sum([fea.embed_dim for fea in user_features])
+        self.item_dims = sum([fea.embed_dim for fea in pos_item_features])
+        self.embedding = EmbeddingLayer(user_features + pos_item_features + neg_item_features)
+        self.user_mlp = MLP(self.user_dims, output_layer=False, **user_params)
+        self.item_mlp = MLP(self.item_dims, output_layer=False, **item_params)
+        self.mode = None
+
+    def forward(self, x):
+        user_embedding = self.user_tower(x)
+        pos_item_embedding, neg_item_embedding = self.item_tower(x)
+        if self.mode == "user":
+            return user_embedding
+        if self.mode == "item":
+            return pos_item_embedding
+        return _row_dot(user_embedding, pos_item_embedding), _row_dot(user_embedding, neg_item_embedding)
+
+    def user_tower(self, x):
+        if self.mode == "item":
+            return None
+        input_user = _embed_any(self.embedding, x, self.user_features, True)
+        return _normalize_rows(_mlp(self.user_mlp, input_user))
+
+    def item_tower(self, x):
+        if self.mode == "user":
+            return None, None
+        input_item_pos = _embed_any(self.embedding, x, self.pos_item_features, True)
+        if self.mode == "item":
+            return _mlp(self.item_mlp, input_item_pos), None
+        input_item_neg = _embed_any(self.embedding, x, self.neg_item_features, True)
+        pos_embedding, neg_embedding = _mlp(self.item_mlp, input_item_pos), _mlp(self.item_mlp, input_item_neg)
+        return _normalize_rows(pos_embedding), _normalize_rows(neg_embedding)
