@@ -1274,6 +1274,37 @@ int rbx_addattn_bwd(const float* d_dout, int64_t dout_stride_b, const float* d_x
                     int32_t dtype, float* d_dx, float* d_dctx, float* d_dv, float* d_dpre, void* d_workspace,
                     size_t workspace_bytes, void* stream);
 
+/* ---- Attentional FM: pair-attention pooling (csrc/rbx_afm.hip; additions only, the version stays) ---------------------------
+ * Replaces the ATen lines of RecBole's AFM (third_party/recbole/model/context_aware_recommender/afm.py:75-99 over AttLayer,
+ * model/layers.py:236-261), whose pair products [B, P, D] and attention hidden layer [B, P, A] are written and kept by
+ * autograd.  B = batch, F = n_fields, D = dim, A = att_dim, P = F (F - 1) / 2 pairs k = (i, j), i < j, in row-major order:
+ *   p_k = x_i * x_j      s_k = sum_a h_a relu(W p_k)_a      a = softmax_k(s)      out = sum_k a_k p_k
+ * d_x is read at x[b x_stride_b + f x_stride_f + c], c < D; d_w [A, D] contiguous (no bias); d_h [A].
+ *   rbx_afm_fwd  one launch.  A wavefront stages one sample's x [F, D] in LDS and walks its pairs in tiles of 16: W p_k runs
+ *                on v_mfma_f32_16x16x4_f32 (A and the last tile padded inside the kernel) with p_k formed on the fly; relu,
+ *                the h product, the max-subtracted softmax and the weighted sum stay on chip.  The division is an IEEE
+ *                division: one pair gives a = 1 exactly, P equal logits 1.0f / P.  Writes d_out [B, D], d_stat [2, B] (the
+ *                maximum logit, then the sum of exp(s - max), per sample) and, when not NULL, d_attn [B, P].
+ *   rbx_afm_bwd  d_dout is read at dout[b dout_stride_b + c]; d_out and d_stat as the forward wrote them; attn has no
+ *                gradient of its own.  One launch recomputes p_k, the pre-activations and a_k and forms ds_k = a_k (dout . p_k
+ *                - dout . out), dpre_k = ds_k h [pre_k > 0], dp_k = a_k dout + W^T dpre_k; dx_i += dp_k x_j and dx_j +=
+ *                dp_k x_i are added on chip and d_dx [B, F, D] is written once.  dW = sum dpre_k p_k^T and dh = sum ds_k
+ *                relu(pre_k): one row of A D + A floats per wavefront in the workspace (rbx_afm_bwd_workspace_size), summed
+ *                in a fixed order by a second launch into d_dw [A, D] and d_dh [A].  d_dx, d_dw, d_dh: NULL skips it.
+ * Supported (rbx_afm_supported): 2 <= F <= 39; D a multiple of 4 in [4, 64]; 1 <= A <= 64; dtype (the RBX_* code of every float
+ * tensor) RBX_F32; x and d_dout 16-byte aligned with strides that are multiples of 4.  Anything else: RBX_ERR_UNSUPPORTED
+ * before any launch.  batch = 0 launches nothing.  No atomics, sums in a fixed order; no call allocates or reads back:
+ * capturable. */
+int rbx_afm_supported(int32_t n_fields, int32_t dim, int32_t att_dim);
+int rbx_afm_fwd(const float* d_x, int64_t x_stride_b, int64_t x_stride_f, const float* d_w, const float* d_h, int64_t batch,
+                int32_t n_fields, int32_t dim, int32_t att_dim, int32_t dtype, float* d_out, float* d_stat, float* d_attn,
+                void* stream);
+size_t rbx_afm_bwd_workspace_size(int64_t batch, int32_t n_fields, int32_t dim, int32_t att_dim);
+int rbx_afm_bwd(const float* d_dout, int64_t dout_stride_b, const float* d_x, int64_t x_stride_b, int64_t x_stride_f,
+                const float* d_w, const float* d_h, const float* d_out, const float* d_stat, int64_t batch, int32_t n_fields,
+                int32_t dim, int32_t att_dim, int32_t dtype, float* d_dx, float* d_dw, float* d_dh, void* d_workspace,
+                size_t workspace_bytes, void* stream);
+
 /* ---- FiBiNet: SENET gate and bilinear pair interaction (csrc/rbx_bilinear.hip; additions only, the version stays) -----------
  * Replaces, under third_party/rechub/basic/layers.py (SENETLayer, BiLinearInteractionLayer) and models/ranking/fibinet.py:31-38,
  * P = F (F - 1) / 2 nn.Linear calls on [B, 1, D] slices run twice per step, a torch.cat of 2 P pieces and a flatten.  B = batch,

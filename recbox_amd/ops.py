@@ -149,6 +149,11 @@ class config(object):
     # instead of the gather composition whose [B, n_neg + 1, D] copy of the item rows autograd keeps.  Off, or for what
     # inbatch_band_supported refuses: that composition (inbatch_band_scores_torch).  Measurements: profiles/inbatch/INDEX.md.
     inbatch_fused = os.environ.get("RECBOX_AMD_INBATCH_FUSED", "1") != "0"
+    # Attentional FM (RecBole's AFM): the pair products, the attention layer, the softmax over the P = F (F - 1) / 2 pairs and
+    # the weighted sum as one launch that keeps a sample's x [F, D] on chip (afm_pool: csrc/rbx_afm.hip) instead of the
+    # composition whose [B, P, D] and [B, P, A] tensors autograd keeps.  Off, or for what afm_pool_supported refuses: that
+    # composition (afm_pool_torch).  Measurements: profiles/afm/INDEX.md.
+    afm_fused = os.environ.get("RECBOX_AMD_AFM_FUSED", "1") != "0"
 
 
 def _require_cuda(t, what):
@@ -5482,3 +5487,103 @@ def inbatch_band_scores(u, v, n_neg, weight=None, temperature=1.0, eps=1e-8):
     if n_neg < 1 or not _inbatch_fused_ok(u, v, n_neg, weight):
         return inbatch_band_scores_torch(u, v, n_neg, weight, temperature, eps)
     return _InbatchBand.apply(u, v, weight, n_neg, 1.0 / float(temperature), float(eps))
+
+
+# ---- Attentional FM: pair-attention pooling (csrc/rbx_afm.hip) ----------------------------------------------------------------
+AFM_MAX_FIELDS, AFM_MAX_DIM, AFM_MAX_ATT = 39, 64, 64
+
+
+def afm_pool_supported(n_fields, dim, att_dim, dtype=torch.float32):
+    """Whether the fused op takes this shape (rbx_afm_supported): float32, 2 .. 39 fields, ``dim`` a multiple of 4 in 4 .. 64,
+    1 .. 64 attention units.  What it refuses runs ``afm_pool_torch``."""
+    if dtype != torch.float32:
+        return False
+    return bool(lib.rbx_afm_supported(int(n_fields), int(dim), int(att_dim)))
+
+
+def afm_pool_torch(x, w, h, want_attn=False):
+    """The composition, with the arithmetic of RecBole's ``AFM.afm_layer`` up to the pooled vector (afm.py:84-93) over
+    ``AttLayer`` (layers.py:253-261), in plain ATen on whatever device the tensors live on: the two sides of every field pair
+    gathered as [B, P, D], their product, ``softmax_P(sum_A relu(pair W^T) * h)`` and the weighted sum over the pairs.  ``x``
+    [B, F, D], ``w`` [A, D], ``h`` [A] -> ``(out [B, D], attn [B, P] or None)``; ``attn`` is returned detached.  Serves what
+    the fused op refuses and is what it is measured against."""
+    ii, jj = _pair_index(x.shape[1], x.device)
+    pair = torch.mul(x[:, ii], x[:, jj])                                       # [B, P, D]
+    sig = torch.relu(torch.nn.functional.linear(pair, w))                      # [B, P, A]
+    att = torch.softmax(torch.sum(torch.mul(sig, h.reshape(-1)), dim=2), dim=1)     # [B, P]
+    out = torch.sum(torch.mul(att.unsqueeze(2), pair), dim=1)
+    return out, (att.detach() if want_attn else None)
+
+
+def _afm_fused_ok(x, w, h):
+    """The refusals of ``afm_pool`` that run the composition: the switch, a shape outside the kernels' range, CPU or non-float32
+    tensors, an empty batch, an ``x`` whose rows are not contiguous, 16-byte aligned and a multiple of 4 floats apart.  Every
+    shape class profiles/afm/INDEX.md measured ran faster fused (or only fused), so no class inside the range is turned away."""
+    if not config.afm_fused or x.dim() != 3 or x.shape[0] == 0:
+        return False
+    if any((not t.is_cuda) or t.dtype != torch.float32 for t in (x, w, h)):
+        return False
+    if not afm_pool_supported(x.shape[1], x.shape[2], w.shape[0]):
+        return False
+    return _fields_in_place(x) and x.stride(0) > 0
+
+
+class _AfmPool(torch.autograd.Function):
+    """(out [B, D], attn [B, P] or None) as ONE launch (rbx_afm_fwd); backward = rbx_afm_bwd (one launch plus the tail that adds
+    the per-wavefront rows of dW / dh).  Saved: x, w, h, out and the [2, B] softmax statistics -- nothing pair-sized; ``attn``
+    carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, w, h, want_attn):
+        B, F, D = x.shape
+        A = w.shape[0]
+        dev = x.device
+        w = w.contiguous()
+        h_shape = h.shape
+        h = h.reshape(A).contiguous()
+        out = torch.empty((B, D), dtype=torch.float32, device=dev)
+        stat = torch.empty((2, B), dtype=torch.float32, device=dev)
+        attn = torch.empty((B, F * (F - 1) // 2), dtype=torch.float32, device=dev) if want_attn else None
+        check(_timed(("afm_fwd", B, F, D, A),
+                     lambda: lib.rbx_afm_fwd(_ptr(x), x.stride(0), x.stride(1), _ptr(w), _ptr(h), B, F, D, A, _lib.RBX_F32,
+                                             _ptr(out), _ptr(stat), _ptr(attn), _stream())))
+        ctx.save_for_backward(x, w, h, out, stat)
+        ctx.h_shape = h_shape
+        if attn is not None:
+            ctx.mark_non_differentiable(attn)
+        return out, attn
+
+    @staticmethod
+    def backward(ctx, dout, _dattn):
+        x, w, h, out, stat = ctx.saved_tensors
+        B, F, D = x.shape
+        A = w.shape[0]
+        dev = x.device
+        need = ctx.needs_input_grad
+        dout = dout.float()
+        if dout.stride(1) != 1 or dout.data_ptr() % 16 != 0 or dout.stride(0) % 4 != 0 or dout.stride(0) < D:
+            dout = dout.contiguous()
+        dx = torch.empty((B, F, D), dtype=torch.float32, device=dev) if need[0] else None
+        dw = torch.empty((A, D), dtype=torch.float32, device=dev) if need[1] else None
+        dh = torch.empty(A, dtype=torch.float32, device=dev) if need[2] else None
+        ws_bytes = lib.rbx_afm_bwd_workspace_size(B, F, D, A)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        check(_timed(("afm_bwd", B, F, D, A),
+                     lambda: lib.rbx_afm_bwd(_ptr(dout), dout.stride(0), _ptr(x), x.stride(0), x.stride(1), _ptr(w), _ptr(h),
+                                             _ptr(out), _ptr(stat), B, F, D, A, _lib.RBX_F32, _ptr(dx), _ptr(dw), _ptr(dh),
+                                             _ptr(ws), ws_bytes, _stream())))
+        return dx, dw, (dh.view(ctx.h_shape) if dh is not None else None), None
+
+
+def afm_pool(x, w, h, want_attn=False):
+    """AFM's attention pooling over the field pairs as one autograd node over rbx_afm_fwd / _bwd: ``x`` [B, F, D], ``w``
+    [A, D] (AttLayer's bias-free Linear), ``h`` [A] -> ``(out [B, D], attn [B, P] or None)`` with ``p_k = x_i * x_j`` over the
+    P = F (F - 1) / 2 pairs in row-major order, ``attn = softmax_k(sum_a h_a relu(W p_k)_a)``, ``out = sum_k attn_k p_k``.
+    ``attn`` carries no gradient.  Nothing of B P D or B P A elements is formed or saved.  CPU or non-float32 tensors, an
+    empty batch, what ``afm_pool_supported`` refuses (D = 6, 40 fields, 65 units), an oddly strided ``x`` and
+    ``config.afm_fused = False`` run ``afm_pool_torch``."""
+    if x.dim() != 3 or w.dim() != 2 or w.shape[1] != x.shape[2] or h.numel() != w.shape[0]:
+        raise RuntimeError("afm_pool: x %s, w %s, h %s do not fit" % (tuple(x.shape), tuple(w.shape), tuple(h.shape)))
+    if not _afm_fused_ok(x, w, h):
+        return afm_pool_torch(x, w, h, want_attn)
+    return _AfmPool.apply(x, w, h, bool(want_attn))

@@ -387,3 +387,33 @@ class EDCN(torch.nn.Module):
             bridge_i = self.bridge_modules[i](cross_i, deep_i)
         x_stack = torch.cat([cross_i, deep_i, bridge_i], dim=1)
         return torch.sigmoid(_lr(self.linear, x_stack).squeeze(1))
+
+
+# ---- Attentional FM (RecBole's AFM in the rechub style) -----------------------------------------------------------------------
+class AFM(torch.nn.Module):
+    """Attentional FM as a trainable model in the style of this zoo: ``EmbeddingLayer`` over ``features`` (unshared
+    ``SparseFeature``s of one ``embed_dim``), an ``LR`` over the flattened embeddings as the first-order term, and
+    ``recbole.context_aware.AFMInteraction`` (one ``ops.afm_pool`` launch each way) as the second-order term; the output is
+    ``sigmoid(first + second)`` [B].  ``interaction.state_dict()`` has RecBole's AFM keys (``attlayer.w.weight``, ``attlayer.h``,
+    ``p``).  RecBole's ``AFM(config, dataset)`` constructor, its ``ContextRecommender`` base (field-typed embedding tables and
+    ``first_order_linear``) and ``calculate_loss`` are NOT mirrored: add ``interaction.reg_loss(reg_weight)`` to the loss for
+    the reference's L2 term."""
+
+    def __init__(self, features, attention_size=25, dropout_prob=0.3):
+        super(AFM, self).__init__()
+        from ...recbole.context_aware import AFMInteraction
+        dims = set(fea.embed_dim for fea in features)
+        if len(dims) != 1 or len(features) < 2:
+            raise ValueError("AFM: at least two features of one embed_dim (got dims %s)" % sorted(dims))
+        self.features = features
+        self.embedding = EmbeddingLayer(features)
+        self.num_fields = len(features)
+        self.embed_dim = dims.pop()
+        self.linear = LR(self.num_fields * self.embed_dim)
+        self.interaction = AFMInteraction(self.num_fields, self.embed_dim, attention_size, dropout_prob)
+
+    def forward(self, x):
+        from .multi_task import _embed
+        embed_x = _embed(self.embedding, x, self.features, False)          # [B, F, D]
+        y = _lr(self.linear, embed_x.flatten(start_dim=1)) + self.interaction(embed_x)
+        return torch.sigmoid(y.squeeze(1))
