@@ -1211,6 +1211,40 @@ int rbx_gru_bwd(const float* d_saved, const float* d_w_hh, const float* d_dout, 
                 const float* d_dhn, const void* d_lengths, int32_t lengths_dtype, int64_t batch, int32_t seq_len,
                 int32_t hidden, int32_t dtype, float* d_dgi, float* d_dghn, float* d_dh0, void* stream);
 
+/* ---- attention-gated GRU recurrence: DIEN's AGRU / AUGRU (csrc/rbx_attgru.hip; additions only, the version stays) ----------
+ * Replaces DynamicRNN over AGRUCell / AUGRUCell of third_party/recbole/model/sequential_recommender/dien.py:389-521 (a Python
+ * loop over the steps of a PackedSequence, whose lengths dien.py:336 copies to the host).  B = batch, L = seq_len, H = hidden.
+ * The reference's gate convention: rows of d_w_hh [3H, H] (contiguous) and d_b_hh [3H] (NULL: none) are ordered r, u, n (its
+ * chunk(3, 1); torch's r, z, n); a = d_att[b L + t], d_att [B, L] contiguous, taken as written (no clamp);
+ *   gh = h W_hh^T + b_hh   r = s(gi_r + gh_r)   u = s(gi_u + gh_u)   n = tanh(gi_n + r gh_n)
+ *   cell 1 (AUGRU): c = a u     cell 0 (AGRU): c = a (u is not formed)     h' = (1 - c) h + c n.
+ * gi = x W_ih^T + b_ih comes from rbx_linear_fwd and is read at gi[b gi_stride_b + t gi_stride_t + c], c < 3H.
+ *   rbx_attgru_fwd   one launch for all L steps: a workgroup owns 16 samples, gh runs on v_mfma_f32_16x16x4_f32 against W_hh
+ *                    held in registers, h stays on chip.  d_h0 [B, H] (NULL: zeros).  d_lengths [B] (RBX_I32 / RBX_I64; NULL: all
+ *                    L), clamped to [0, L]: for t >= lengths[b] the state is frozen and d_out[b, t, :] = 0; d_hn[b] is the state
+ *                    after step lengths[b] - 1 (length 0: h0).  Writes d_out [B, L, H], d_hn [B, H] and, for the backward,
+ *                    d_saved [B, L, 5, H] = r, u, n, gh_n, h_prev of every position (h_prev is also the x operand of dW_hh;
+ *                    cell 0 leaves the u slot unwritten).
+ *   rbx_attgru_bwd   one launch, t = L-1 .. 0 with dh on chip.  d_dout (NULL: none) is read at
+ *                    dout[b dout_stride_b + t dout_stride_t + j]; d_dhn [B, H] (NULL: none).  Writes d_dgi [B, L, 3H] (the
+ *                    gradient of gi; cell 0: zeros in the u columns), d_dghn [B, L, H] = d_gi_n r (the n-gate columns in which
+ *                    the gradient of gh differs from d_dgi), d_datt [B, L] (the gradient of the score: a sum over the hidden
+ *                    units, in a fixed order) and d_dh0 [B, H]; positions at and beyond a sample's length get zeros.
+ * dW_ih, dx, dW_hh and the bias gradients are rbx_linear_bwd calls over these matrices.
+ * Supported (rbx_attgru_supported): H a multiple of 4 in [4, 128], L >= 1, cell 0 or 1; dtype (the RBX_* code of every float
+ * tensor) must be RBX_F32; gi and d_dout 16-byte aligned with strides that are multiples of 4.  Anything else:
+ * RBX_ERR_UNSUPPORTED before any launch.  batch = 0 launches nothing.  No atomics, sums in a fixed order; no call allocates or
+ * reads back: capturable. */
+int rbx_attgru_supported(int32_t hidden, int32_t seq_len, int32_t cell);
+int rbx_attgru_fwd(const float* d_gi, int64_t gi_stride_b, int64_t gi_stride_t, const float* d_att, const float* d_w_hh,
+                   const float* d_b_hh, const float* d_h0, const void* d_lengths, int32_t lengths_dtype, int64_t batch,
+                   int32_t seq_len, int32_t hidden, int32_t cell, int32_t dtype, float* d_out, float* d_saved, float* d_hn,
+                   void* stream);
+int rbx_attgru_bwd(const float* d_saved, const float* d_att, const float* d_w_hh, const float* d_dout, int64_t dout_stride_b,
+                   int64_t dout_stride_t, const float* d_dhn, const void* d_lengths, int32_t lengths_dtype, int64_t batch,
+                   int32_t seq_len, int32_t hidden, int32_t cell, int32_t dtype, float* d_dgi, float* d_dghn, float* d_datt,
+                   float* d_dh0, void* stream);
+
 /* ---- expert-gate mixing: MMOE, CGC / PLE, AITM (csrc/rbx_mix.hip; additions only, the version stays) -----------------------
  * Replaces, under third_party/rechub/models/multi_task/mmoe.py:46-57, ple.py:102-128 and aitm.py:77-84, the torch.cat of the
  * expert outputs into [B, E, H], one torch.mul per gate into another [B, E, H], and a torch.sum.  B = batch, H = hidden,

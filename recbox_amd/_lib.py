@@ -284,6 +284,10 @@ SIGNATURES = {
     "rbx_gru_supported": (ctypes.c_int, [_i32, _i32]),
     "rbx_gru_fwd": (ctypes.c_int, [_P, _i64, _i64, _P, _P, _P, _P, _i32, _i64, _i32, _i32, _i32, _P, _P, _P, _P]),
     "rbx_gru_bwd": (ctypes.c_int, [_P, _P, _P, _i64, _i64, _P, _P, _i32, _i64, _i32, _i32, _i32, _P, _P, _P, _P]),
+    "rbx_attgru_supported": (ctypes.c_int, [_i32, _i32, _i32]),
+    "rbx_attgru_fwd": (ctypes.c_int, [_P, _i64, _i64, _P, _P, _P, _P, _P, _i32, _i64, _i32, _i32, _i32, _i32, _P, _P, _P, _P]),
+    "rbx_attgru_bwd": (ctypes.c_int, [_P, _P, _P, _P, _i64, _i64, _P, _P, _i32, _i64, _i32, _i32, _i32, _i32, _P, _P, _P, _P,
+                                      _P]),
     "rbx_expert_mix_supported": (ctypes.c_int, [_i32, _i32, _i32, _IP, _IP, _i32]),
     "rbx_expert_mix_fwd": (ctypes.c_int, [_PP, _LP, _PP, _IP, _IP, _i64, _i32, _i32, _i32, _i32, _i32, _P, _P, _P]),
     "rbx_expert_mix_bwd": (ctypes.c_int, [_PP, _LP, _PP, _P, _PP, _IP, _IP, _i64, _i32, _i32, _i32, _i32, _i32, _PP, _PP, _P]),

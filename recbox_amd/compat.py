@@ -120,7 +120,8 @@ _RECHUB = {
 
 # Names a path gained after its entry was published.  ``alias_table()`` keeps an entry as it was first listed (callers compare
 # entries); ``install()`` binds these as well.
-_RECHUB_ALSO = {"models.matching.comirec": ["ComirecSA"], "models.ranking": ["FiBiNet", "DCN", "DCNv2", "EDCN", "WideDeep", "AFM"],
+_RECHUB_ALSO = {"models.matching.comirec": ["ComirecSA"], "models.ranking": ["FiBiNet", "DCN", "DCNv2", "EDCN", "WideDeep", "AFM",
+                                                                                  "DIEN"],
                 "models.matching": ["YoutubeSBC", "FaceBookDSSM"]}
 
 

@@ -1,4 +1,7 @@
-"""Mirrors of the RecBole pieces the project serves (third_party/recbole): ``layers.AttLayer`` and, in ``context_aware``, the
-interaction part of AFM over ``ops.afm_pool``.  RecBole's ``(config, dataset)`` constructors, its ``ContextRecommender`` base
-class, trainer and ``calculate_loss`` are not mirrored, and ``compat.install()`` registers nothing under ``recbole.*``."""
-from . import context_aware, layers  # noqa: F401
+"""Mirrors of the RecBole pieces the project serves (third_party/recbole): ``layers`` (``AttLayer``, ``MLPLayers``,
+``activation_layer``, ``Dice``, ``SequenceAttLayer``), in ``context_aware`` the interaction part of AFM over ``ops.afm_pool``,
+and in ``sequential`` the layers of DIEN (``AGRUCell``, ``AUGRUCell``, ``DynamicRNN``, ``InterestExtractorNetwork``,
+``InterestEvolvingLayer``) over ``ops.att_gru`` / ``ops.gru``.  RecBole's ``(config, dataset)`` constructors, its recommender
+base classes, ``ContextSeqEmbLayer``, trainer and ``calculate_loss`` are not mirrored, and ``compat.install()`` registers
+nothing under ``recbole.*``: the trainable models (``AFM``, ``DIEN``) are registered with the rechub ranking zoo."""
+from . import context_aware, layers, sequential  # noqa: F401

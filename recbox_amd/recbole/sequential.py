@@ -1,0 +1,189 @@
+"""The layers of RecBole's DIEN (third_party/recbole/model/sequential_recommender/dien.py:193-521): ``AGRUCell``, ``AUGRUCell``,
+``DynamicRNN``, ``InterestExtractorNetwork`` and ``InterestEvolvingLayer``, with the reference's constructors, attribute names
+and ``state_dict`` keys.  For GPU tensors the attention-gated recurrence is ``ops.att_gru`` (one launch each way,
+csrc/rbx_attgru.hip), the plain GRUs are ``ops.gru`` with the lengths read on the device, and nothing is packed or copied to
+the host; for CPU tensors the same arithmetic runs in plain ATen.  RecBole's ``DIEN(config, dataset)`` model,
+``ContextSeqEmbLayer`` and ``calculate_loss`` are not mirrored (``rechub.models.ranking.DIEN`` is the trainable model)."""
+import torch
+import torch.nn.functional as F
+from torch import nn
+from torch.nn.utils.rnn import PackedSequence, pack_padded_sequence, pad_packed_sequence
+
+from .. import ops
+from .layers import MLPLayers, SequenceAttLayer
+
+
+def _masked_walk(step, x, h, lengths):
+    """``h = step(t, h)`` over the positions of ``x`` [B, L, .] with packed-sequence semantics -> (out [B, L, H], h_n)."""
+    outs = []
+    for t in range(x.shape[1]):
+        new = step(t, h)
+        if lengths is not None:
+            act = (lengths > t).unsqueeze(1)
+            h = torch.where(act, new, h)
+            outs.append(torch.where(act, new, torch.zeros_like(new)))
+        else:
+            h = new
+            outs.append(new)
+    return torch.stack(outs, dim=1), h
+
+
+def _gru_padded(gru, x, lengths):
+    """One-layer batch-first ``nn.GRU`` as parameter holder over padded ``x`` [B, L, I] -> (out [B, L, H], h_n [B, H])."""
+    w_ih, w_hh = gru.weight_ih_l0, gru.weight_hh_l0
+    b_ih, b_hh = (gru.bias_ih_l0, gru.bias_hh_l0) if gru.bias else (None, None)
+    if x.is_cuda:
+        return ops.gru(x, w_ih, w_hh, b_ih, b_hh, None, lengths)
+    H = gru.hidden_size
+    gi = F.linear(x, w_ih, b_ih)
+
+    def step(t, h):
+        gh = F.linear(h, w_hh, b_hh)
+        r = torch.sigmoid(gi[:, t, :H] + gh[:, :H])
+        z = torch.sigmoid(gi[:, t, H:2 * H] + gh[:, H:2 * H])
+        n = torch.tanh(gi[:, t, 2 * H:] + r * gh[:, 2 * H:])
+        return (1 - z) * n + z * h
+    return _masked_walk(step, x, x.new_zeros(x.shape[0], H), lengths)
+
+
+class _AttCell(nn.Module):
+    """What AGRUCell and AUGRUCell share: the parameters (rows ordered r, u, n; ``torch.randn`` weights, zero biases) and
+    one step in ATen."""
+    cell = None
+
+    def __init__(self, input_size, hidden_size, bias=True):
+        super(_AttCell, self).__init__()
+        self.input_size = input_size
+        self.hidden_size = hidden_size
+        self.bias = bias
+        self.weight_ih = nn.Parameter(torch.randn(3 * hidden_size, input_size))
+        self.weight_hh = nn.Parameter(torch.randn(3 * hidden_size, hidden_size))
+        if self.bias:
+            self.bias_ih = nn.Parameter(torch.zeros(3 * hidden_size))
+            self.bias_hh = nn.Parameter(torch.zeros(3 * hidden_size))
+        else:
+            self.register_parameter("bias_ih", None)
+            self.register_parameter("bias_hh", None)
+
+    def forward(self, input, hidden_output, att_score):
+        gi = F.linear(input, self.weight_ih, self.bias_ih)
+        gh = F.linear(hidden_output, self.weight_hh, self.bias_hh)
+        i_r, i_u, i_h = gi.chunk(3, 1)
+        h_r, h_u, h_h = gh.chunk(3, 1)
+        reset_gate = torch.sigmoid(i_r + h_r)
+        new_state = torch.tanh(i_h + reset_gate * h_h)
+        att_score = att_score.view(-1, 1)
+        if self.cell == "AUGRU":
+            att_score = att_score * torch.sigmoid(i_u + h_u)
+        return (1 - att_score) * hidden_output + att_score * new_state
+
+
+class AGRUCell(_AttCell):
+    """Attention based GRU: the score replaces the update gate, ``h' = (1 - a) h + a n`` (the u rows are unused)."""
+    cell = "AGRU"
+
+
+class AUGRUCell(_AttCell):
+    """GRU with attentional update gate: ``c = a u``, ``h' = (1 - c) h + c n``."""
+    cell = "AUGRU"
+
+
+class DynamicRNN(nn.Module):
+    """The attention-gated recurrence over a cell's parameters (``rnn.weight_ih`` ...).  ``forward`` takes the packed pair
+    exactly as the reference does -- it unpacks, runs ``forward_padded`` and repacks, which reads the lengths on the host: for
+    drop-in use, not capturable.  ``forward_padded(keys, att, lengths)`` is the padded form the layers below call."""
+
+    def __init__(self, input_size, hidden_size, bias=True, gru="AGRU"):
+        super(DynamicRNN, self).__init__()
+        self.input_size = input_size
+        self.hidden_size = hidden_size
+        if gru == "AGRU":
+            self.rnn = AGRUCell(input_size, hidden_size, bias)
+        elif gru == "AUGRU":
+            self.rnn = AUGRUCell(input_size, hidden_size, bias)
+
+    def forward_padded(self, keys, att_scores, keys_length=None, hidden_output=None):
+        """``keys`` [B, L, I], ``att_scores`` [B, L], ``keys_length`` [B] or None -> (out [B, L, H], h_n [B, H])."""
+        cell = self.rnn
+        if keys.is_cuda:
+            return ops.att_gru(keys, att_scores, cell.weight_ih, cell.weight_hh, cell.bias_ih, cell.bias_hh, hidden_output,
+                               keys_length, cell=cell.cell)
+        h = hidden_output if hidden_output is not None else keys.new_zeros(keys.shape[0], self.hidden_size)
+        att_scores = att_scores.reshape(keys.shape[0], keys.shape[1])
+        return _masked_walk(lambda t, h: cell(keys[:, t], h, att_scores[:, t]), keys, h, keys_length)
+
+    def forward(self, input, att_scores=None, hidden_output=None):
+        if not isinstance(input, PackedSequence) or not isinstance(att_scores, PackedSequence):
+            raise NotImplementedError("DynamicRNN only supports packed input and att_scores")
+        keys, lengths = pad_packed_sequence(input, batch_first=True)
+        att, _ = pad_packed_sequence(att_scores, batch_first=True)
+        if hidden_output is not None and input.unsorted_indices is not None:
+            hidden_output = hidden_output[input.unsorted_indices]          # the reference's rows follow the packed order
+        out, _ = self.forward_padded(keys, att, lengths.to(keys.device), hidden_output)
+        return pack_padded_sequence(out, lengths, batch_first=True, enforce_sorted=input.sorted_indices is None)
+
+
+class InterestExtractorNetwork(nn.Module):
+    """The interest extractor: a GRU over the behaviour sequence (``gru``: an ``nn.GRU`` as parameter holder, the compute on
+    ``ops.gru`` with the lengths on the device) and the auxiliary loss of the next behaviour against a negative one."""
+
+    def __init__(self, input_size, hidden_size, mlp_size):
+        super(InterestExtractorNetwork, self).__init__()
+        self.gru = nn.GRU(input_size=input_size, hidden_size=hidden_size, batch_first=True)
+        self.auxiliary_net = MLPLayers(layers=mlp_size, activation="none")
+
+    def forward(self, keys, keys_length, neg_keys=None):
+        rnn_outputs, _ = _gru_padded(self.gru, keys, keys_length)
+        aux_loss = self.auxiliary_loss(rnn_outputs[:, :-1, :], keys[:, 1:, :], neg_keys[:, 1:, :], keys_length - 1)
+        return rnn_outputs, aux_loss
+
+    def auxiliary_loss(self, h_states, click_seq, noclick_seq, keys_length):
+        """The reference's ``binary_cross_entropy_with_logits`` over the rows ``t < keys_length``, written mask-weighted:
+        ``(sum m softplus(-click) + sum m softplus(noclick)) / (2 sum m)`` -- no data-dependent shape, no host copy."""
+        batch_size, hist_length, _ = h_states.shape
+        mask = (torch.arange(hist_length, device=h_states.device).view(1, -1) < keys_length.view(-1, 1)).to(h_states.dtype)
+        click_prop = self.auxiliary_net(torch.cat([h_states, click_seq], dim=-1)).view(batch_size, hist_length)
+        noclick_prop = self.auxiliary_net(torch.cat([h_states, noclick_seq], dim=-1)).view(batch_size, hist_length)
+        total = (mask * F.softplus(-click_prop)).sum() + (mask * F.softplus(noclick_prop)).sum()
+        return total / (2 * mask.sum())
+
+
+class InterestEvolvingLayer(nn.Module):
+    """The interest-evolving layer for all four ``gru`` values: 'GRU' (a GRU, then attention pooling of its outputs), 'AIGRU'
+    (the scores scale the GRU's inputs), 'AGRU' and 'AUGRU' (the attention-gated recurrence, ``ops.att_gru``).
+    ``queries`` [B, E], ``keys`` [B, T, E], ``keys_length`` [B] -> [B, H]; the final state is the op's ``h_n`` (the reference
+    gathers the output at position ``keys_length - 1``, the same rows)."""
+
+    def __init__(self, mask_mat, input_size, rnn_hidden_size, att_hidden_size=(80, 40), activation="sigmoid",
+                 softmax_stag=True, gru="GRU"):
+        super(InterestEvolvingLayer, self).__init__()
+        self.mask_mat = mask_mat
+        self.gru = gru
+        if gru == "GRU":
+            self.attention_layer = SequenceAttLayer(mask_mat, att_hidden_size, activation, softmax_stag, False)
+            self.dynamic_rnn = nn.GRU(input_size=input_size, hidden_size=rnn_hidden_size, batch_first=True)
+        elif gru == "AIGRU":
+            self.attention_layer = SequenceAttLayer(mask_mat, att_hidden_size, activation, softmax_stag, True)
+            self.dynamic_rnn = nn.GRU(input_size=input_size, hidden_size=rnn_hidden_size, batch_first=True)
+        elif gru == "AGRU" or gru == "AUGRU":
+            self.attention_layer = SequenceAttLayer(mask_mat, att_hidden_size, activation, softmax_stag, True)
+            self.dynamic_rnn = DynamicRNN(input_size=input_size, hidden_size=rnn_hidden_size, gru=gru)
+
+    def final_output(self, outputs, keys_length):
+        """The row of ``outputs`` [B, T, H] at position ``keys_length - 1`` (kept for callers; ``forward`` uses ``h_n``)."""
+        batch_size, hist_len, _ = outputs.shape
+        mask = torch.arange(hist_len, device=keys_length.device).repeat(batch_size, 1) == (keys_length.view(-1, 1) - 1)
+        return outputs[mask]
+
+    def forward(self, queries, keys, keys_length):
+        if self.gru == "GRU":
+            rnn_outputs, _ = _gru_padded(self.dynamic_rnn, keys, keys_length)
+            outputs = self.attention_layer(queries, rnn_outputs, keys_length).squeeze(1)
+        elif self.gru == "AIGRU":
+            att_outputs = self.attention_layer(queries, keys, keys_length)
+            interest = keys * att_outputs.transpose(1, 2)
+            _, outputs = _gru_padded(self.dynamic_rnn, interest, keys_length)
+        elif self.gru == "AGRU" or self.gru == "AUGRU":
+            att_outputs = self.attention_layer(queries, keys, keys_length).squeeze(1)          # [B, T]
+            _, outputs = self.dynamic_rnn.forward_padded(keys, att_outputs, keys_length)
+        return outputs

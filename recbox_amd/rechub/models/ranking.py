@@ -417,3 +417,65 @@ class AFM(torch.nn.Module):
         embed_x = _embed(self.embedding, x, self.features, False)          # [B, F, D]
         y = _lr(self.linear, embed_x.flatten(start_dim=1)) + self.interaction(embed_x)
         return torch.sigmoid(y.squeeze(1))
+
+
+# ---- Deep Interest Evolution Network (RecBole's DIEN in the rechub style) -------------------------------------------------------
+class DIEN(torch.nn.Module):
+    """DIEN as a trainable model in the style of this zoo, beside ``DIN``: ``EmbeddingLayer`` over ``features`` (profile),
+    ``history_features`` and ``neg_history_features`` (``SequenceFeature``s with ``pooling="concat"``, usually
+    ``shared_with`` the target's table; the negatives are the sampled non-clicked behaviours of the auxiliary loss) and
+    ``target_features``.  The history embeddings are concatenated over the history features into [B, L, E] and the targets
+    into [B, E] (so the widths must agree); the lengths are counted on the device from the first history feature's non-zero
+    ids (left-aligned histories, at least one behaviour per sample).  ``recbole.sequential.InterestExtractorNetwork`` (``ops.gru``)
+    and ``InterestEvolvingLayer`` (``gru_type`` in 'GRU', 'AIGRU', 'AGRU', 'AUGRU'; the last two on ``ops.att_gru``) give the
+    evolved interest; [evolution | targets | profile features] feed a Dice MLP as in ``DIN``.  ``attention_mlp_params``:
+    ``dims`` (the hidden sizes of the score MLP, default [80, 40]) and ``activation`` (default "sigmoid"); the auxiliary net
+    has ``mlp_params["dims"]`` hidden sizes.  ``forward(x)`` returns ``(sigmoid prediction [B], aux_loss)``; the training loss
+    is ``bce + model.alpha * aux_loss``.  RecBole's ``DIEN(config, dataset)`` constructor, ``ContextSeqEmbLayer`` and
+    ``calculate_loss`` are NOT mirrored."""
+
+    def __init__(self, features, history_features, neg_history_features, target_features, mlp_params, attention_mlp_params,
+                 gru_type="AUGRU", alpha=1.0):
+        super(DIEN, self).__init__()
+        from ...recbole.sequential import InterestEvolvingLayer, InterestExtractorNetwork
+        if gru_type not in ("GRU", "AIGRU", "AGRU", "AUGRU"):
+            raise ValueError("DIEN: gru_type must be GRU, AIGRU, AGRU or AUGRU (got %r)" % (gru_type,))
+        self.features = features
+        self.history_features = history_features
+        self.neg_history_features = neg_history_features
+        self.target_features = target_features
+        self.gru_type = gru_type
+        self.alpha = alpha
+        self.item_dim = sum(f.embed_dim for f in history_features)
+        if (not history_features or len(neg_history_features) != len(history_features)
+                or sum(f.embed_dim for f in target_features) != self.item_dim
+                or sum(f.embed_dim for f in neg_history_features) != self.item_dim):
+            raise ValueError("DIEN: history, negative history and target features must have the same total width")
+        self.embedding = EmbeddingLayer(features + history_features + neg_history_features + target_features)
+        att = dict(attention_mlp_params or {})
+        att_dims = [4 * self.item_dim] + list(att.get("dims", [80, 40]))
+        self.interest_extractor = InterestExtractorNetwork(self.item_dim, self.item_dim,
+                                                           [2 * self.item_dim] + list(mlp_params["dims"]) + [1])
+        self.interest_evolution = InterestEvolvingLayer(None, self.item_dim, self.item_dim, att_dims,
+                                                        activation=att.get("activation", "sigmoid"), gru=gru_type)
+        self.all_dims = 2 * self.item_dim + sum(f.embed_dim for f in features)
+        self.mlp = MLP(self.all_dims, activation="dice", **mlp_params)
+
+    def _sequence(self, x, features):
+        from .multi_task import _embed
+        rows = _embed(self.embedding, x, features, False)                   # [B, n, L, E_f]
+        B, n, L, E = rows.shape
+        return rows.permute(0, 2, 1, 3).reshape(B, L, n * E)
+
+    def forward(self, x):
+        from .multi_task import _embed, _mlp
+        history = self._sequence(x, self.history_features)                  # [B, L, E]
+        negatives = self._sequence(x, self.neg_history_features)
+        target = _embed(self.embedding, x, self.target_features, False).flatten(start_dim=1)         # [B, E]
+        lengths = (x[self.history_features[0].name] != 0).sum(dim=1)
+        interest, aux_loss = self.interest_extractor(history, lengths, negatives)
+        evolution = self.interest_evolution(target, interest, lengths)
+        parts = [evolution, target]
+        if self.features:
+            parts.append(_embed(self.embedding, x, self.features, False).flatten(start_dim=1))
+        return torch.sigmoid(_mlp(self.mlp, torch.cat(parts, dim=1)).squeeze(1)), aux_loss
