@@ -1211,7 +1211,7 @@ int rbx_gru_bwd(const float* d_saved, const float* d_w_hh, const float* d_dout, 
                 const float* d_dhn, const void* d_lengths, int32_t lengths_dtype, int64_t batch, int32_t seq_len,
                 int32_t hidden, int32_t dtype, float* d_dgi, float* d_dghn, float* d_dh0, void* stream);
 
-/* ---- attention-gated GRU recurrence: DIEN's AGRU / AUGRU (csrc/rbx_attgru.hip; additions only, the version stays) ----------
+/* ---- attention-gated GRU recurrence: DIEN's AGRU / AUGRU (csrc/rbx_gru.hip; additions only, the version stays) ----------
  * Replaces DynamicRNN over AGRUCell / AUGRUCell of third_party/recbole/model/sequential_recommender/dien.py:389-521 (a Python
  * loop over the steps of a PackedSequence, whose lengths dien.py:336 copies to the host).  B = batch, L = seq_len, H = hidden.
  * The reference's gate convention: rows of d_w_hh [3H, H] (contiguous) and d_b_hh [3H] (NULL: none) are ordered r, u, n (its

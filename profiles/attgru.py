@@ -1,4 +1,4 @@
-"""Forward + backward of ops.att_gru (csrc/rbx_attgru.hip) against the step-loop composition ops.att_gru_torch, same process,
+"""Forward + backward of ops.att_gru (csrc/rbx_gru.hip) against the step-loop composition ops.att_gru_torch, same process,
 same inputs, alternating:
 
     python profiles/attgru.py [--out profiles/attgru/table.md] [--quick]

@@ -20,6 +20,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 HERE = os.path.join(ROOT, "profiles", "gru")
+CELLS = ("AGRU", "AUGRU", "GRU")                 # csrc/rbx_gru.hip's GruCell
 
 
 def resources():
@@ -35,12 +36,13 @@ def resources():
         if not m:
             continue
         if m.group(1) == "Function Name":
-            k = re.search(r"gru_(fwd|bwd)_kernelILi(\d+)E", m.group(2))
-            cur = {"name": "gru_%s_kernel<%s>" % (k.group(1), k.group(2)) if k else m.group(2)}
+            k = re.search(r"gru_(fwd|bwd)_kernelILi(\d+)ELi(\d+)E", m.group(2))
+            cur = {"name": "gru_%s_kernel<%s, %s>" % (k.group(1), k.group(2), CELLS[int(k.group(3))]) if k else m.group(2)}
             rows.append(cur)
         elif cur is not None:
             cur[m.group(1)] = m.group(2)
-    lines = ["| kernel (k-steps laid out: H <= 4 x) | VGPRs | AGPRs | SGPRs | scratch B/lane | VGPR spills | LDS B/block | waves/SIMD |",
+    rows.sort(key=lambda r: r["name"].split(",")[-1])          # cell by cell; within one, the compiler's order
+    lines = ["| kernel (k-steps laid out: H <= 4 x; cell) | VGPRs | AGPRs | SGPRs | scratch B/lane | VGPR spills | LDS B/block | waves/SIMD |",
              "|---|---|---|---|---|---|---|---|"]
     for r in rows:
         lines.append("| %s | %s | %s | %s | %s | %s | %s | %s |" % (r["name"], r.get("VGPRs"), r.get("AGPRs"), r.get("TotalSGPRs"),

@@ -125,7 +125,7 @@ class config(object):
     gru_fused = os.environ.get("RECBOX_AMD_GRU_FUSED", "1") != "0"
     # DIEN's interest-evolving layer (RecBole's DynamicRNN over AGRUCell / AUGRUCell): the attention-gated recurrence as one
     # launch forward and one backward with the GRU kernels' tiling, the per-position score read on the device and its gradient
-    # summed on chip (att_gru: csrc/rbx_attgru.hip) instead of a Python loop over t.  Off, or for what att_gru_supported
+    # summed on chip (att_gru: csrc/rbx_gru.hip) instead of a Python loop over t.  Off, or for what att_gru_supported
     # refuses: that loop (att_gru_torch).  Forward + backward against the loop (profiles/attgru/INDEX.md): 45 - 48 x / 22 - 26 x /
     # 18 - 19 x at B = 4096, 10 - 15 x at B = 65 536 (H = 16 / 64 / 128, L = 50), 33 - 35 x at B = 512, L = 20, H = 32: no shape
     # class loses, so there is no width threshold.
@@ -4596,15 +4596,30 @@ def capsule_bilinear_route(x, w, mask, interest_num, routing_times=3):
     return _CapsuleBilinearRoute.apply(x, w, mask, K, routing_times)
 
 
-# ---- GRU recurrence: GRU4Rec / NARM (csrc/rbx_gru.hip) ---------------------------------------------------------------------
-GRU_MAX_HIDDEN = 128
-_GRU_SAVED = 5                 # r, z, n, gh_n, h_prev per position (rbx_gru_fwd's d_saved)
+# ---- GRU recurrences: GRU4Rec / NARM, DIEN's attention-gated AGRU / AUGRU (csrc/rbx_gru.hip) ---------------------------------
+# One kernel body, one autograd node and one step loop serve the three cells; a cell is None (the plain GRU, entry points
+# rbx_gru_*, switch config.gru_fused) or the C ABI's code of an attention cell (rbx_attgru_*, config.attgru_fused).
+GRU_MAX_HIDDEN = ATTGRU_MAX_HIDDEN = 128
+_GRU_SAVED = 5                 # r, z, n, gh_n, h_prev per position (the kernels' d_saved; AGRU leaves z, its "u", unwritten)
+_ATTGRU_CELLS = {"AGRU": 0, "AUGRU": 1}
+
+
+def _attgru_cell(cell):
+    if cell not in _ATTGRU_CELLS:
+        raise ValueError("att_gru: cell must be 'AGRU' or 'AUGRU' (got %r)" % (cell,))
+    return _ATTGRU_CELLS[cell]
 
 
 def gru_supported(hidden, seq_len):
     """Whether the fused recurrence takes this shape (rbx_gru_supported): ``hidden`` a multiple of 4 in 4 .. 128, ``seq_len``
     >= 1.  What it refuses runs ``gru_torch``."""
     return bool(lib.rbx_gru_supported(int(hidden), int(seq_len)))
+
+
+def att_gru_supported(hidden, seq_len, cell="AUGRU"):
+    """Whether the fused recurrence takes this shape (rbx_attgru_supported): ``hidden`` a multiple of 4 in 4 .. 128,
+    ``seq_len`` >= 1, ``cell`` 'AGRU' or 'AUGRU'.  What it refuses runs ``att_gru_torch``."""
+    return bool(lib.rbx_attgru_supported(int(hidden), int(seq_len), _attgru_cell(cell)))
 
 
 def _gru_lengths(lengths, B, device):
@@ -4616,11 +4631,35 @@ def _gru_lengths(lengths, B, device):
     return lengths.reshape(B).contiguous()
 
 
-def gru_torch(x, w_ih, w_hh, b_ih=None, b_hh=None, h0=None, lengths=None):
-    """The step-loop composition: ``ops.linear`` for the input projection of all positions and for ``h W_hh^T`` of every step,
-    ATen for the gates.  Serves what ``gru_supported`` refuses and is what the fused op is measured against.  Same semantics
-    as ``gru`` (``lengths`` read on the device: no packing, no host copy)."""
-    _require_cuda(x, "gru input")
+def _attgru_scores(att, B, L):
+    if att.numel() != B * L:
+        raise RuntimeError("att_gru: att %s does not fit x [%d, %d, .]" % (tuple(att.shape), B, L))
+    return att.reshape(B, L)
+
+
+def _gru_args(name, x, w_ih, w_hh, h0, att=None):
+    """The argument checks of ``gru`` / ``att_gru`` (``name``) -> ``(h0 as [B, H] or None, att as [B, L] or None)``."""
+    _require_cuda(x, name + " input")
+    if att is not None:
+        _require_cuda(att, name + " att")
+    _require_cuda(w_ih, name + " weight_ih")
+    _require_cuda(w_hh, name + " weight_hh")
+    if x.dim() != 3 or w_ih.shape[0] != w_hh.shape[0] or w_hh.shape[0] != 3 * w_hh.shape[1] or w_ih.shape[1] != x.shape[2]:
+        raise RuntimeError("%s: x %s, weight_ih %s, weight_hh %s do not fit" % (name, tuple(x.shape), tuple(w_ih.shape),
+                                                                               tuple(w_hh.shape)))
+    B, L = x.shape[0], x.shape[1]
+    if att is not None:
+        att = _attgru_scores(att, B, L)
+    if h0 is not None:
+        _require_cuda(h0, name + " h0")
+        h0 = h0.reshape(B, w_hh.shape[1])
+    return h0, att
+
+
+def _gru_steps(x, w_ih, w_hh, b_ih, b_hh, h0, lengths, blend):
+    """The step loop of ``gru_torch`` / ``att_gru_torch``: ``ops.linear`` for the input projection of all positions and for
+    ``h W_hh^T`` of every step, ATen for the gates.  ``blend(t, h, z, n)`` gives ``h'`` of step ``t``; ``z()`` and ``n()``
+    form the gate when called, so each cell launches what it uses, in its own order."""
     B, L, _ = x.shape
     H = w_hh.shape[1]
     x, w_ih, w_hh = x.float(), w_ih.float(), w_hh.float()
@@ -4632,9 +4671,8 @@ def gru_torch(x, w_ih, w_hh, b_ih=None, b_hh=None, h0=None, lengths=None):
         gh = linear(h, w_hh, b_hh)
         g = gi[:, t]
         r = torch.sigmoid(g[:, :H] + gh[:, :H])
-        z = torch.sigmoid(g[:, H:2 * H] + gh[:, H:2 * H])
-        n = torch.tanh(g[:, 2 * H:] + r * gh[:, 2 * H:])
-        hnew = (1 - z) * n + z * h
+        hnew = blend(t, h, lambda: torch.sigmoid(g[:, H:2 * H] + gh[:, H:2 * H]),
+                     lambda: torch.tanh(g[:, 2 * H:] + r * gh[:, 2 * H:]))
         if lengths is not None:
             act = (lengths > t).unsqueeze(1)
             h = torch.where(act, hnew, h)
@@ -4645,133 +4683,16 @@ def gru_torch(x, w_ih, w_hh, b_ih=None, b_hh=None, h0=None, lengths=None):
     return torch.stack(outs, dim=1), h
 
 
-def _gru_fused_ok(x, w_ih, w_hh, b_ih, b_hh, h0):
-    """The refusals of ``gru`` that run the composition: a hidden width outside the kernels' range, non-float32 tensors, an
-    input that is a strided view or whose base is not 16-byte aligned."""
-    if not config.gru_fused or x.dim() != 3 or not gru_supported(w_hh.shape[1], x.shape[1]):
-        return False
-    if any(t is not None and t.dtype != torch.float32 for t in (x, w_ih, w_hh, b_ih, b_hh, h0)):
-        return False
-    return x.is_contiguous() and x.data_ptr() % 16 == 0
-
-
-class _Gru(torch.autograd.Function):
-    """(out [B, L, H], h_n [B, H]) of one GRU layer: the input projection on the dense path, the recurrence as ONE launch
-    (rbx_gru_fwd); backward = ONE launch (rbx_gru_bwd) for d_gi / d_gh_n / d_h0, then the dense path's GEMMs for dx, dW_ih,
-    dW_hh and the bias gradients."""
-
-    @staticmethod
-    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, h0, lengths):
-        B, L, I = x.shape
-        H = w_hh.shape[1]
-        dev = x.device
-        x2 = x.reshape(B * L, I)
-        w_ih, w_hh = w_ih.contiguous(), w_hh.contiguous()
-        gi = _lin_fwd(x2, w_ih, b_ih.contiguous() if b_ih is not None else None)          # [B L, 3H]
-        out = torch.empty((B, L, H), dtype=torch.float32, device=dev)
-        hn = torch.empty((B, H), dtype=torch.float32, device=dev)
-        saved = torch.empty((B, L, _GRU_SAVED * H), dtype=torch.float32, device=dev)
-        b_hh = b_hh.contiguous() if b_hh is not None else None
-        h0 = h0.contiguous() if h0 is not None else None
-        check(_timed(("gru_fwd", B, L, H),
-                     lambda: lib.rbx_gru_fwd(_ptr(gi), L * 3 * H, 3 * H, _ptr(w_hh), _ptr(b_hh), _ptr(h0), _ptr(lengths),
-                                             _DTYPE_CODE[lengths.dtype] if lengths is not None else 0, B, L, H, _lib.RBX_F32,
-                                             _ptr(out), _ptr(saved), _ptr(hn), _stream())))
-        ctx.save_for_backward(x2, w_ih, w_hh, saved, lengths)
-        ctx.dims = (B, L, I, H)
-        ctx.has_bias = (b_ih is not None, b_hh is not None)
-        ctx.has_h0 = h0 is not None
-        ctx.set_materialize_grads(False)
-        return out, hn
-
-    @staticmethod
-    def backward(ctx, d_out, d_hn):
-        x2, w_ih, w_hh, saved, lengths = ctx.saved_tensors
-        B, L, I, H = ctx.dims
-        dev = x2.device
-        M = B * L
-        if d_out is not None:
-            d_out = d_out.float()
-            if d_out.stride(2) != 1 or d_out.data_ptr() % 16 != 0 or d_out.stride(0) % 4 != 0 or d_out.stride(1) % 4 != 0:
-                d_out = d_out.contiguous()
-        d_hn = d_hn.float().contiguous() if d_hn is not None else None
-        dgi = torch.empty((M, 3 * H), dtype=torch.float32, device=dev)
-        dghn = torch.empty((M, H), dtype=torch.float32, device=dev)
-        dh0 = torch.empty((B, H), dtype=torch.float32, device=dev)
-        check(_timed(("gru_bwd", B, L, H),
-                     lambda: lib.rbx_gru_bwd(_ptr(saved), _ptr(w_hh), _ptr(d_out),
-                                             d_out.stride(0) if d_out is not None else L * H,
-                                             d_out.stride(1) if d_out is not None else H, _ptr(d_hn), _ptr(lengths),
-                                             _DTYPE_CODE[lengths.dtype] if lengths is not None else 0, B, L, H, _lib.RBX_F32,
-                                             _ptr(dgi), _ptr(dghn), _ptr(dh0), _stream())))
-        need = ctx.needs_input_grad
-        dx = _lin_dx(dgi, w_ih).view(B, L, I) if need[0] else None
-        dw_ih = db_ih = dw_hh = db_hh = None
-        want_bih, want_bhh = ctx.has_bias[0] and need[3], ctx.has_bias[1] and need[4]
-        if need[1] or want_bih or want_bhh:
-            dw_ih = torch.empty((3 * H, I), dtype=torch.float32, device=dev)
-            db_ih = torch.empty(3 * H, dtype=torch.float32, device=dev)
-            _lin_dwdb(x2, w_ih, dgi, dw_ih, db_ih)
-        if need[2] or want_bhh:
-            # h_prev of every position is a column block of the saved rows (row stride 5H).  Rows r, z of dW_hh are rows of
-            # d_gi^T h_prev; the n rows come from d_gh_n^T h_prev (the first product's n rows are not used)
-            hp = saved.view(M, _GRU_SAVED * H)[:, 4 * H:]
-            g_all = torch.empty((3 * H, H), dtype=torch.float32, device=dev)
-            g_n = torch.empty((H, H), dtype=torch.float32, device=dev)
-            db_n = torch.empty(H, dtype=torch.float32, device=dev)
-            _lin_dwdb(hp, w_hh, dgi, g_all, None)
-            _lin_dwdb(hp, w_hh, dghn, g_n, db_n)
-            dw_hh = torch.cat([g_all[:2 * H], g_n], dim=0)
-            if want_bhh:
-                db_hh = torch.cat([db_ih[:2 * H], db_n], dim=0)
-        return (dx, dw_ih if need[1] else None, dw_hh if need[2] else None, db_ih if want_bih else None, db_hh,
-                dh0 if (ctx.has_h0 and need[5]) else None, None)
-
-
-def gru(x, w_ih, w_hh, b_ih=None, b_hh=None, h0=None, lengths=None):
-    """One GRU layer over ``x`` [B, L, I] (batch first) with torch's parameters ``w_ih`` [3H, I], ``w_hh`` [3H, H], ``b_ih`` /
-    ``b_hh`` [3H] (rows ordered r, z, n) -> ``(out [B, L, H], h_n [B, H])``, one autograd node.  ``h0`` [B, H] (None = zeros).
-    ``lengths`` [B] (int32 / int64, on the device, None = all L) gives packed-sequence semantics without packing: for
-    ``t >= lengths[b]`` the state is frozen and ``out[b, t] = 0``, ``h_n[b]`` is the state after step ``lengths[b] - 1``;
-    ``lengths[b] = 0`` gives ``h_n[b] = h0[b]`` and a zero row.  Raises on CPU tensors; a shape or layout the kernels refuse
-    (``gru_supported``, non-float32, oddly strided input) and ``config.gru_fused = False`` run ``gru_torch``."""
+def gru_torch(x, w_ih, w_hh, b_ih=None, b_hh=None, h0=None, lengths=None):
+    """The step-loop composition: ``ops.linear`` for the input projection of all positions and for ``h W_hh^T`` of every step,
+    ATen for the gates.  Serves what ``gru_supported`` refuses and is what the fused op is measured against.  Same semantics
+    as ``gru`` (``lengths`` read on the device: no packing, no host copy)."""
     _require_cuda(x, "gru input")
-    _require_cuda(w_ih, "gru weight_ih")
-    _require_cuda(w_hh, "gru weight_hh")
-    if x.dim() != 3 or w_ih.shape[0] != w_hh.shape[0] or w_hh.shape[0] != 3 * w_hh.shape[1] or w_ih.shape[1] != x.shape[2]:
-        raise RuntimeError("gru: x %s, weight_ih %s, weight_hh %s do not fit" % (tuple(x.shape), tuple(w_ih.shape),
-                                                                                tuple(w_hh.shape)))
-    B = x.shape[0]
-    if h0 is not None:
-        _require_cuda(h0, "gru h0")
-        h0 = h0.reshape(B, w_hh.shape[1])
-    if B == 0 or not _gru_fused_ok(x, w_ih, w_hh, b_ih, b_hh, h0):
-        return gru_torch(x, w_ih, w_hh, b_ih, b_hh, h0, lengths)
-    return _Gru.apply(x, w_ih, w_hh, b_ih, b_hh, h0, _gru_lengths(lengths, B, x.device))
 
-
-# ---- attention-gated GRU recurrence: DIEN's AGRU / AUGRU (csrc/rbx_attgru.hip) -----------------------------------------------
-ATTGRU_MAX_HIDDEN = 128
-_ATTGRU_SAVED = 5              # r, u, n, gh_n, h_prev per position (rbx_attgru_fwd's d_saved; AGRU leaves u unwritten)
-_ATTGRU_CELLS = {"AGRU": 0, "AUGRU": 1}
-
-
-def _attgru_cell(cell):
-    if cell not in _ATTGRU_CELLS:
-        raise ValueError("att_gru: cell must be 'AGRU' or 'AUGRU' (got %r)" % (cell,))
-    return _ATTGRU_CELLS[cell]
-
-
-def att_gru_supported(hidden, seq_len, cell="AUGRU"):
-    """Whether the fused recurrence takes this shape (rbx_attgru_supported): ``hidden`` a multiple of 4 in 4 .. 128,
-    ``seq_len`` >= 1, ``cell`` 'AGRU' or 'AUGRU'.  What it refuses runs ``att_gru_torch``."""
-    return bool(lib.rbx_attgru_supported(int(hidden), int(seq_len), _attgru_cell(cell)))
-
-
-def _attgru_scores(att, B, L):
-    if att.numel() != B * L:
-        raise RuntimeError("att_gru: att %s does not fit x [%d, %d, .]" % (tuple(att.shape), B, L))
-    return att.reshape(B, L)
+    def blend(t, h, z, n):
+        z, n = z(), n()
+        return (1 - z) * n + z * h
+    return _gru_steps(x, w_ih, w_hh, b_ih, b_hh, h0, lengths, blend)
 
 
 def att_gru_torch(x, att, w_ih, w_hh, b_ih=None, b_hh=None, h0=None, lengths=None, cell="AUGRU"):
@@ -4780,47 +4701,33 @@ def att_gru_torch(x, att, w_ih, w_hh, b_ih=None, b_hh=None, h0=None, lengths=Non
     Same semantics as ``att_gru`` (``lengths`` read on the device: no packing, no host copy)."""
     _require_cuda(x, "att_gru input")
     augru = _attgru_cell(cell) == 1
-    B, L, _ = x.shape
-    H = w_hh.shape[1]
-    x, w_ih, w_hh = x.float(), w_ih.float(), w_hh.float()
-    att = _attgru_scores(att, B, L).float()
-    gi = linear(x, w_ih, b_ih)                                                  # [B, L, 3H]
-    h = h0.float() if h0 is not None else torch.zeros(B, H, dtype=torch.float32, device=x.device)
-    lengths = _gru_lengths(lengths, B, x.device)
-    outs = []
-    for t in range(L):
-        gh = linear(h, w_hh, b_hh)
-        g = gi[:, t]
-        r = torch.sigmoid(g[:, :H] + gh[:, :H])
-        n = torch.tanh(g[:, 2 * H:] + r * gh[:, 2 * H:])
-        c = att[:, t:t + 1]
+    att = _attgru_scores(att, x.shape[0], x.shape[1]).float()
+
+    def blend(t, h, z, n):
+        n, c = n(), att[:, t:t + 1]
         if augru:
-            c = c * torch.sigmoid(g[:, H:2 * H] + gh[:, H:2 * H])
-        hnew = (1 - c) * h + c * n
-        if lengths is not None:
-            act = (lengths > t).unsqueeze(1)
-            h = torch.where(act, hnew, h)
-            outs.append(torch.where(act, hnew, torch.zeros_like(hnew)))
-        else:
-            h = hnew
-            outs.append(hnew)
-    return torch.stack(outs, dim=1), h
+            c = c * z()
+        return (1 - c) * h + c * n
+    return _gru_steps(x, w_ih, w_hh, b_ih, b_hh, h0, lengths, blend)
 
 
-def _attgru_fused_ok(x, att, w_ih, w_hh, b_ih, b_hh, h0, cell):
-    """The refusals of ``att_gru`` that run the composition: a hidden width outside the kernels' range, non-float32 tensors, an
-    input that is a strided view or whose base is not 16-byte aligned."""
-    if not config.attgru_fused or x.dim() != 3 or not att_gru_supported(w_hh.shape[1], x.shape[1], cell):
-        return False
-    if any(t is not None and t.dtype != torch.float32 for t in (x, att, w_ih, w_hh, b_ih, b_hh, h0)):
+def _gru_fused_ok(x, att, w_ih, w_hh, b_ih, b_hh, h0, cell):
+    """The refusals of ``gru`` (``cell`` None) / ``att_gru`` that run the composition: the op's own switch, a hidden width
+    outside the kernels' range, non-float32 tensors, an input that is a strided view or whose base is not 16-byte aligned."""
+    if cell is None:
+        ok = config.gru_fused and gru_supported(w_hh.shape[1], x.shape[1])
+    else:
+        ok = config.attgru_fused and att_gru_supported(w_hh.shape[1], x.shape[1], cell)
+    if not ok or any(t is not None and t.dtype != torch.float32 for t in (x, att, w_ih, w_hh, b_ih, b_hh, h0)):
         return False
     return x.is_contiguous() and x.data_ptr() % 16 == 0
 
 
-class _AttGru(torch.autograd.Function):
-    """(out [B, L, H], h_n [B, H]) of one attention-gated GRU layer: the input projection on the dense path, the recurrence as
-    ONE launch (rbx_attgru_fwd); backward = ONE launch (rbx_attgru_bwd) for d_gi / d_gh_n / d_att / d_h0, then the dense path's
-    GEMMs for dx, dW_ih, dW_hh and the bias gradients."""
+class _GruLayer(torch.autograd.Function):
+    """(out [B, L, H], h_n [B, H]) of one GRU layer of any cell (``att`` and ``cell`` None: the plain GRU; else the scores
+    [B, L] and the C ABI's cell code): the input projection on the dense path, the recurrence as ONE launch (rbx_gru_fwd /
+    rbx_attgru_fwd); backward = ONE launch (rbx_gru_bwd / rbx_attgru_bwd) for d_gi / d_gh_n / d_h0 (and d_att), then the
+    dense path's GEMMs for dx, dW_ih, dW_hh and the bias gradients."""
 
     @staticmethod
     def forward(ctx, x, att, w_ih, w_hh, b_ih, b_hh, h0, lengths, cell):
@@ -4828,18 +4735,24 @@ class _AttGru(torch.autograd.Function):
         H = w_hh.shape[1]
         dev = x.device
         x2 = x.reshape(B * L, I)
-        att = att.contiguous()
+        att = att.contiguous() if att is not None else None
         w_ih, w_hh = w_ih.contiguous(), w_hh.contiguous()
         gi = _lin_fwd(x2, w_ih, b_ih.contiguous() if b_ih is not None else None)          # [B L, 3H]
         out = torch.empty((B, L, H), dtype=torch.float32, device=dev)
         hn = torch.empty((B, H), dtype=torch.float32, device=dev)
-        saved = torch.empty((B, L, _ATTGRU_SAVED * H), dtype=torch.float32, device=dev)
+        saved = torch.empty((B, L, _GRU_SAVED * H), dtype=torch.float32, device=dev)
         b_hh = b_hh.contiguous() if b_hh is not None else None
         h0 = h0.contiguous() if h0 is not None else None
-        check(_timed(("attgru_fwd", B, L, H, cell),
-                     lambda: lib.rbx_attgru_fwd(_ptr(gi), L * 3 * H, 3 * H, _ptr(att), _ptr(w_hh), _ptr(b_hh), _ptr(h0),
-                                                _ptr(lengths), _DTYPE_CODE[lengths.dtype] if lengths is not None else 0, B, L,
-                                                H, cell, _lib.RBX_F32, _ptr(out), _ptr(saved), _ptr(hn), _stream())))
+        len_dt = _DTYPE_CODE[lengths.dtype] if lengths is not None else 0
+        if cell is None:
+            check(_timed(("gru_fwd", B, L, H),
+                         lambda: lib.rbx_gru_fwd(_ptr(gi), L * 3 * H, 3 * H, _ptr(w_hh), _ptr(b_hh), _ptr(h0), _ptr(lengths),
+                                                 len_dt, B, L, H, _lib.RBX_F32, _ptr(out), _ptr(saved), _ptr(hn), _stream())))
+        else:
+            check(_timed(("attgru_fwd", B, L, H, cell),
+                         lambda: lib.rbx_attgru_fwd(_ptr(gi), L * 3 * H, 3 * H, _ptr(att), _ptr(w_hh), _ptr(b_hh), _ptr(h0),
+                                                    _ptr(lengths), len_dt, B, L, H, cell, _lib.RBX_F32, _ptr(out), _ptr(saved),
+                                                    _ptr(hn), _stream())))
         ctx.save_for_backward(x2, att, w_ih, w_hh, saved, lengths)
         ctx.dims = (B, L, I, H)
         ctx.cell = cell
@@ -4852,6 +4765,7 @@ class _AttGru(torch.autograd.Function):
     def backward(ctx, d_out, d_hn):
         x2, att, w_ih, w_hh, saved, lengths = ctx.saved_tensors
         B, L, I, H = ctx.dims
+        cell = ctx.cell
         dev = x2.device
         M = B * L
         if d_out is not None:
@@ -4859,17 +4773,22 @@ class _AttGru(torch.autograd.Function):
             if d_out.stride(2) != 1 or d_out.data_ptr() % 16 != 0 or d_out.stride(0) % 4 != 0 or d_out.stride(1) % 4 != 0:
                 d_out = d_out.contiguous()
         d_hn = d_hn.float().contiguous() if d_hn is not None else None
+        os_b, os_t = (d_out.stride(0), d_out.stride(1)) if d_out is not None else (L * H, H)
+        len_dt = _DTYPE_CODE[lengths.dtype] if lengths is not None else 0
         dgi = torch.empty((M, 3 * H), dtype=torch.float32, device=dev)
         dghn = torch.empty((M, H), dtype=torch.float32, device=dev)
-        datt = torch.empty((B, L), dtype=torch.float32, device=dev)
+        datt = torch.empty((B, L), dtype=torch.float32, device=dev) if cell is not None else None
         dh0 = torch.empty((B, H), dtype=torch.float32, device=dev)
-        check(_timed(("attgru_bwd", B, L, H, ctx.cell),
-                     lambda: lib.rbx_attgru_bwd(_ptr(saved), _ptr(att), _ptr(w_hh), _ptr(d_out),
-                                                d_out.stride(0) if d_out is not None else L * H,
-                                                d_out.stride(1) if d_out is not None else H, _ptr(d_hn), _ptr(lengths),
-                                                _DTYPE_CODE[lengths.dtype] if lengths is not None else 0, B, L, H, ctx.cell,
-                                                _lib.RBX_F32, _ptr(dgi), _ptr(dghn), _ptr(datt), _ptr(dh0), _stream())))
-        need = ctx.needs_input_grad
+        if cell is None:
+            check(_timed(("gru_bwd", B, L, H),
+                         lambda: lib.rbx_gru_bwd(_ptr(saved), _ptr(w_hh), _ptr(d_out), os_b, os_t, _ptr(d_hn), _ptr(lengths),
+                                                 len_dt, B, L, H, _lib.RBX_F32, _ptr(dgi), _ptr(dghn), _ptr(dh0), _stream())))
+        else:
+            check(_timed(("attgru_bwd", B, L, H, cell),
+                         lambda: lib.rbx_attgru_bwd(_ptr(saved), _ptr(att), _ptr(w_hh), _ptr(d_out), os_b, os_t, _ptr(d_hn),
+                                                    _ptr(lengths), len_dt, B, L, H, cell, _lib.RBX_F32, _ptr(dgi), _ptr(dghn),
+                                                    _ptr(datt), _ptr(dh0), _stream())))
+        need = ctx.needs_input_grad              # x, att, w_ih, w_hh, b_ih, b_hh, h0, lengths, cell
         dx = _lin_dx(dgi, w_ih).view(B, L, I) if need[0] else None
         dw_ih = db_ih = dw_hh = db_hh = None
         want_bih, want_bhh = ctx.has_bias[0] and need[4], ctx.has_bias[1] and need[5]
@@ -4878,9 +4797,10 @@ class _AttGru(torch.autograd.Function):
             db_ih = torch.empty(3 * H, dtype=torch.float32, device=dev)
             _lin_dwdb(x2, w_ih, dgi, dw_ih, db_ih)
         if need[3] or want_bhh:
-            # as in _Gru.backward: rows r, u of dW_hh are rows of d_gi^T h_prev (AGRU: the u columns of d_gi are zeros, so
-            # its u rows are exact zeros); the n rows come from d_gh_n^T h_prev
-            hp = saved.view(M, _ATTGRU_SAVED * H)[:, 4 * H:]
+            # h_prev of every position is a column block of the saved rows (row stride 5H).  Rows r, z of dW_hh are rows of
+            # d_gi^T h_prev (AGRU: the z columns of d_gi are zeros, so its z rows are exact zeros); the n rows come from
+            # d_gh_n^T h_prev (the first product's n rows are not used)
+            hp = saved.view(M, _GRU_SAVED * H)[:, 4 * H:]
             g_all = torch.empty((3 * H, H), dtype=torch.float32, device=dev)
             g_n = torch.empty((H, H), dtype=torch.float32, device=dev)
             db_n = torch.empty(H, dtype=torch.float32, device=dev)
@@ -4891,6 +4811,20 @@ class _AttGru(torch.autograd.Function):
                 db_hh = torch.cat([db_ih[:2 * H], db_n], dim=0)
         return (dx, datt if need[1] else None, dw_ih if need[2] else None, dw_hh if need[3] else None,
                 db_ih if want_bih else None, db_hh, dh0 if (ctx.has_h0 and need[6]) else None, None, None)
+
+
+def gru(x, w_ih, w_hh, b_ih=None, b_hh=None, h0=None, lengths=None):
+    """One GRU layer over ``x`` [B, L, I] (batch first) with torch's parameters ``w_ih`` [3H, I], ``w_hh`` [3H, H], ``b_ih`` /
+    ``b_hh`` [3H] (rows ordered r, z, n) -> ``(out [B, L, H], h_n [B, H])``, one autograd node.  ``h0`` [B, H] (None = zeros).
+    ``lengths`` [B] (int32 / int64, on the device, None = all L) gives packed-sequence semantics without packing: for
+    ``t >= lengths[b]`` the state is frozen and ``out[b, t] = 0``, ``h_n[b]`` is the state after step ``lengths[b] - 1``;
+    ``lengths[b] = 0`` gives ``h_n[b] = h0[b]`` and a zero row.  Raises on CPU tensors; a shape or layout the kernels refuse
+    (``gru_supported``, non-float32, oddly strided input) and ``config.gru_fused = False`` run ``gru_torch``."""
+    h0, _ = _gru_args("gru", x, w_ih, w_hh, h0)
+    B = x.shape[0]
+    if B == 0 or not _gru_fused_ok(x, None, w_ih, w_hh, b_ih, b_hh, h0, None):
+        return gru_torch(x, w_ih, w_hh, b_ih, b_hh, h0, lengths)
+    return _GruLayer.apply(x, None, w_ih, w_hh, b_ih, b_hh, h0, _gru_lengths(lengths, B, x.device), None)
 
 
 def att_gru(x, att, w_ih, w_hh, b_ih=None, b_hh=None, h0=None, lengths=None, cell="AUGRU"):
@@ -4904,22 +4838,12 @@ def att_gru(x, att, w_ih, w_hh, b_ih=None, b_hh=None, h0=None, lengths=None, cel
     ``out[b, t] = 0``, ``h_n[b]`` is the state after step ``lengths[b] - 1``; ``lengths[b] = 0`` gives ``h_n[b] = h0[b]`` and a
     zero row.  Raises on CPU tensors; a shape or layout the kernels refuse (``att_gru_supported``, non-float32, oddly strided
     input) and ``config.attgru_fused = False`` run ``att_gru_torch``."""
-    _require_cuda(x, "att_gru input")
-    _require_cuda(att, "att_gru att")
-    _require_cuda(w_ih, "att_gru weight_ih")
-    _require_cuda(w_hh, "att_gru weight_hh")
+    h0, att = _gru_args("att_gru", x, w_ih, w_hh, h0, att)
     code = _attgru_cell(cell)
-    if x.dim() != 3 or w_ih.shape[0] != w_hh.shape[0] or w_hh.shape[0] != 3 * w_hh.shape[1] or w_ih.shape[1] != x.shape[2]:
-        raise RuntimeError("att_gru: x %s, weight_ih %s, weight_hh %s do not fit" % (tuple(x.shape), tuple(w_ih.shape),
-                                                                                    tuple(w_hh.shape)))
-    B, L = x.shape[0], x.shape[1]
-    att = _attgru_scores(att, B, L)
-    if h0 is not None:
-        _require_cuda(h0, "att_gru h0")
-        h0 = h0.reshape(B, w_hh.shape[1])
-    if B == 0 or not _attgru_fused_ok(x, att, w_ih, w_hh, b_ih, b_hh, h0, cell):
+    B = x.shape[0]
+    if B == 0 or not _gru_fused_ok(x, att, w_ih, w_hh, b_ih, b_hh, h0, cell):
         return att_gru_torch(x, att, w_ih, w_hh, b_ih, b_hh, h0, lengths, cell)
-    return _AttGru.apply(x, att, w_ih, w_hh, b_ih, b_hh, h0, _gru_lengths(lengths, B, x.device), code)
+    return _GruLayer.apply(x, att, w_ih, w_hh, b_ih, b_hh, h0, _gru_lengths(lengths, B, x.device), code)
 
 
 # ---- additive attention pooling: NARM / STAMP (csrc/rbx_addattn.hip) ---------------------------------------------------------

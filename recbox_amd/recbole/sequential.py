@@ -1,7 +1,7 @@
 """The layers of RecBole's DIEN (third_party/recbole/model/sequential_recommender/dien.py:193-521): ``AGRUCell``, ``AUGRUCell``,
 ``DynamicRNN``, ``InterestExtractorNetwork`` and ``InterestEvolvingLayer``, with the reference's constructors, attribute names
 and ``state_dict`` keys.  For GPU tensors the attention-gated recurrence is ``ops.att_gru`` (one launch each way,
-csrc/rbx_attgru.hip), the plain GRUs are ``ops.gru`` with the lengths read on the device, and nothing is packed or copied to
+csrc/rbx_gru.hip), the plain GRUs are ``ops.gru`` with the lengths read on the device, and nothing is packed or copied to
 the host; for CPU tensors the same arithmetic runs in plain ATen.  RecBole's ``DIEN(config, dataset)`` model,
 ``ContextSeqEmbLayer`` and ``calculate_loss`` are not mirrored (``rechub.models.ranking.DIEN`` is the trainable model)."""
 import torch

@@ -1,4 +1,4 @@
-"""The fused attention-gated GRU on the HIP path (csrc/rbx_attgru.hip: ops.att_gru, the RecBole DIEN mirrors, rechub's DIEN)
+"""The fused attention-gated GRU on the HIP path (csrc/rbx_gru.hip: ops.att_gru, the RecBole DIEN mirrors, rechub's DIEN)
 against the restatement of tests/attgru64.py in float64 on the CPU, under the scale-aware bar of tests/fp32_bar.py: per tensor
 max|got - want| <= max(4 e32, 2e-6 max|want|), e32 the error of the float32 CPU run of the same restatement (nothing the
 kernels produce enters the bar; factor 4 everywhere but for one result of the DIEN step, see DIEN_FACTORS).  Every float64 comparison also runs the fp32 step-loop composition
@@ -345,7 +345,7 @@ def test_dien_step_fused_and_unfused_against_float64(kind, monkeypatch):
     Measured on the MI355X at factor 4, worst err / bar: AGRU 0.75 on both routes; AUGRU 0.55 fused and, for every tensor but
     one, 0.57 with the switch off.  The one: the gradient of ``mlp.mlp.2.alpha`` (the first Dice of the final MLP, 16 values,
     each a sum of 64 cancelling terms behind a BatchNorm), where the composition itself (switch off: ops.att_gru_torch, no
-    kernel of csrc/rbx_attgru.hip runs) has err 1.819e-08 against 4 e32 = 1.687e-08, 1.08 of the bar; e32 is 4.217e-09 there
+    kernel of csrc/rbx_gru.hip runs) has err 1.819e-08 against 4 e32 = 1.687e-08, 1.08 of the bar; e32 is 4.217e-09 there
     and 1.835e-08 for the same tensor under AGRU, so the float32 CPU run happened to land close.  The composition's own ratio
     sets the factor for that result: 8, the next power of two, at which the composition has 0.54 and the fused route 0.07."""
     from recbox_amd import ops

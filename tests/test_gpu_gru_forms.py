@@ -3,9 +3,9 @@ tests/gru64.py under the scale-aware bar of tests/fp32_bar.py: per tensor, max|g
 e32 the error of the same restatement run in float32 on the CPU.  Nothing the kernel returns enters the bar.
 
 Forms (workgroup = 16 samples, one wavefront per 16 hidden units, H a multiple of 4 in 4 .. 128):
-  gru_fwd_kernel<8>  / gru_bwd_kernel<8>    hidden <= 32       H = 4 (the floor), 20 (a partial second wavefront), 32
-  gru_fwd_kernel<16> / gru_bwd_kernel<16>   32 < hidden <= 64  H = 36, 64
-  gru_fwd_kernel<32> / gru_bwd_kernel<32>   64 < hidden        H = 68, 100, 128
+  gru_fwd_kernel<8, GRU>  / gru_bwd_kernel<8, GRU>    hidden <= 32       H = 4 (the floor), 20 (a partial second wavefront), 32
+  gru_fwd_kernel<16, GRU> / gru_bwd_kernel<16, GRU>   32 < hidden <= 64  H = 36, 64
+  gru_fwd_kernel<32, GRU> / gru_bwd_kernel<32, GRU>   64 < hidden        H = 68, 100, 128
   each at B = 1, 16 (a full tile), 17 (a tile holding one sample), 37 and L = 1, 2, 7 (both halves of the double-buffered
   state image); L = 200 at H = 64, B = 37 (the longest recurrence: the bar follows it through e32).
   Operands present or NULL: b_ih / b_hh, h0, lengths; d_out only, d_hn only (the other NULL in rbx_gru_bwd).
