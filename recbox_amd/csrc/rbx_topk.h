@@ -11,7 +11,9 @@ constexpr int kTopkCand = kTopkSeg;   // candidate slots per row (one segment of
 
 __device__ __forceinline__ unsigned key_of(float v) {
   const unsigned u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);          // larger float <=> larger key
+  // larger float <=> larger key, equal floats <=> equal keys: -0.0 (0x80000000) takes the key of +0.0, so that the two
+  // zeros tie and the lower index decides between them (value_of returns +0.0 for either)
+  return (u > 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ unsigned long long pack_winner(unsigned key, long long index) {
   return (static_cast<unsigned long long>(key) << 32) | static_cast<unsigned>(~static_cast<unsigned>(index));

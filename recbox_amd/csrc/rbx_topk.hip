@@ -47,10 +47,24 @@ __global__ __launch_bounds__(256) void topk_kernel(const float* __restrict__ val
   const int len = static_cast<int>((n_row - first < seg) ? (n_row - first > 0 ? n_row - first : 0) : seg);
   const float* row = vals + u * row_stride + first;
   const long long* irow = idx_in != nullptr ? idx_in + u * row_stride + first : nullptr;
-  const int want = (K < len) ? K : len;
   const int tid = threadIdx.x;
   __shared__ unsigned s_row[kTopkSeg];
-  for (int i = tid; i < len; i += 256) s_row[i] = key_of(row[i * sample_stride]);     // the only pass over HBM
+  __shared__ int s_real;
+  // A survivor at position -1 is the padding of a segment that was shorter than K, not an element: it is staged as key
+  // 0, below the key of every score (-inf is 0x007FFFFF), and is not counted, so `want` real elements rank above it
+  // and no level selects, counts or reports it.  Padding reaches the output only as the empty slots after them.
+  if (tid == 0) s_real = 0;
+  __syncthreads();
+  int mine = 0;
+  for (int i = tid; i < len; i += 256) {                                               // the only pass over HBM
+    const bool real = irow == nullptr || irow[i] >= 0;
+    s_row[i] = real ? key_of(row[i * sample_stride]) : 0u;
+    mine += real ? 1 : 0;
+  }
+  if (irow != nullptr && mine > 0) atomicAdd(&s_real, mine);
+  __syncthreads();
+  const int real_len = irow != nullptr ? s_real : len;
+  const int want = (K < real_len) ? K : real_len;
 
   // ---- radix select on the 64-bit word (key << 32 | ~position): 4 passes over the keys find the key T of the want-th
   // largest element; if more elements equal T than places are left, 4 more passes over THOSE elements' ~position find

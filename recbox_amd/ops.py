@@ -2452,7 +2452,10 @@ def gather_rows(columns, index):
 def topk(scores, k, index=None):
     """Per row the k largest entries of scores [rows, n] (fp32), sorted by (score descending, index ascending):
     (values [rows, k] fp32, indexes [rows, k] int64).  ``index`` [rows, n] int64 replaces the column number as the
-    reported index.  Rows shorter than k are padded with (-FLT_MAX, -1).  (rbx_topk: radix select + LDS bitonic sort)"""
+    reported index.  Rows shorter than k are padded with (-FLT_MAX, -1) after every real entry, -inf and -FLT_MAX scores
+    included.  +0.0 and -0.0 are equal scores (the lower index goes first) and a selected -0.0 may be returned as +0.0.
+    NaN scores are outside the contract: their place in the order is unspecified.  (rbx_topk: radix select + LDS bitonic
+    sort)"""
     _require_cuda(scores, "scores")
     if scores.dtype != torch.float32 or scores.dim() != 2 or scores.stride(1) != 1:
         scores = scores.float().contiguous()

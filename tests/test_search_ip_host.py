@@ -11,17 +11,10 @@ import pytest
 import torch
 
 from conftest import ROOT
+from retrieval_exact import sample_rank                    # rbx_topk's sample-rank rule: one restatement for all tests
 
 ENTRY_POINTS = ("rbx_search_ip_workspace_size", "rbx_search_ip")
 FAKE = 0x10000                                             # a non-NULL "device pointer" no refused call may touch
-
-
-def sample_rank(n, k):
-    """rbx_topk's rule: rank among 8 192 strided samples, 0 = the sampled threshold does not apply."""
-    if n <= 16384:
-        return 0
-    r = (4 * k * 8192 + n - 1) // n + 8
-    return r if r < 2048 else 0
 
 
 def test_header_declares_the_entry_points():
