@@ -1341,6 +1341,44 @@ int rbx_afm_bwd(const float* d_dout, int64_t dout_stride_b, const float* d_x, in
                 int32_t dim, int32_t att_dim, int32_t dtype, float* d_dx, float* d_dw, float* d_dh, void* d_workspace,
                 size_t workspace_bytes, void* stream);
 
+/* ---- AutoInt: multi-head self-attention over the fields, one layer (csrc/rbx_fieldattn.hip; additions only, the version stays)
+ * Replaces, per layer of third_party/recbole/model/context_aware_recommender/autoint.py:88-98, nn.MultiheadAttention called as
+ * attn(x, x, x) on the [F, B, E] view: the in-projection into [F, B, 3 E], three head-major copies, the [B h, F, F] scores
+ * written, soft-maxed, dropped out and re-read, their average over the heads and the out-projection.  B = batch, F = n_fields,
+ * E = dim, h = heads, dh = E / h.  Per sample, x [F, E]:
+ *   q | k | v = x Win^T + bin       S_t = (q_t dh^-1/2) k_t^T       P_t = softmax over the keys (max-subtracted)
+ *   P~_t = keep_t * P_t * 65536 / (65536 - thr16)   (p_drop > 0)       o = concat_t P~_t v_t
+ *   z = o Wout^T + bout             y = z [+ res] [then relu]
+ * d_x is read at x[b x_stride_b + f x_stride_f + e], so the reference's [F, B, E] view and a [B, F, E] tensor both come in
+ * without a copy; d_res (NULL: none) likewise.  d_in_w [3 E, E], d_in_b [3 E] or NULL, d_out_w [E, E], d_out_b [E] or NULL,
+ * contiguous.  keep(b h + t, query, key) is the function of rbx_attn_dropout_fwd with the same (p_drop, seed, d_seed_add):
+ * rbx_attn_dropout_mask(B h, F, F, ...) returns the mask these kernels use; nothing is stored, p_drop = 0 draws nothing.
+ *   rbx_fieldattn_fwd  one launch.  A wavefront stages one sample's x in LDS (field rows padded to 16 inside the kernel); both
+ *                      projections, q k^T and P v run on v_mfma_f32_16x16x4_f32; q, k, v, the probabilities and o stay on
+ *                      chip.  Writes d_y [B, F, E] and, when not NULL, the pre-dropout probabilities d_attn [B, h, F, F].
+ *   rbx_fieldattn_bwd  d_dy is read at dy[b dy_stride_b + f dy_stride_f + e]; d_y (the forward's, needed only with relu) gives
+ *                      the relu mask.  One launch recomputes q, k, v, P, the mask and o with the forward's instructions and
+ *                      writes d_dx [B, F, E] and d_dres [B, F, E] (= dy under the relu mask); the weight and bias gradients
+ *                      are summed per wavefront into one workspace row of 4 E E + 4 E floats
+ *                      (rbx_fieldattn_bwd_workspace_size: at most 2048 rows, whatever the batch) and a second launch adds the
+ *                      rows in a fixed order into d_din_w [3 E, E], d_din_b [3 E], d_dout_w [E, E], d_dout_b [E].  Every
+ *                      output pointer may be NULL to skip it; with all four weight outputs NULL the workspace is not read.
+ * Supported (rbx_fieldattn_supported): 2 <= F <= 48; E a multiple of 4 in [4, 32]; 1 <= h <= 8 dividing E with dh a multiple
+ * of 4; dtype (the RBX_* code of every float tensor) RBX_F32; x, res and dy 16-byte aligned with strides that are multiples of
+ * 4.  Anything else: RBX_ERR_UNSUPPORTED before any launch.  batch = 0 launches nothing.  No atomics, sums in a fixed order;
+ * no call allocates or reads back: capturable.  Workgroups take up to 160 KiB of dynamic LDS. */
+int rbx_fieldattn_supported(int32_t n_fields, int32_t dim, int32_t heads);
+int rbx_fieldattn_fwd(const float* d_x, int64_t x_stride_b, int64_t x_stride_f, const float* d_in_w, const float* d_in_b,
+                      const float* d_out_w, const float* d_out_b, const float* d_res, int64_t res_stride_b, int64_t res_stride_f,
+                      int32_t relu, int64_t batch, int32_t n_fields, int32_t dim, int32_t heads, int32_t dtype, float p_drop,
+                      uint64_t seed, const uint64_t* d_seed_add, float* d_y, float* d_attn, void* stream);
+size_t rbx_fieldattn_bwd_workspace_size(int64_t batch, int32_t n_fields, int32_t dim, int32_t heads);
+int rbx_fieldattn_bwd(const float* d_dy, int64_t dy_stride_b, int64_t dy_stride_f, const float* d_x, int64_t x_stride_b,
+                      int64_t x_stride_f, const float* d_in_w, const float* d_in_b, const float* d_out_w, const float* d_y,
+                      int32_t relu, int64_t batch, int32_t n_fields, int32_t dim, int32_t heads, int32_t dtype, float p_drop,
+                      uint64_t seed, const uint64_t* d_seed_add, float* d_dx, float* d_dres, float* d_din_w, float* d_din_b,
+                      float* d_dout_w, float* d_dout_b, void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* ---- FiBiNet: SENET gate and bilinear pair interaction (csrc/rbx_bilinear.hip; additions only, the version stays) -----------
  * Replaces, under third_party/rechub/basic/layers.py (SENETLayer, BiLinearInteractionLayer) and models/ranking/fibinet.py:31-38,
  * P = F (F - 1) / 2 nn.Linear calls on [B, 1, D] slices run twice per step, a torch.cat of 2 P pieces and a flatten.  B = batch,

@@ -6,6 +6,7 @@ librecbox_hip.so on raw ``data_ptr()``s.  There is no eager/PyTorch fallback: a
 CPU tensor or a missing library raises.
 """
 import ctypes
+import math
 import os
 import weakref
 
@@ -161,6 +162,17 @@ class config(object):
     # composition whose [B, P, D] and [B, P, A] tensors autograd keeps.  Off, or for what afm_pool_supported refuses: that
     # composition (afm_pool_torch).  Measurements: profiles/afm/INDEX.md.
     afm_fused = os.environ.get("RECBOX_AMD_AFM_FUSED", "1") != "0"
+    # AutoInt: one multi-head self-attention layer over the fields as one launch that keeps a sample's x, q, k, v and one head's
+    # F x F probabilities on chip (field_attn: csrc/rbx_fieldattn.hip) instead of nn.MultiheadAttention's chain, whose
+    # [B h, F, F] score tensors autograd keeps.  Off, or for what field_attn_supported refuses: the composition
+    # (field_attn_torch).  Measurements: profiles/autoint/INDEX.md.
+    field_attn_fused = os.environ.get("RECBOX_AMD_FIELD_ATTN_FUSED", "1") != "0"
+    # The classes field_attn sends to the kernels: up to this many fields and this width.  Measured (profiles/autoint/INDEX.md):
+    # at 26 fields x 16 the kernels are ahead of nn.MultiheadAttention and of linear + attention + linear; at 39 fields (a third
+    # 16-row tile) or width 32 they lose to the latter, so those classes run the composition.  The kernels themselves take up to
+    # 48 fields x 32 (field_attn_supported); the tests raise these two attributes to run them there.
+    field_attn_fields = 32
+    field_attn_dim = 16
 
 
 def _require_cuda(t, what):
@@ -5702,3 +5714,159 @@ def afm_pool(x, w, h, want_attn=False):
     if not _afm_fused_ok(x, w, h):
         return afm_pool_torch(x, w, h, want_attn)
     return _AfmPool.apply(x, w, h, bool(want_attn))
+
+
+# ---- AutoInt: multi-head self-attention over the fields (csrc/rbx_fieldattn.hip) ----------------------------------------------
+FIELD_ATTN_MAX_FIELDS, FIELD_ATTN_MAX_DIM, FIELD_ATTN_MAX_HEADS = 48, 32, 8
+
+
+def field_attn_supported(n_fields, dim, heads, dtype=torch.float32):
+    """Whether the fused layer takes this shape (rbx_fieldattn_supported): float32, 2 .. 48 fields, ``dim`` a multiple of 4 in
+    4 .. 32, 1 .. 8 heads dividing ``dim`` into widths that are multiples of 4.  What it refuses runs ``field_attn_torch``."""
+    if dtype != torch.float32:
+        return False
+    return bool(lib.rbx_fieldattn_supported(int(n_fields), int(dim), int(heads)))
+
+
+def _drop_scale(dropout_p):
+    """65536 / (65536 - thr16), thr16 = round(65536 p): what the dropout kernels multiply a kept probability by."""
+    thr = min(int(float(dropout_p) * 65536.0 + 0.5), 65535)
+    return 65536.0 / float(65536 - thr)
+
+
+def field_attn_torch(x, in_w, in_b, out_w, out_b, heads, residual=None, relu=False, dropout_p=0.0, keep=None, want_attn=False):
+    """One self-attention layer over the fields with the arithmetic of ``nn.MultiheadAttention(E, heads)`` called as
+    ``attn(x, x, x)`` without masks (autoint.py:90-91), in plain ATen on whatever device the tensors live on.  ``x`` [B, F, E]
+    (the reference's [F, B, E] tensor, transposed), ``in_w`` [3 E, E], ``in_b`` [3 E] or None, ``out_w`` [E, E], ``out_b`` [E] or
+    None -> ``(y [B, F, E], attn [B, heads, F, F] or None)``:
+
+        q | k | v = x in_w^T + in_b      S_t = (q_t dh^-1/2) k_t^T      P_t = softmax_keys(S_t)      o = concat_t P~_t v_t
+        y = o out_w^T + out_b [+ residual] [then relu]
+
+    ``keep`` (bool, B heads F F elements) with ``dropout_p`` gives ``P~ = keep * P * 65536 / (65536 - round(65536 p))``, the
+    kernels' dropout; ``dropout_p > 0`` without ``keep`` draws a torch dropout mask; otherwise ``P~ = P``.  ``attn`` is the
+    pre-dropout P, detached.  Serves what the fused op refuses and is what it is measured against."""
+    B, F, E = x.shape
+    dh = E // heads
+    qkv = torch.nn.functional.linear(x, in_w, in_b)                                        # [B, F, 3 E]
+    q, k, v = (qkv[..., i * E:(i + 1) * E].reshape(B, F, heads, dh).transpose(1, 2) for i in range(3))
+    q = q * math.sqrt(1.0 / float(dh))
+    p = torch.softmax(torch.matmul(q, k.transpose(-2, -1)), dim=-1)                        # [B, h, F, F]
+    pd = p
+    if keep is not None:
+        pd = p * (keep.reshape(B, heads, F, F).to(p.dtype) * _drop_scale(dropout_p))
+    elif dropout_p > 0.0:
+        pd = torch.nn.functional.dropout(p, p=dropout_p)
+    o = torch.matmul(pd, v).transpose(1, 2).reshape(B, F, E)
+    y = torch.nn.functional.linear(o, out_w, out_b)
+    if residual is not None:
+        y = y + residual
+    if relu:
+        y = torch.relu(y)
+    return y, (p.detach() if want_attn else None)
+
+
+def _field_attn_fused_ok(x, in_w, in_b, out_w, out_b, heads, residual):
+    """The refusals of ``field_attn`` that run the composition: the switch, a shape outside the kernels' range, CPU or
+    non-float32 tensors, an empty batch, a class the measurements gate (more than ``config.field_attn_fields`` fields or wider
+    than ``config.field_attn_dim``), an ``x`` whose rows are not contiguous, 16-byte aligned and a multiple of 4 floats apart."""
+    if not config.field_attn_fused or x.shape[0] == 0:
+        return False
+    if x.shape[1] > config.field_attn_fields or x.shape[2] > config.field_attn_dim:
+        return False
+    if any(t is not None and ((not t.is_cuda) or t.dtype != torch.float32) for t in (x, in_w, in_b, out_w, out_b, residual)):
+        return False
+    if not field_attn_supported(x.shape[1], x.shape[2], heads):
+        return False
+    return _fields_in_place(x)
+
+
+class _FieldAttn(torch.autograd.Function):
+    """(y [B, F, E], attn [B, h, F, F] or None) as ONE launch (rbx_fieldattn_fwd); backward = rbx_fieldattn_bwd (one launch plus
+    the tail that adds the per-wavefront rows of the weight gradients).  Saved: the inputs and, with relu, y -- the backward
+    recomputes q, k, v, the probabilities and the dropout mask, so no softmax statistics are kept; ``attn`` carries no
+    gradient."""
+
+    @staticmethod
+    def forward(ctx, x, in_w, in_b, out_w, out_b, residual, heads, relu, p_drop, seed, want_attn):
+        B, F, E = x.shape
+        dev = x.device
+        in_w, out_w = in_w.contiguous(), out_w.contiguous()
+        in_b = in_b.contiguous() if in_b is not None else None
+        out_b = out_b.contiguous() if out_b is not None else None
+        if residual is not None and not _fields_in_place(residual):
+            residual = residual.contiguous()
+        y = torch.empty((B, F, E), dtype=torch.float32, device=dev)
+        attn = torch.empty((B, heads, F, F), dtype=torch.float32, device=dev) if want_attn else None
+        tick = dropout_tick(dev) if p_drop > 0 else None
+        rs = (residual.stride(0), residual.stride(1)) if residual is not None else (0, 0)
+        check(_timed(("fieldattn_fwd", B, F, E, heads),
+                     lambda: lib.rbx_fieldattn_fwd(_ptr(x), x.stride(0), x.stride(1), _ptr(in_w), _ptr(in_b), _ptr(out_w),
+                                                   _ptr(out_b), _ptr(residual), rs[0], rs[1], int(relu), B, F, E, heads,
+                                                   _lib.RBX_F32, p_drop, seed, _ptr(tick), _ptr(y), _ptr(attn), _stream())))
+        ctx.save_for_backward(x, in_w, in_b, out_w, y if relu else None)
+        ctx.meta = (heads, relu, p_drop, seed, tick, residual is not None, out_b is not None)
+        if attn is not None:
+            ctx.mark_non_differentiable(attn)
+        return y, attn
+
+    @staticmethod
+    def backward(ctx, dy, _dattn):
+        x, in_w, in_b, out_w, y = ctx.saved_tensors
+        heads, relu, p_drop, seed, tick, has_res, has_ob = ctx.meta
+        B, F, E = x.shape
+        dev = x.device
+        need = ctx.needs_input_grad
+        dy = dy.float()
+        if not _fields_in_place(dy):
+            dy = dy.contiguous()
+
+        def new(want, *shape):
+            return torch.empty(shape, dtype=torch.float32, device=dev) if want else None
+        dx = new(need[0], B, F, E)
+        dwi, dbi = new(need[1], 3 * E, E), new(need[2] and in_b is not None, 3 * E)
+        dwo, dbo = new(need[3], E, E), new(need[4] and has_ob, E)
+        want_res = need[5] and has_res
+        dres = new(want_res and relu, B, F, E)
+        ws_bytes, ws = 0, None
+        if any(t is not None for t in (dwi, dbi, dwo, dbo)):
+            ws_bytes = lib.rbx_fieldattn_bwd_workspace_size(B, F, E, heads)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        if ws is not None or dx is not None or dres is not None:
+            check(_timed(("fieldattn_bwd", B, F, E, heads),
+                         lambda: lib.rbx_fieldattn_bwd(_ptr(dy), dy.stride(0), dy.stride(1), _ptr(x), x.stride(0), x.stride(1),
+                                                       _ptr(in_w), _ptr(in_b), _ptr(out_w), _ptr(y), int(relu), B, F, E, heads,
+                                                       _lib.RBX_F32, p_drop, seed, _ptr(tick), _ptr(dx), _ptr(dres), _ptr(dwi),
+                                                       _ptr(dbi), _ptr(dwo), _ptr(dbo), _ptr(ws), ws_bytes, _stream())))
+        if want_res and not relu:
+            dres = dy                                                  # without relu the residual's gradient is dy itself
+        return dx, dwi, dbi, dwo, dbo, dres, None, None, None, None, None
+
+
+def field_attn(x, in_w, in_b, out_w, out_b, heads, residual=None, relu=False, dropout_p=0.0, seed=None, want_attn=False):
+    """One AutoInt interacting layer as one autograd node over rbx_fieldattn_fwd / _bwd: ``nn.MultiheadAttention(E, heads)``
+    called as ``attn(x, x, x)`` (see ``field_attn_torch`` for the formulas), with ``x`` [B, F, E] -- the transpose of the
+    reference's [F, B, E] tensor is read in place -- and an optional epilogue ``+ residual`` [B, F, E], then relu.  Returns
+    ``(y [B, F, E], attn [B, heads, F, F] or None)``; ``attn`` is the pre-dropout probabilities and carries no gradient.
+    ``dropout_p`` > 0 drops probabilities with the mask ``attention_dropout_mask(B * heads, F, F, dropout_p, seed)``; ``seed``
+    defaults to 64 bits from torch's CPU generator.  Nothing of B heads F F or B F 3 E elements is formed or saved unless
+    ``want_attn``.  CPU or non-float32 tensors, an empty batch, what ``field_attn_supported`` refuses, more than
+    ``config.field_attn_fields`` fields or a width above ``config.field_attn_dim`` (measured slower), an oddly strided ``x`` and
+    ``config.field_attn_fused = False`` run ``field_attn_torch`` (which then draws a torch dropout mask)."""
+    heads = int(heads)
+    if x.dim() != 3 or heads < 1:
+        raise RuntimeError("field_attn: x %s is not [B, F, E] or heads = %d" % (tuple(x.shape), heads))
+    E = x.shape[2]
+    if (E % heads != 0 or tuple(in_w.shape) != (3 * E, E) or tuple(out_w.shape) != (E, E)
+            or (in_b is not None and tuple(in_b.shape) != (3 * E,)) or (out_b is not None and tuple(out_b.shape) != (E,))
+            or (residual is not None and residual.shape != x.shape)):
+        raise RuntimeError("field_attn: x %s, heads %d, in_w %s, out_w %s, biases, residual do not fit"
+                           % (tuple(x.shape), heads, tuple(in_w.shape), tuple(out_w.shape)))
+    if dropout_p and not 0.0 <= dropout_p < 1.0:
+        raise ValueError("dropout probability has to be between 0 and 1, but got {}".format(dropout_p))
+    dropout_p = float(dropout_p or 0.0)
+    if not _field_attn_fused_ok(x, in_w, in_b, out_w, out_b, heads, residual):
+        return field_attn_torch(x, in_w, in_b, out_w, out_b, heads, residual, relu, dropout_p, None, want_attn)
+    if dropout_p > 0.0 and seed is None:
+        seed = _draw_seed()
+    return _FieldAttn.apply(x, in_w, in_b, out_w, out_b, residual, heads, bool(relu), dropout_p, int(seed or 0), bool(want_attn))

@@ -479,3 +479,34 @@ class DIEN(torch.nn.Module):
         if self.features:
             parts.append(_embed(self.embedding, x, self.features, False).flatten(start_dim=1))
         return torch.sigmoid(_mlp(self.mlp, torch.cat(parts, dim=1)).squeeze(1)), aux_loss
+
+
+# ---- AutoInt (RecBole's AutoInt in the rechub style) --------------------------------------------------------------------------
+class AutoInt(torch.nn.Module):
+    """AutoInt as a trainable model in the style of this zoo: ``EmbeddingLayer`` over ``features`` (unshared ``SparseFeature``s
+    of one ``embed_dim``), an ``LR`` over the flattened embeddings as the first-order term, and
+    ``recbole.context_aware.AutoIntInteraction`` (one ``ops.field_attn`` launch each way per layer) for the attention and MLP
+    terms; the output is ``sigmoid(first + interaction)`` [B].  ``interaction.state_dict()`` has RecBole's AutoInt keys.
+    RecBole's ``AutoInt(config, dataset)`` constructor, its ``ContextRecommender`` base and ``calculate_loss`` are NOT
+    mirrored."""
+
+    def __init__(self, features, attention_size=16, n_layers=3, num_heads=2, mlp_hidden_size=(128, 128),
+                 dropout_probs=(0.2, 0.2, 0.2), has_residual=True):
+        super(AutoInt, self).__init__()
+        from ...recbole.context_aware import AutoIntInteraction
+        dims = set(fea.embed_dim for fea in features)
+        if len(dims) != 1 or len(features) < 2:
+            raise ValueError("AutoInt: at least two features of one embed_dim (got dims %s)" % sorted(dims))
+        self.features = features
+        self.embedding = EmbeddingLayer(features)
+        self.num_fields = len(features)
+        self.embed_dim = dims.pop()
+        self.linear = LR(self.num_fields * self.embed_dim)
+        self.interaction = AutoIntInteraction(self.num_fields, self.embed_dim, attention_size, n_layers, num_heads,
+                                              list(mlp_hidden_size), list(dropout_probs), has_residual)
+
+    def forward(self, x):
+        from .multi_task import _embed
+        embed_x = _embed(self.embedding, x, self.features, False)          # [B, F, D]
+        y = _lr(self.linear, embed_x.flatten(start_dim=1)) + self.interaction(embed_x)
+        return torch.sigmoid(y.squeeze(1))
