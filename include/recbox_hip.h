@@ -1379,6 +1379,41 @@ int rbx_fieldattn_bwd(const float* d_dy, int64_t dy_stride_b, int64_t dy_stride_
                       uint64_t seed, const uint64_t* d_seed_add, float* d_dx, float* d_dres, float* d_din_w, float* d_din_b,
                       float* d_dout_w, float* d_dout_b, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ---- FiGNN: one message-passing step of the field graph (csrc/rbx_fignn.hip; additions only, the version stays) --------------
+ * Replaces, per layer of third_party/recbole/model/context_aware_recommender/fignn.py:119-137, the gathered [B, F^2, 2 A] concat
+ * in front of Linear(2 A, 1), GraphLayer's two broadcast matmuls and bmm, nn.GRUCell on [B F, A] and the residual add.
+ * B = batch, F = n_fields, A = dim.  Per sample, h, h0 [F, A] (h0: the residual and the graph's source), gates r, z, n:
+ *   s_i = w_attn[:A] . h0_i     d_j = w_attn[A:] . h0_j     g[i, :] = softmax_j leaky_relu(s_i + d_j, 0.01), g[i, i] = 0
+ *   hout_j = W_out[j] h_j       aggr_i = sum_j g[i, j] hout_j        a_i = W_in[i] aggr_i + bias_p
+ *   r = sig(W_ir a + b_ir + W_hr h + b_hr)   z = sig(W_iz a + b_iz + W_hz h + b_hz)   n = tanh(W_in a + b_in + r (W_hn h + b_hn))
+ *   h'_i = (1 - z) n + z h_i + h0_i
+ * d_h, d_h0, d_dy [B, F, A], d_w_attn [2 A], d_w_out, d_w_in [F, A, A], d_bias_p [A], d_w_ih, d_w_hh [3 A, A], d_b_ih, d_b_hh
+ * [3 A]: contiguous; h, h0 and w_attn 16-byte aligned (they are read four floats at a time).
+ *   rbx_fignn_step_fwd  one launch.  A workgroup keeps hout and aggr of a tile of 16 (or 8) samples in LDS; the four matrix products
+ *                       and g hout run on v_mfma_f32_16x16x4_f32, a field's matrices are fetched once per workgroup and tile.
+ *                       Writes d_y [B, F, A] and, when not NULL, d_graph [B, F, F].
+ *   rbx_fignn_step_bwd  one launch that recomputes the forward from its inputs and writes d_dh and d_dh0 [B, F, A] (separate
+ *                       tensors: dh0 comes through the epilogue and through g), plus a tail launch that adds the per-workgroup
+ *                       (dW_out, dW_in) and per-wavefront (the rest) partial rows of the workspace in a fixed order into
+ *                       d_dw_attn [2 A], d_dw_out, d_dw_in [F, A, A], d_dbias_p [A], d_dw_ih, d_dw_hh [3 A, A], d_db_ih, d_db_hh
+ *                       [3 A].  Every output pointer may be NULL to skip it; with all eight weight outputs NULL there are no
+ *                       partial rows, no tail and no workspace.  rbx_fignn_step_bwd_workspace_size: at most 256 rows of
+ *                       2 F A^2 and 1024 of 6 A^2 + 9 A floats whatever the batch (26 MiB at 39 x 16, 91 MiB at 39 x 32, 109 MiB at 48 x 32).
+ * Supported (rbx_fignn_step_supported): 2 <= F <= 48 and A a multiple of 4 in [4, 32], every combination: where the backward's
+ * two [F][16][A + 4] buffers do not fit in 160 KiB of LDS (from 46 fields at A = 20, 39 at 24, 34 at 28, 30 at 32) a tile is 8
+ * samples.  dtype (the RBX_* code of every tensor) RBX_F32.  Anything else: RBX_ERR_UNSUPPORTED before any launch.  batch = 0
+ * launches nothing.  No atomics, sums in a fixed order: equal bits run to run; no call allocates or reads back: capturable. */
+int rbx_fignn_step_supported(int32_t n_fields, int32_t dim);
+int rbx_fignn_step_fwd(const float* d_h, const float* d_h0, const float* d_w_attn, const float* d_w_out, const float* d_w_in,
+                       const float* d_bias_p, const float* d_w_ih, const float* d_w_hh, const float* d_b_ih, const float* d_b_hh,
+                       int64_t batch, int32_t n_fields, int32_t dim, int32_t dtype, float* d_y, float* d_graph, void* stream);
+size_t rbx_fignn_step_bwd_workspace_size(int64_t batch, int32_t n_fields, int32_t dim);
+int rbx_fignn_step_bwd(const float* d_dy, const float* d_h, const float* d_h0, const float* d_w_attn, const float* d_w_out,
+                       const float* d_w_in, const float* d_bias_p, const float* d_w_ih, const float* d_w_hh, const float* d_b_ih,
+                       const float* d_b_hh, int64_t batch, int32_t n_fields, int32_t dim, int32_t dtype, float* d_dh,
+                       float* d_dh0, float* d_dw_attn, float* d_dw_out, float* d_dw_in, float* d_dbias_p, float* d_dw_ih,
+                       float* d_dw_hh, float* d_db_ih, float* d_db_hh, void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* ---- FiBiNet: SENET gate and bilinear pair interaction (csrc/rbx_bilinear.hip; additions only, the version stays) -----------
  * Replaces, under third_party/rechub/basic/layers.py (SENETLayer, BiLinearInteractionLayer) and models/ranking/fibinet.py:31-38,
  * P = F (F - 1) / 2 nn.Linear calls on [B, 1, D] slices run twice per step, a torch.cat of 2 P pieces and a flatten.  B = batch,

@@ -307,6 +307,10 @@ SIGNATURES = {
     "rbx_fieldattn_bwd_workspace_size": (_sz, [_i64, _i32, _i32, _i32]),
     "rbx_fieldattn_bwd": (ctypes.c_int, [_P, _i64, _i64, _P, _i64, _i64, _P, _P, _P, _P, _i32, _i64, _i32, _i32, _i32, _i32, _f32,
                                          _u64, _P, _P, _P, _P, _P, _P, _P, _P, _sz, _P]),
+    "rbx_fignn_step_supported": (ctypes.c_int, [_i32, _i32]),
+    "rbx_fignn_step_fwd": (ctypes.c_int, [_P] * 10 + [_i64, _i32, _i32, _i32, _P, _P, _P]),
+    "rbx_fignn_step_bwd_workspace_size": (_sz, [_i64, _i32, _i32]),
+    "rbx_fignn_step_bwd": (ctypes.c_int, [_P] * 11 + [_i64, _i32, _i32, _i32] + [_P] * 11 + [_sz, _P]),
     "rbx_senet_gate_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32]),
     "rbx_senet_gate_fwd": (ctypes.c_int, [_P, _i64, _i64, _P, _P, _i64, _i32, _i32, _i32, _i32, _i32, _P, _P, _P]),
     "rbx_senet_gate_bwd_workspace_size": (_sz, [_i64, _i32, _i32]),

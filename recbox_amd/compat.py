@@ -121,7 +121,7 @@ _RECHUB = {
 # Names a path gained after its entry was published.  ``alias_table()`` keeps an entry as it was first listed (callers compare
 # entries); ``install()`` binds these as well.
 _RECHUB_ALSO = {"models.matching.comirec": ["ComirecSA"], "models.ranking": ["FiBiNet", "DCN", "DCNv2", "EDCN", "WideDeep", "AFM",
-                                                                                  "DIEN", "AutoInt"],
+                                                                                  "DIEN", "AutoInt", "FiGNN"],
                 "models.matching": ["YoutubeSBC", "FaceBookDSSM"]}
 
 

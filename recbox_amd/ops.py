@@ -173,6 +173,17 @@ class config(object):
     # 48 fields x 32 (field_attn_supported); the tests raise these two attributes to run them there.
     field_attn_fields = 32
     field_attn_dim = 16
+    # FiGNN: one message-passing step of the field graph (edge weights, GraphLayer, the GRU cell, + h0) as one launch each way
+    # that keeps a tile's hout and aggr on chip (fignn_step: csrc/rbx_fignn.hip) instead of a dozen ATen launches and five or
+    # six saved [B, F, A] .. [B, F, 3 A] tensors per layer.  Off, or for what fignn_step_supported refuses: the composition
+    # (fignn_step_torch).
+    fignn_fused = os.environ.get("RECBOX_AMD_FIGNN_FUSED", "1") != "0"
+    # The classes fignn_step sends to the kernels: up to this many fields and this width.  Measured (profiles/fignn/INDEX.md,
+    # forward + backward against fignn_step_torch): width 16 is 2.5 - 4.2 x at B = 4096 and 5.2 - 9.1 x at B = 65 536 for 26, 39
+    # and 48 fields; width 32 is 1.6 - 1.7 x except 26 fields at B = 4096, where the kernels lose (0.88 x, spread 1 %), so that width
+    # runs the composition.  The kernels themselves take up to 48 fields x 32; the tests raise these two attributes.
+    fignn_fields = 48
+    fignn_dim = 16
 
 
 def _require_cuda(t, what):
@@ -5870,3 +5881,127 @@ def field_attn(x, in_w, in_b, out_w, out_b, heads, residual=None, relu=False, dr
     if dropout_p > 0.0 and seed is None:
         seed = _draw_seed()
     return _FieldAttn.apply(x, in_w, in_b, out_w, out_b, residual, heads, bool(relu), dropout_p, int(seed or 0), bool(want_attn))
+
+
+# ---- FiGNN: one message-passing step of the field graph (csrc/rbx_fignn.hip) ------------------------------------------------------
+FIGNN_MAX_FIELDS, FIGNN_MAX_DIM = 48, 32
+
+
+def fignn_step_supported(n_fields, dim, dtype=torch.float32):
+    """Whether the fused step takes this shape (rbx_fignn_step_supported): float32, 2 .. 48 fields, ``dim`` a multiple of 4 in
+    4 .. 32 (wide shapes run on tiles of 8 samples, not 16).  One field has no neighbour and is refused.  What it refuses runs ``fignn_step_torch``."""
+    if dtype != torch.float32:
+        return False
+    return bool(lib.rbx_fignn_step_supported(int(n_fields), int(dim)))
+
+
+def fignn_step_torch(h, h0, w_attn, W_out, W_in, bias_p, w_ih, w_hh, b_ih, b_hh, want_graph=False):
+    """One message-passing layer of FiGNN (fignn.py:119-137 and GraphLayer.forward) in plain ATen on whatever device the
+    tensors live on.  ``h``, ``h0`` [B, F, A] (``h0`` = att_feature: the residual and the graph's source), ``w_attn`` [2 A]
+    (``W_attn.weight[0]``), ``W_out``, ``W_in`` [F, A, A], ``bias_p`` [A], the ``nn.GRUCell`` parameters ``w_ih``, ``w_hh``
+    [3 A, A], ``b_ih``, ``b_hh`` [3 A] -> ``(h' [B, F, A], g [B, F, F] or None)``:
+
+        s_i = w_attn[:A] . h0_i    d_j = w_attn[A:] . h0_j    g[i, :] = softmax_j leaky_relu(s_i + d_j, 0.01), g[i, i] = 0
+        a_i = W_in[i] sum_j g[i, j] W_out[j] h_j + bias_p     h'_i = GRUCell(a_i, h_i) + h0_i
+
+    The reference's concat-and-Linear over the F^2 gathered pairs is ``s_i + d_j``; nothing of F^2 by A is formed.  ``g`` is
+    detached.  Serves what the fused op refuses and is what it is measured against."""
+    B, F, A = h.shape
+    w_attn = w_attn.reshape(-1)
+    s = torch.matmul(h0, w_attn[:A])                                                       # [B, F]
+    d = torch.matmul(h0, w_attn[A:])
+    alpha = torch.nn.functional.leaky_relu(s.unsqueeze(2) + d.unsqueeze(1), 0.01)
+    alpha = alpha.masked_fill(torch.eye(F, dtype=torch.bool, device=h.device), float("-inf"))
+    g = torch.softmax(alpha, dim=-1)                                                       # [B, F, F]
+    hout = torch.einsum("fnk,bfk->bfn", W_out, h)
+    a = torch.einsum("fnk,bfk->bfn", W_in, torch.bmm(g, hout)) + bias_p
+    gi = torch.nn.functional.linear(a, w_ih, b_ih)
+    gh = torch.nn.functional.linear(h, w_hh, b_hh)
+    r = torch.sigmoid(gi[..., :A] + gh[..., :A])
+    z = torch.sigmoid(gi[..., A:2 * A] + gh[..., A:2 * A])
+    n = torch.tanh(gi[..., 2 * A:] + r * gh[..., 2 * A:])
+    return (1.0 - z) * n + z * h + h0, (g.detach() if want_graph else None)
+
+
+def _fignn_fused_ok(h, h0, weights):
+    """The refusals of ``fignn_step`` that run the composition: the switch, an empty batch, a class the gates exclude, CPU or
+    non-float32 tensors, a shape outside the kernels' range, an ``h`` or ``h0`` that is not contiguous and 16-byte aligned."""
+    if not config.fignn_fused or h.shape[0] == 0:
+        return False
+    if h.shape[1] > config.fignn_fields or h.shape[2] > config.fignn_dim:
+        return False
+    if any((not t.is_cuda) or t.dtype != torch.float32 for t in (h, h0) + tuple(weights)):
+        return False
+    if not fignn_step_supported(h.shape[1], h.shape[2]):
+        return False
+    return all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in (h, h0))
+
+
+class _FignnStep(torch.autograd.Function):
+    """(h' [B, F, A], g [B, F, F] or None) as ONE launch (rbx_fignn_step_fwd); backward = rbx_fignn_step_bwd (one launch plus
+    the tail that adds the partial rows of the weight gradients; no tail and no workspace when only h / h0 need gradients).
+    Saved: the inputs only -- the backward recomputes g, hout, aggr, a and the gates; ``g`` carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, h, h0, w_attn, W_out, W_in, bias_p, w_ih, w_hh, b_ih, b_hh, want_graph):
+        B, F, A = h.shape
+        dev = h.device
+        ws = tuple(t.contiguous() for t in (w_attn.reshape(-1), W_out, W_in, bias_p, w_ih, w_hh, b_ih, b_hh))
+        if ws[0].data_ptr() % 16 != 0:
+            ws = (ws[0].clone(),) + ws[1:]
+        y = torch.empty((B, F, A), dtype=torch.float32, device=dev)
+        graph = torch.empty((B, F, F), dtype=torch.float32, device=dev) if want_graph else None
+        check(_timed(("fignn_step_fwd", B, F, A),
+                     lambda: lib.rbx_fignn_step_fwd(_ptr(h), _ptr(h0), *[_ptr(t) for t in ws], B, F, A, _lib.RBX_F32, _ptr(y),
+                                                    _ptr(graph), _stream())))
+        ctx.save_for_backward(h, h0, *ws)
+        ctx.w_attn_shape = w_attn.shape
+        if graph is not None:
+            ctx.mark_non_differentiable(graph)
+        return y, graph
+
+    @staticmethod
+    def backward(ctx, dy, _dgraph):
+        h, h0 = ctx.saved_tensors[:2]
+        ws = ctx.saved_tensors[2:]
+        B, F, A = h.shape
+        dev = h.device
+        need = ctx.needs_input_grad
+        dy = dy.float().contiguous()
+
+        def new(want, *shape):
+            return torch.empty(shape, dtype=torch.float32, device=dev) if want else None
+        dh, dh0 = new(need[0], B, F, A), new(need[1], B, F, A)
+        dw = [new(need[2 + i], *ws[i].shape) for i in range(8)]
+        ws_bytes, wsp = 0, None
+        if any(t is not None for t in dw):
+            ws_bytes = lib.rbx_fignn_step_bwd_workspace_size(B, F, A)
+            wsp = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        if wsp is not None or dh is not None or dh0 is not None:
+            check(_timed(("fignn_step_bwd", B, F, A),
+                         lambda: lib.rbx_fignn_step_bwd(_ptr(dy), _ptr(h), _ptr(h0), *[_ptr(t) for t in ws], B, F, A, _lib.RBX_F32,
+                                                        _ptr(dh), _ptr(dh0), *[_ptr(t) for t in dw], _ptr(wsp), ws_bytes,
+                                                        _stream())))
+        if dw[0] is not None:
+            dw[0] = dw[0].view(ctx.w_attn_shape)
+        return (dh, dh0) + tuple(dw) + (None,)
+
+
+def fignn_step(h, h0, w_attn, W_out, W_in, bias_p, w_ih, w_hh, b_ih, b_hh, want_graph=False):
+    """One message-passing layer of FiGNN as one autograd node over rbx_fignn_step_fwd / _bwd (see ``fignn_step_torch`` for
+    the formulas and the arguments).  Returns ``(h' [B, F, A], g [B, F, F] or None)``; ``g`` is the graph the reference keeps
+    as ``self.graph`` and carries no gradient.  ``h`` and ``h0`` may be the same tensor (the first layer): their gradients are
+    separate outputs that autograd adds.  Nothing is saved but the inputs.  CPU or non-float32 tensors, an empty batch, what
+    ``fignn_step_supported`` refuses, more than ``config.fignn_fields`` fields or a width above ``config.fignn_dim``, a
+    non-contiguous ``h`` or ``h0`` and ``config.fignn_fused = False`` run ``fignn_step_torch``."""
+    if h.dim() != 3 or h0.shape != h.shape:
+        raise RuntimeError("fignn_step: h %s and h0 %s are not the same [B, F, A]" % (tuple(h.shape), tuple(h0.shape)))
+    B, F, A = h.shape
+    if (w_attn.numel() != 2 * A or tuple(W_out.shape) != (F, A, A) or tuple(W_in.shape) != (F, A, A)
+            or tuple(bias_p.shape) != (A,) or tuple(w_ih.shape) != (3 * A, A) or tuple(w_hh.shape) != (3 * A, A)
+            or tuple(b_ih.shape) != (3 * A,) or tuple(b_hh.shape) != (3 * A,)):
+        raise RuntimeError("fignn_step: h %s and the weights do not fit" % (tuple(h.shape),))
+    weights = (w_attn, W_out, W_in, bias_p, w_ih, w_hh, b_ih, b_hh)
+    if not _fignn_fused_ok(h, h0, weights):
+        return fignn_step_torch(h, h0, *weights, want_graph=want_graph)
+    return _FignnStep.apply(h, h0, *weights, bool(want_graph))

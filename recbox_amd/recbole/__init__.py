@@ -1,8 +1,10 @@
 """Mirrors of the RecBole pieces the project serves (third_party/recbole): ``layers`` (``AttLayer``, ``MLPLayers``,
-``activation_layer``, ``Dice``, ``SequenceAttLayer``), in ``context_aware`` the interaction part of AFM over ``ops.afm_pool``
-and that of AutoInt (``AutoIntInteraction``, also exported here) over ``ops.field_attn``, and in ``sequential`` the layers of DIEN (``AGRUCell``, ``AUGRUCell``, ``DynamicRNN``, ``InterestExtractorNetwork``,
-``InterestEvolvingLayer``) over ``ops.att_gru`` / ``ops.gru``.  RecBole's ``(config, dataset)`` constructors, its recommender
-base classes, ``ContextSeqEmbLayer``, trainer and ``calculate_loss`` are not mirrored, and ``compat.install()`` registers
-nothing under ``recbole.*``: the trainable models (``AFM``, ``DIEN``) are registered with the rechub ranking zoo."""
+``activation_layer``, ``Dice``, ``SequenceAttLayer``); in ``context_aware`` the interaction part of AFM over ``ops.afm_pool``,
+that of AutoInt (``AutoIntInteraction``, also exported here) over ``ops.field_attn`` and that of FiGNN (``GraphLayer``,
+``FiGNNInteraction``, also exported here) over ``ops.field_attn`` and ``ops.fignn_step``; in ``sequential`` the layers of DIEN
+(``AGRUCell``, ``AUGRUCell``, ``DynamicRNN``, ``InterestExtractorNetwork``, ``InterestEvolvingLayer``) over ``ops.att_gru`` /
+``ops.gru``.  RecBole's ``(config, dataset)`` constructors, its recommender base classes, ``ContextSeqEmbLayer``, trainer and
+``calculate_loss`` are not mirrored, and ``compat.install()`` registers nothing under ``recbole.*``: the trainable models
+(``AFM``, ``AutoInt``, ``FiGNN``, ``DIEN``) are registered with the rechub ranking zoo."""
 from . import context_aware, layers, sequential  # noqa: F401
-from .context_aware import AutoIntInteraction  # noqa: F401
+from .context_aware import AutoIntInteraction, FiGNNInteraction, GraphLayer  # noqa: F401

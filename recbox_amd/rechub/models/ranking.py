@@ -510,3 +510,31 @@ class AutoInt(torch.nn.Module):
         embed_x = _embed(self.embedding, x, self.features, False)          # [B, F, D]
         y = _lr(self.linear, embed_x.flatten(start_dim=1)) + self.interaction(embed_x)
         return torch.sigmoid(y.squeeze(1))
+
+
+# ---- FiGNN (RecBole's FiGNN in the rechub style) ------------------------------------------------------------------------------
+class FiGNN(torch.nn.Module):
+    """FiGNN as a trainable model in the style of this zoo: ``EmbeddingLayer`` over ``features`` (unshared ``SparseFeature``s of
+    one ``embed_dim``) and ``recbole.context_aware.FiGNNInteraction`` (one ``ops.field_attn`` launch, then one
+    ``ops.fignn_step`` launch each way per message-passing layer, then the attentional scoring); the output is
+    ``sigmoid(fignn_layer(embeddings))`` [B], as the reference's ``predict``.  ``interaction.state_dict()`` has RecBole's FiGNN
+    keys.  RecBole's ``FiGNN(config, dataset)`` constructor, its ``ContextRecommender`` base and ``calculate_loss`` are NOT
+    mirrored."""
+
+    def __init__(self, features, attention_size=16, n_layers=3, num_heads=2, hidden_dropout=0.2, attn_dropout=0.2):
+        super(FiGNN, self).__init__()
+        from ...recbole.context_aware import FiGNNInteraction
+        dims = set(fea.embed_dim for fea in features)
+        if len(dims) != 1 or len(features) < 2:
+            raise ValueError("FiGNN: at least two features of one embed_dim (got dims %s)" % sorted(dims))
+        self.features = features
+        self.embedding = EmbeddingLayer(features)
+        self.num_fields = len(features)
+        self.embed_dim = dims.pop()
+        self.interaction = FiGNNInteraction(self.num_fields, self.embed_dim, attention_size, n_layers, num_heads, hidden_dropout,
+                                            attn_dropout)
+
+    def forward(self, x):
+        from .multi_task import _embed
+        embed_x = _embed(self.embedding, x, self.features, False)          # [B, F, D]
+        return torch.sigmoid(self.interaction(embed_x).squeeze(1))
