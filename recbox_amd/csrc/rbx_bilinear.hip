@@ -641,9 +641,14 @@ static int bl_check(const char* what, const float* x, int64_t xsb, int64_t xsf, 
   return RBX_OK;
 }
 
+// above 64 KiB of dynamic LDS a kernel has to be opted in; a refusal is reported here, not by the launch that would follow
 template <typename K>
-static void bl_allow_lds(K kernel, size_t lds) {
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+static int bl_allow_lds(const char* what, K kernel, size_t lds) {
+  if (lds <= 64 * 1024) return RBX_OK;
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+  if (e == hipSuccess) return RBX_OK;
+  (void)hipGetLastError();
+  return fail(RBX_ERR_LAUNCH, "%s: the opt-in to %zu bytes of dynamic LDS failed: %s", what, lds, hipGetErrorString(e));
 }
 
 }  // namespace rbx
@@ -728,7 +733,10 @@ extern "C" int rbx_bilinear_pairs_fwd(const float* d_x, int64_t x_stride_b, int6
   const dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>((P + a.ppb - 1) / a.ppb)), block(kBlBlock);
   const size_t lds = bl_fwd_lds(fields, dim);
   hipStream_t s = as_stream(stream);
-#define RBX_BL_FWD(DD) bl_allow_lds(bl_fwd_kernel<DD>, lds); hipLaunchKernelGGL(bl_fwd_kernel<DD>, grid, block, lds, s, a)
+  int rc_lds = RBX_OK;
+#define RBX_BL_FWD(DD)                                                                      \
+  if ((rc_lds = bl_allow_lds("bilinear_pairs_fwd", bl_fwd_kernel<DD>, lds)) == RBX_OK)      \
+  hipLaunchKernelGGL(bl_fwd_kernel<DD>, grid, block, lds, s, a)
   switch (dim) {
     case 4: RBX_BL_FWD(4); break;
     case 8: RBX_BL_FWD(8); break;
@@ -736,6 +744,7 @@ extern "C" int rbx_bilinear_pairs_fwd(const float* d_x, int64_t x_stride_b, int6
     default: RBX_BL_FWD(32); break;
   }
 #undef RBX_BL_FWD
+  if (rc_lds != RBX_OK) return rc_lds;
   return check_launch("bilinear_pairs_fwd");
 }
 
@@ -772,10 +781,12 @@ extern "C" int rbx_bilinear_pairs_bwd(const float* d_dout, int64_t dout_stride_b
   const dim3 grid_tail(dim * dim / 16, bl_matrices(kind, fields));
   const size_t lds = bl_dx_lds(fields, dim);
   hipStream_t s = as_stream(stream);
-#define RBX_BL_BWD(DD)                                                       \
-  bl_allow_lds(bl_dx_kernel<DD>, lds);                                       \
-  hipLaunchKernelGGL(bl_dx_kernel<DD>, grid_dx, block, lds, s, a);           \
-  hipLaunchKernelGGL(bl_dw_kernel<DD>, grid_dw, block, 0, s, a)
+  int rc_lds = RBX_OK;
+#define RBX_BL_BWD(DD)                                                                          \
+  if ((rc_lds = bl_allow_lds("bilinear_pairs_bwd", bl_dx_kernel<DD>, lds)) == RBX_OK) {         \
+    hipLaunchKernelGGL(bl_dx_kernel<DD>, grid_dx, block, lds, s, a);                            \
+    hipLaunchKernelGGL(bl_dw_kernel<DD>, grid_dw, block, 0, s, a);                              \
+  }
   switch (dim) {
     case 4: RBX_BL_BWD(4); break;
     case 8: RBX_BL_BWD(8); break;
@@ -783,6 +794,7 @@ extern "C" int rbx_bilinear_pairs_bwd(const float* d_dout, int64_t dout_stride_b
     default: RBX_BL_BWD(32); break;
   }
 #undef RBX_BL_BWD
+  if (rc_lds != RBX_OK) return rc_lds;
   const int rc2 = check_launch("bilinear_pairs_bwd");
   if (rc2 != RBX_OK) return rc2;
   hipLaunchKernelGGL(bl_dw_tail_kernel, grid_tail, dim3(256), 0, s, a.part, chunks, fields, P, dim, kind, a.transposed, d_dw);

@@ -340,9 +340,14 @@ static size_t cm_part_floats(int n, int E, int r) {
   return m * kCmChunks;
 }
 
+// above 64 KiB of dynamic LDS a kernel has to be opted in; a refusal is reported here, not by the launch that would follow
 template <typename K>
-static void cm_allow_lds(K kernel, size_t lds) {
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+static int cm_allow_lds(const char* what, K kernel, size_t lds) {
+  if (lds <= 64 * 1024) return RBX_OK;
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+  if (e == hipSuccess) return RBX_OK;
+  (void)hipGetLastError();
+  return fail(RBX_ERR_LAUNCH, "%s: the opt-in to %zu bytes of dynamic LDS failed: %s", what, lds, hipGetErrorString(e));
 }
 
 static int cm_log2(int r) {
@@ -392,7 +397,8 @@ extern "C" int rbx_crossmix_fwd(const float* d_x0, int64_t x0_stride, const floa
   a.x0 = d_x0; a.x0s = x0_stride; a.xl = d_xl; a.xls = xl_stride; a.U = d_u; a.V = d_v; a.C = d_c; a.G = d_g; a.b = d_b;
   a.out = d_out; a.os = out_stride; a.B = batch; a.n = n; a.E = experts; a.r = rank; a.rsh = cm_log2(rank);
   const size_t lds = cm_fwd_lds(n, experts * rank);
-  cm_allow_lds(cm_fwd_kernel, lds);
+  const int rc_lds = cm_allow_lds("crossmix_fwd", cm_fwd_kernel, lds);
+  if (rc_lds != RBX_OK) return rc_lds;
   hipLaunchKernelGGL(cm_fwd_kernel, dim3(static_cast<unsigned>((batch + kCmTile - 1) / kCmTile)), dim3(kCmBlock), lds,
                      as_stream(stream), a);
   return check_launch("crossmix_fwd");
@@ -432,7 +438,8 @@ extern "C" int rbx_crossmix_bwd(const float* d_dout, int64_t dout_stride, const 
   a.B = batch; a.n = n; a.E = E; a.r = r; a.rsh = cm_log2(r); a.acc = accumulate != 0;
   hipStream_t s = as_stream(stream);
   const size_t lds = cm_bwd_lds(n, ER);
-  cm_allow_lds(cm_bwd_kernel, lds);
+  const int rc_lds = cm_allow_lds("crossmix_bwd", cm_bwd_kernel, lds);
+  if (rc_lds != RBX_OK) return rc_lds;
   hipLaunchKernelGGL(cm_bwd_kernel, dim3(static_cast<unsigned>((batch + kCmTile - 1) / kCmTile)), dim3(kCmBlock), lds, s, a);
   int rc2 = check_launch("crossmix_bwd");
   if (rc2 != RBX_OK) return rc2;

@@ -13,6 +13,7 @@ import torch
 
 import crossmix64
 import fp32_bar
+import test_gpu_crossmix_forms as forms
 from conftest import Fixture
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -47,6 +48,31 @@ def test_seeds_reach_the_saturated_branch_of_tanh_and_mostly_stay_out_of_it():
         a = crossmix64.tanh_inputs(crossmix64.make_case(11, B, n, E, r, L)).abs()
         frac = float((a > 3).double().mean())
         assert 0.0 < frac < 0.5, (B, n, E, r, L, frac)
+
+
+def test_the_form_cases_cover_every_form_of_the_launch_geometry():
+    forms.check_the_list_covers_every_form()
+    reached = 0
+    for name in forms.CASES:
+        a = crossmix64.tanh_inputs(forms.make(name)).abs()
+        assert bool(torch.isfinite(a).all()) and float((a > 3).double().mean()) < 0.5, name
+        reached += int((a > 3).sum())
+    assert reached > 0
+
+
+@pytest.mark.parametrize("name", list(forms.CASES))
+def test_a_form_case_reaches_its_form_and_its_references_hold_the_bar(name):
+    """What tests/test_gpu_crossmix_forms.py sends to the GPU, judged here first: the case selects the launch geometry its table
+    names, the library takes it, the fp32 restatement is finite and under the bar, and another fp32 summation order -- the
+    composition on the CPU -- holds the same bar against float64."""
+    from recbox_amd import ops
+    forms.check_forms(name)
+    case, (want, ref32) = forms._case(name)
+    got = crossmix64.run(ops.cross_mix_torch, case, "cpu")
+    for key in crossmix64.names(forms.CASES[name][0][4]):
+        assert bool(torch.isfinite(ref32[key]).all()), key
+        fp32_bar.assert_bar("%s ref32 %s" % (key, name), ref32[key], want[key], ref32[key])
+        fp32_bar.assert_bar("%s composition %s" % (key, name), got[key], want[key], ref32[key])
 
 
 @pytest.mark.parametrize("which", crossmix64.MODELS)

@@ -13,6 +13,7 @@ import torch
 
 import fibinet64
 import fp32_bar
+import test_gpu_fibinet_forms as forms
 from conftest import Fixture
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -57,6 +58,28 @@ def test_seeds_stay_away_from_the_kinks_and_the_gate_opens_and_closes():
             a = fibinet64.gate64(case["x"], case["w1"], case["w2"], "relu")[0]
             closed, opened = closed or bool((a == 0).any()), opened or bool((a > 0).any())
         assert closed and opened, F
+
+
+def test_the_form_cases_cover_every_form_of_the_launch_geometry():
+    forms.check_the_list_covers_every_form()
+
+
+@pytest.mark.parametrize("name", list(forms.CASES))
+def test_a_form_case_reaches_its_form_and_its_references_hold_the_bar(name):
+    """What tests/test_gpu_fibinet_forms.py sends to the GPU, judged here first: the case selects the launch geometry its table
+    names (the chunk count and the gate's grid read from the library), its seed keeps every ReLU of the gate KINK away from
+    zero, the fp32 restatement is finite and under the bar, and another fp32 summation order -- the composition on the CPU --
+    holds the same bar against float64."""
+    from recbox_amd import ops
+    forms.check_forms(name)
+    case, (want, ref32) = forms._case(name)
+    ws = forms.CASES[name][0][6]
+    assert fibinet64.kink_margin(case["x"], case["w1"], case["w2"], case["act"]) >= fibinet64.KINK
+    got = fibinet64.run(ops.senet_gate_torch, ops.bilinear_pairs_torch, case, "cpu", ws)
+    for key in fibinet64.NAMES:
+        assert bool(torch.isfinite(ref32[key]).all()), key
+        fp32_bar.assert_bar("%s ref32 %s" % (key, name), ref32[key], want[key], ref32[key])
+        fp32_bar.assert_bar("%s composition %s" % (key, name), got[key], want[key], ref32[key])
 
 
 @pytest.mark.parametrize("kind", fibinet64.KINDS)
