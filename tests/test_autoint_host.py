@@ -6,6 +6,8 @@ import pytest
 import torch
 
 import fieldattn64 as fa
+import fp32_bar
+import test_gpu_autoint_forms as forms
 from conftest import Fixture
 
 TOL = 1e-4
@@ -95,6 +97,50 @@ def test_composition_against_float64(res, relu, bias):
             assert tuple(got[n].shape) == tuple(want[n].shape), n
             scale = float(want[n].abs().max())
             _close(got[n], want[n], n, 2e-5 * max(scale, 1.0))
+
+
+def test_the_form_cases_cover_every_form_of_the_launch_geometry():
+    forms.check_the_list_covers_every_form()
+
+
+def test_the_restatement_gives_the_wavefront_counts_the_form_list_was_chosen_from():
+    """``forms`` restates fa_waves: three backward wavefronts exactly at FP 48 with E 12 and at FP 32 with E 24 or 28, and the
+    shapes of tests/test_gpu_autoint.py reach backward counts of 4, 2 and 1 only; the three shapes closest to kFaLdsCap."""
+    k = forms.constants()
+    three = {(FP, E) for FP in (16, 32, 48) for E in range(4, 33, 4) if forms.forms(37, FP, E, k)["nw_bwd"] == 3}
+    assert three == {(48, 12), (32, 24), (32, 28)}
+    old = [(2, 4), (3, 8), (5, 12), (7, 16), (16, 16), (17, 16), (23, 32), (26, 16), (39, 16), (18, 32), (26, 32), (39, 32), (48, 32)]
+    assert {forms.forms(37, F, E, k)["nw_bwd"] for F, E in old} == {4, 2, 1}
+    for (FP, E), lds in forms.NEAR_CAP.items():
+        assert forms.forms(37, FP, E, k)["bwd_lds"] == lds
+    top = sorted((forms.forms(37, FP, E, k)["bwd_lds"] for FP in (16, 32, 48) for E in range(4, 33, 4)), reverse=True)
+    assert top[:3] == sorted(forms.NEAR_CAP.values(), reverse=True) and top[0] <= k["kFaLdsCap"]
+    assert forms.FORMS == [(False, False, True), (True, True, True), (True, False, False), (False, True, False)]
+
+
+@pytest.mark.parametrize("name", list(forms.CASES))
+def test_a_form_case_reaches_its_form_and_its_references_hold_the_bar(name):
+    """What tests/test_gpu_autoint_forms.py sends to the GPU, judged here first: the case selects the launch geometry its table
+    line names (the workspace rows read from the library), ``make_case`` finds a seed for it, the fp32 composition is finite and
+    under the bar, and another fp32 order of the forward -- the restatement's own formulas in fp32 -- holds the same bar."""
+    forms.check_forms(name)
+    case = forms.make(name)
+    want, ref32 = forms.refs(name)
+    for n in forms.ALL:
+        if want[n] is None:
+            assert ref32[n] is None, n
+            continue
+        assert bool(torch.isfinite(ref32[n]).all()), n
+        fp32_bar.assert_bar("%s ref32 %s" % (n, name), ref32[n], want[n], ref32[n])
+    z, p = fa.forward64(case, dtype=torch.float32)[:2]
+    fp32_bar.assert_bar("y restated-fp32 %s" % name, torch.relu(z) if case["relu"] else z, want["y"], ref32["y"])
+    fp32_bar.assert_bar("attn restated-fp32 %s" % name, p, want["attn"], ref32["attn"])
+
+
+@pytest.mark.parametrize("B,F,E,h", forms.DROP)
+def test_the_dropout_form_cases_draw_a_seed(B, F, E, h):
+    case = fa.make_case(B, F, E, h, True, True, True, 0.25)
+    assert case["p"] == 0.25 and case["relu"] and forms.forms(B, F, E)["rows"] < B
 
 
 def test_composition_under_a_keep_mask_against_float64():

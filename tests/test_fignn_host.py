@@ -8,6 +8,7 @@ import torch
 
 import fignn64 as fg
 import fp32_bar
+import test_gpu_fignn_forms as forms
 from conftest import Fixture
 
 TOL = 1e-4
@@ -39,6 +40,48 @@ def test_composition_against_float64(B, F, A, same):
             assert got[n] is None, n
         else:
             fp32_bar.assert_bar("%s F%d A%d" % (n, F, A), got[n], want[n], ref32[n])
+
+
+def test_the_form_cases_cover_every_form_of_the_launch_geometry():
+    forms.check_the_list_covers_every_form()
+
+
+def test_the_restatement_gives_the_ranges_the_kernel_file_quotes():
+    """``forms`` restates fg_tile / fg_waves: it has to give the 16 -> 8 switches the .hip file's header quotes (46 x 20, 39 x 24,
+    34 x 28, 30 x 32) and the ranges the form list was chosen from; the shapes of tests/test_gpu_fignn.py reach the forward with
+    4 wavefronts only, and a lone backward wavefront never."""
+    first8, combos = forms.header_figures()
+    assert first8 == {20: 46, 24: 39, 28: 34, 32: 30}
+    assert set(combos.values()) == forms.COMBOS
+
+    def fields(A, pred):
+        return [F for F in range(2, 49) if (F, A) in combos and pred(combos[(F, A)])]
+    assert fields(16, lambda c: c[1] == 2) == [45, 46, 47, 48] and fields(20, lambda c: c[1] == 2) == [38, 39, 40, 41, 42, 43]
+    assert fields(20, lambda c: c[1] == 1) == [44, 45] and fields(24, lambda c: c[1] == 1) == [38]
+    lone = lambda c: c[0] == 16 and c[2] == 1
+    assert fields(32, lone) == [26, 27, 28, 29] and fields(28, lone) == [30, 31, 32, 33] and fields(20, lone) == [42, 43, 44, 45]
+    assert combos[(29, 32)] == (16, 4, 1)
+    old = [(2, 4), (3, 8), (5, 12), (7, 16), (16, 16), (17, 16), (26, 16), (39, 16), (23, 32), (30, 32), (39, 32), (48, 32)]
+    assert {combos[s] for s in old} == {(16, 4, 4), (16, 4, 2), (8, 4, 4), (8, 4, 2)}
+
+
+@pytest.mark.parametrize("name", list(forms.CASES))
+def test_a_form_case_reaches_its_form_and_its_references_hold_the_bar(name):
+    """What tests/test_gpu_fignn_forms.py sends to the GPU, judged here first: the case selects the launch geometry its table
+    line names (the workspace rows read from the library), ``make_case`` finds a seed for it, the fp32 restatement is finite and
+    under the bar, and another fp32 summation order -- the composition on the CPU -- holds the same bar against float64."""
+    from recbox_amd import ops
+    forms.check_forms(name)
+    case = forms.make(name)
+    want, ref32 = forms.refs(name)
+    got = fg.run(ops.fignn_step_torch, case, "cpu")
+    for n in fg.NAMES:
+        if want[n] is None:
+            assert ref32[n] is None and got[n] is None, n
+            continue
+        assert bool(torch.isfinite(ref32[n]).all()), n
+        fp32_bar.assert_bar("%s ref32 %s" % (n, name), ref32[n], want[n], ref32[n])
+        fp32_bar.assert_bar("%s composition %s" % (n, name), got[n], want[n], ref32[n])
 
 
 def test_cpu_tensors_and_empty_batches_run_the_composition():
