@@ -28,14 +28,10 @@
 
 namespace rbx {
 
-typedef float aa_f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kAaTile = 16;                 // positions per tile = rows of the MFMA
 constexpr int kAaPad = kAaTile + 1;         // row stride of the staged x tile
 constexpr int kAaMin = 4, kAaMax = 128;     // D and H
 constexpr int kAaMaxGrid = 2048;            // workgroups of a launch = rows of the dv workspace
-
-__device__ __forceinline__ float aa_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 
 __device__ __forceinline__ bool aa_mask_on(const void* p, long long idx, int dt) {
   if (p == nullptr) return true;
@@ -48,11 +44,6 @@ __device__ __forceinline__ bool aa_mask_on(const void* p, long long idx, int dt)
 }
 
 // sum over the 16 lanes that share a quad (the 16 units / columns of a wave)
-__device__ __forceinline__ float aa_sum16(float v) {
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // rows l0 .. l0 + 15 of x[b] into xs[c * kAaPad + row]; zeros beyond L
 __device__ __forceinline__ void aa_stage(const float* __restrict__ xb, const long long xs_l, const int l0, const int L,
@@ -92,13 +83,13 @@ __global__ __launch_bounds__(16 * KS) void addattn_fwd_kernel(
       aa_stage(xb, xs_l, l0, L, D, xs);
       __syncthreads();
       if (wv < nwh) {
-        aa_f32x4 acc = {cj, cj, cj, cj};
+        f32x4 acc = {cj, cj, cj, cj};
 #pragma unroll
         for (int s = 0; s < KS; ++s)
           if (s < nkd) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(xs[(4 * s + quad) * kAaPad + col], wf[s], acc, 0, 0, 0);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float t = aa_sum16(vj * aa_sigmoid(acc[r]));
+          const float t = group_sum<16, kWave>(vj * sigmoidf_fast(acc[r]));
           if (col == 0) qp[wv][quad * 4 + r] = t;
         }
       }
@@ -112,7 +103,7 @@ __global__ __launch_bounds__(16 * KS) void addattn_fwd_kernel(
       }
     }
     if (wv == 0) {
-      esum = aa_sum16(esum);
+      esum = group_sum<16, kWave>(esum);
       if (lane == 0) den = fmaxf(esum, eps);
     }
     __syncthreads();                       // den, and every e of this sample (written by this workgroup)
@@ -173,7 +164,7 @@ __global__ __launch_bounds__(16 * KS) void addattn_bwd_kernel(
       float p = 0.f;
       if (l < L)
         for (int c = col; c < D; c += 16) p = fma_rn(dd[c], xb[l * xs_l + c], p);
-      gpart = fma_rn(l < L ? ab[l] : 0.f, aa_sum16(p), gpart);
+      gpart = fma_rn(l < L ? ab[l] : 0.f, group_sum<16, kWave>(p), gpart);
     }
     gpart += __shfl_xor(gpart, 16, 64);
     gpart += __shfl_xor(gpart, 32, 64);
@@ -190,7 +181,7 @@ __global__ __launch_bounds__(16 * KS) void addattn_bwd_kernel(
 #pragma unroll
       for (int r = 0; r < 4; ++r) al[r] = (l0 + quad * 4 + r < L) ? ab[l0 + quad * 4 + r] : 0.f;
       if (wv < nwh) {
-        aa_f32x4 acc = {cj, cj, cj, cj};
+        f32x4 acc = {cj, cj, cj, cj};
 #pragma unroll
         for (int s = 0; s < KS; ++s)
           if (s < nkd) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(xs[(4 * s + quad) * kAaPad + col], wf[s], acc, 0, 0, 0);
@@ -200,8 +191,8 @@ __global__ __launch_bounds__(16 * KS) void addattn_bwd_kernel(
           const int row = quad * 4 + r;
           float p = 0.f;                   // g_l = dout . x_l: this lane's columns col, col + 16, ..., then the 16 lanes
           for (int c = col; c < D; c += 16) p = fma_rn(dd[c], xs[c * kAaPad + row], p);
-          const float dq = al[r] * (aa_sum16(p) - G);
-          const float sg = aa_sigmoid(acc[r]);
+          const float dq = al[r] * (group_sum<16, kWave>(p) - G);
+          const float sg = sigmoidf_fast(acc[r]);
           dpr[r] = jok ? dq * vj * sg * (1.f - sg) : 0.f;
           dc_acc += dpr[r];
           dv_acc += jok ? dq * sg : 0.f;
@@ -212,7 +203,7 @@ __global__ __launch_bounds__(16 * KS) void addattn_bwd_kernel(
       __syncthreads();                     // dpre of the tile is in dp; nobody reads xs any more
       if (wv < nwd) {
         const float dj = cok ? dd[j] : 0.f;
-        aa_f32x4 acc = {al[0] * dj, al[1] * dj, al[2] * dj, al[3] * dj};
+        f32x4 acc = {al[0] * dj, al[1] * dj, al[2] * dj, al[3] * dj};
 #pragma unroll
         for (int s = 0; s < KS; ++s)
           if (s < nkh) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(dp[64 * s + lane], wt[s], acc, 0, 0, 0);
@@ -250,8 +241,6 @@ __global__ __launch_bounds__(256) void addattn_dv_kernel(const float* __restrict
   if (r == 0 && h < H) dv[h] = sm[0][c];
 }
 
-static bool aa_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 static unsigned aa_grid(int64_t batch) { return static_cast<unsigned>(batch < kAaMaxGrid ? batch : kAaMaxGrid); }
 
 static int aa_check(const char* what, int64_t batch, int32_t seq_len, int32_t dim, int32_t hidden, int32_t dtype,
@@ -263,7 +252,7 @@ static int aa_check(const char* what, int64_t batch, int32_t seq_len, int32_t di
   if (dtype != RBX_F32) return fail(RBX_ERR_UNSUPPORTED, "%s: tensor dtype code %d (float32 only)", what, dtype);
   if (mask != nullptr && mask_dtype != RBX_I32 && mask_dtype != RBX_I64 && mask_dtype != RBX_F32 && mask_dtype != RBX_MASK_U8)
     return fail(RBX_ERR_UNSUPPORTED, "%s: mask_dtype=%d", what, mask_dtype);
-  if (x != nullptr && (!aa_aligned(x) || (xs_b & 3) != 0 || (xs_l & 3) != 0 || xs_l < dim || xs_b < 0))
+  if (x != nullptr && (!aligned16(x) || (xs_b & 3) != 0 || (xs_l & 3) != 0 || xs_l < dim || xs_b < 0))
     return fail(RBX_ERR_UNSUPPORTED, "%s: x must be 16-byte aligned with strides that are multiples of 4 floats", what);
   return RBX_OK;
 }
@@ -317,7 +306,7 @@ extern "C" int rbx_addattn_bwd(const float* d_dout, int64_t dout_stride_b, const
   if (batch == 0) return RBX_OK;
   if (!d_dout || !d_x || !d_w || !d_v || !d_alpha || !d_dx || !d_dctx || !d_dv)
     return fail(RBX_ERR_INVALID, "addattn_bwd: NULL tensor");
-  if (!aa_aligned(d_dout) || (dout_stride_b & 3) != 0 || dout_stride_b < dim)
+  if (!aligned16(d_dout) || (dout_stride_b & 3) != 0 || dout_stride_b < dim)
     return fail(RBX_ERR_UNSUPPORTED, "addattn_bwd: d_out must be 16-byte aligned with a row stride that is a multiple of 4 floats");
   if (d_workspace == nullptr || workspace_bytes < rbx_addattn_bwd_workspace_size(batch, hidden))
     return fail(RBX_ERR_WORKSPACE, "addattn_bwd: workspace too small");

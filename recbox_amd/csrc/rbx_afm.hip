@@ -24,10 +24,9 @@
 // No atomics, every sum in a fixed order: two runs give the same bits.  No host read-back, nothing allocated; everything on
 // the caller's stream.  Nothing of B P D or B P A elements exists.
 #include "rbx_internal.h"
+#include "rbx_tile16.h"
 
 namespace rbx {
-
-typedef float af_f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kAfMinF = 2, kAfMaxF = 39;
 constexpr int kAfMinD = 4, kAfMaxD = 64;
@@ -56,16 +55,15 @@ struct AfmArgs {
 
 // unit / column blocks the kernels are instantiated for: 1, 2 or 4 blocks of 16
 static __host__ __device__ inline int af_blocks(int n) { return n <= 16 ? 1 : (n <= 32 ? 2 : 4); }
-static __host__ __device__ inline int af_ppad(int P) { return (P + kAfTile - 1) & ~(kAfTile - 1); }
 // row stride of W [A, D] in LDS: the four quads of a B operand read rows 4 s + quad, 16 floats each, in distinct banks
 static __host__ __device__ inline int af_ldd(int nd) { return (nd & 1) ? 16 * nd : 16 * nd + 16; }
-static __host__ __device__ inline int af_fwd_wave_floats(int F, int D) { return F * D + af_ppad(F * (F - 1) / 2) + 64; }
+static __host__ __device__ inline int af_fwd_wave_floats(int F, int D) { return F * D + pad16(F * (F - 1) / 2) + 64; }
 static __host__ __device__ inline int af_bwd_wave_floats(int F, int D, int na, int nd) {
   return 2 * F * D + 16 * 16 * (na > nd ? na : nd) + 64;
 }
-static __host__ __device__ inline int af_fwd_shared_floats(int F) { return af_ppad(F * (F - 1) / 2) / 2; }
+static __host__ __device__ inline int af_fwd_shared_floats(int F) { return pad16(F * (F - 1) / 2) / 2; }
 static __host__ __device__ inline int af_bwd_shared_floats(int F, int na, int nd) {
-  return af_ppad(F * (F - 1) / 2) / 2 + 16 * na * af_ldd(nd);
+  return pad16(F * (F - 1) / 2) / 2 + 16 * na * af_ldd(nd);
 }
 static int af_waves(int shared_floats, int wave_floats) {
   for (int nw = 4; nw > 1; nw >>= 1)
@@ -82,11 +80,6 @@ static unsigned af_grid(int64_t batch, int nw) {
 }
 
 // sum over the 16 lanes that share a quad
-__device__ __forceinline__ float af_sum16(float v) {
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // the pair table: entry k = i | j << 8 of pair k in row-major order, 0 beyond P
 __device__ __forceinline__ void af_pairs(unsigned short* pij, const int F, const int P, const int ppad) {
@@ -126,14 +119,14 @@ __device__ __forceinline__ void af_load_w(const AfmArgs& g, const int col, const
 template <int NA, int KS>
 __device__ __forceinline__ void af_tile_logits(const float* xs, const unsigned short* pij, const int t, const int P, const int D,
                                                const int col, const int quad, const float (&wf)[NA][KS], const float (&hr)[NA],
-                                               af_f32x4 (&acc)[NA], float (&lg)[4]) {
+                                               f32x4 (&acc)[NA], float (&lg)[4]) {
   const int k = kAfTile * t + col, nkd = D >> 2;
   const unsigned ij = pij[k];
   const float* xi = xs + (ij & 255u) * D + quad;
   const float* xj = xs + (ij >> 8) * D + quad;
   const bool valid = k < P;
 #pragma unroll
-  for (int n = 0; n < NA; ++n) acc[n] = af_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int n = 0; n < NA; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int s = 0; s < KS; ++s) {
     if (s < nkd) {
@@ -147,7 +140,7 @@ __device__ __forceinline__ void af_tile_logits(const float* xs, const unsigned s
     float v = 0.f;
 #pragma unroll
     for (int n = 0; n < NA; ++n) v = fma_rn(hr[n], fmaxf(acc[n][r], 0.f), v);
-    lg[r] = af_sum16(v);
+    lg[r] = group_sum<16, kWave>(v);
   }
 }
 
@@ -157,7 +150,7 @@ template <int NA, int ND>
 __global__ __launch_bounds__(256) void afm_fwd_kernel(const AfmArgs g) {
   constexpr int KS = 4 * ND;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, col = lane & 15, quad = lane >> 4, nw = blockDim.x >> 6;
-  const int F = g.F, D = g.D, P = g.P, FD = F * D, ppad = af_ppad(P);
+  const int F = g.F, D = g.D, P = g.P, FD = F * D, ppad = pad16(P);
   unsigned short* pij = reinterpret_cast<unsigned short*>(af_smem);
   float* xs = af_smem + af_fwd_shared_floats(F) + wv * af_fwd_wave_floats(F, D);   // [F, D]
   float* lgs = xs + FD;                                                            // [ppad] logits, then e, then a
@@ -176,7 +169,7 @@ __global__ __launch_bounds__(256) void afm_fwd_kernel(const AfmArgs g) {
     __syncthreads();                       // xs (and, the first time, the pair table)
     float m = -INFINITY;
     for (int t = 0; t < ntile; ++t) {
-      af_f32x4 acc[NA];
+      f32x4 acc[NA];
       float lg[4];
       af_tile_logits<NA, KS>(xs, pij, t, P, D, col, quad, wf, hr, acc, lg);
       const int k0 = kAfTile * t + 4 * quad;
@@ -227,7 +220,7 @@ template <int NA, int ND>
 __global__ __launch_bounds__(256) void afm_bwd_kernel(const AfmArgs g) {
   constexpr int KS = 4 * ND, DP = 16 * ND, MX = 16 * (NA > ND ? NA : ND);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, col = lane & 15, quad = lane >> 4, nw = blockDim.x >> 6;
-  const int F = g.F, D = g.D, A = g.A, P = g.P, FD = F * D, ppad = af_ppad(P), ldd = af_ldd(ND), nka = (A + 3) >> 2;
+  const int F = g.F, D = g.D, A = g.A, P = g.P, FD = F * D, ppad = pad16(P), ldd = af_ldd(ND), nka = (A + 3) >> 2;
   unsigned short* pij = reinterpret_cast<unsigned short*>(af_smem);
   float* wl = af_smem + ppad / 2;                                                  // W [16 NA][ldd], zero padded
   float* xs = af_smem + af_bwd_shared_floats(F, NA, ND) + wv * af_bwd_wave_floats(F, D, NA, ND);   // [F, D]
@@ -243,13 +236,13 @@ __global__ __launch_bounds__(256) void afm_bwd_kernel(const AfmArgs g) {
   af_load_w<NA, KS>(g, col, quad, wf, hr);
   const int ntile = ppad / kAfTile;
 
-  af_f32x4 dwacc[NA][ND];                  // dW[16 n + 4 quad + r][16 m + col] over all samples of this wavefront
+  f32x4 dwacc[NA][ND];                  // dW[16 n + 4 quad + r][16 m + col] over all samples of this wavefront
   float dh_acc[NA];                        // dh[16 n + col], this quad's pairs
 #pragma unroll
   for (int n = 0; n < NA; ++n) {
     dh_acc[n] = 0.f;
 #pragma unroll
-    for (int mm = 0; mm < ND; ++mm) dwacc[n][mm] = af_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int mm = 0; mm < ND; ++mm) dwacc[n][mm] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
 
   const long long step = static_cast<long long>(gridDim.x) * nw;
@@ -266,12 +259,12 @@ __global__ __launch_bounds__(256) void afm_bwd_kernel(const AfmArgs g) {
     {
       float p = 0.f;
       for (int cc = col; cc < D; cc += 16) p = fma_rn(dd[cc], ok ? g.out_in[b * D + cc] : 0.f, p);
-      Gd = af_sum16(p);
+      Gd = group_sum<16, kWave>(p);
     }
     const float m = ok ? g.stat_in[b] : 0.f, sum = ok ? g.stat_in[g.B + b] : 1.f;
 
     for (int t = 0; t < ntile; ++t) {
-      af_f32x4 acc[NA];
+      f32x4 acc[NA];
       float lg[4], ar[4], dpr[NA][4];
       unsigned ijr[4];
       af_tile_logits<NA, KS>(xs, pij, t, P, D, col, quad, wf, hr, acc, lg);
@@ -285,7 +278,7 @@ __global__ __launch_bounds__(256) void afm_bwd_kernel(const AfmArgs g) {
         const float* xj = xs + (ij >> 8) * D;
         float p = 0.f;
         for (int cc = col; cc < D; cc += 16) p = fma_rn(dd[cc], mul_rn(xi[cc], xj[cc]), p);
-        const float gk = af_sum16(p);
+        const float gk = group_sum<16, kWave>(p);
         const float a = valid ? expf(lg[r] - m) / sum : 0.f;
         const float ds = a * (gk - Gd);
         ar[r] = a;
@@ -315,11 +308,11 @@ __global__ __launch_bounds__(256) void afm_bwd_kernel(const AfmArgs g) {
       for (int n = 0; n < NA; ++n)
         *reinterpret_cast<float4*>(dpw + (16 * n + col) * 16 + 4 * quad) = make_float4(dpr[n][0], dpr[n][1], dpr[n][2], dpr[n][3]);
       __syncthreads();                     // dpre of the tile
-      af_f32x4 dpacc[ND];                  // dp: pair 4 quad + r, column 16 m + col
+      f32x4 dpacc[ND];                  // dp: pair 4 quad + r, column 16 m + col
 #pragma unroll
       for (int mm = 0; mm < ND; ++mm) {
         const float dj = dd[16 * mm + col];
-        dpacc[mm] = af_f32x4{ar[0] * dj, ar[1] * dj, ar[2] * dj, ar[3] * dj};
+        dpacc[mm] = f32x4{ar[0] * dj, ar[1] * dj, ar[2] * dj, ar[3] * dj};
       }
 #pragma unroll
       for (int s = 0; s < 4 * NA; ++s) {
@@ -377,21 +370,12 @@ __global__ __launch_bounds__(256) void afm_bwd_kernel(const AfmArgs g) {
   }
 }
 
-// dW[e] / dh[e - A D] = sum over the rows of the workspace: thread (row lane r = tid / 16, column tid % 16) adds rows r,
-// r + 16, ... in ascending order, then a tree over the 16 row lanes
+// dW[e] / dh[e - A D] = sum over the rows of the workspace, in colsum16's order
 __global__ __launch_bounds__(256) void afm_tail_kernel(const float* __restrict__ part, const int rows, const int rl, const int ad,
                                                        float* __restrict__ dw, float* __restrict__ dh) {
   __shared__ float sm[16][17];
   const int c = threadIdx.x & 15, r = threadIdx.x >> 4, e = blockIdx.x * 16 + c;
-  float s = 0.f;
-  if (e < rl)
-    for (int q = r; q < rows; q += 16) s += part[static_cast<long long>(q) * rl + e];
-  sm[r][c] = s;
-  __syncthreads();
-  for (int o = 8; o > 0; o >>= 1) {
-    if (r < o) sm[r][c] += sm[r + o][c];
-    __syncthreads();
-  }
+  colsum16(part, rows, rl, e, r, c, sm);
   if (r == 0 && e < rl) {
     if (e < ad) {
       if (dw != nullptr) dw[e] = sm[0][c];
@@ -401,8 +385,6 @@ __global__ __launch_bounds__(256) void afm_tail_kernel(const float* __restrict__
   }
 }
 
-static bool af_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 static int af_check(const char* what, int64_t batch, int32_t n_fields, int32_t dim, int32_t att_dim, int32_t dtype, const void* x,
                     int64_t xs_b, int64_t xs_f) {
   if (batch < 0) return fail(RBX_ERR_INVALID, "%s: batch=%lld", what, static_cast<long long>(batch));
@@ -410,7 +392,7 @@ static int af_check(const char* what, int64_t batch, int32_t n_fields, int32_t d
     return fail(RBX_ERR_UNSUPPORTED, "%s: n_fields=%d in [%d,%d], dim=%d a multiple of 4 in [%d,%d], att_dim=%d in [1,%d]", what,
                 n_fields, kAfMinF, kAfMaxF, dim, kAfMinD, kAfMaxD, att_dim, kAfMaxA);
   if (dtype != RBX_F32) return fail(RBX_ERR_UNSUPPORTED, "%s: tensor dtype code %d (float32 only)", what, dtype);
-  if (x != nullptr && (!af_aligned(x) || (xs_b & 3) != 0 || (xs_f & 3) != 0 || xs_f < dim || xs_b < 0))
+  if (x != nullptr && (!aligned16(x) || (xs_b & 3) != 0 || (xs_f & 3) != 0 || xs_f < dim || xs_b < 0))
     return fail(RBX_ERR_UNSUPPORTED, "%s: x must be 16-byte aligned with strides that are multiples of 4 floats", what);
   return RBX_OK;
 }
@@ -476,7 +458,7 @@ extern "C" int rbx_afm_bwd(const float* d_dout, int64_t dout_stride_b, const flo
   if (rc != RBX_OK) return rc;
   if (batch == 0) return RBX_OK;
   if (!d_dout || !d_x || !d_w || !d_h || !d_out || !d_stat) return fail(RBX_ERR_INVALID, "afm_bwd: NULL tensor");
-  if (!af_aligned(d_dout) || (dout_stride_b & 3) != 0 || dout_stride_b < dim)
+  if (!aligned16(d_dout) || (dout_stride_b & 3) != 0 || dout_stride_b < dim)
     return fail(RBX_ERR_UNSUPPORTED, "afm_bwd: d_dout must be 16-byte aligned with a row stride that is a multiple of 4 floats");
   if (d_workspace == nullptr || workspace_bytes < rbx_afm_bwd_workspace_size(batch, n_fields, dim, att_dim))
     return fail(RBX_ERR_WORKSPACE, "afm_bwd: workspace too small");

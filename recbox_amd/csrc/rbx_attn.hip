@@ -466,9 +466,7 @@ extern "C" int rbx_attn_dropout_fwd(const float* d_q, const float* d_k, const fl
   hipStream_t s = as_stream(stream);
 #define CALL(HD)                                                                                                  \
   do {                                                                                                            \
-    if (lds > 64 * 1024)                                                                                          \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<HD>),                                    \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));                     \
+    if ((rc = allow_lds("attn_fwd_kernel", &attn_fwd_kernel<HD>, lds)) != RBX_OK) return rc;                     \
     hipLaunchKernelGGL((attn_fwd_kernel<HD>), dim3(static_cast<unsigned>(bh), qb), dim3(kAttnThreads), lds, s, d_q, \
                        d_k, d_v, d_mask, lq, lk, scale, causal, mask_fill, d_o, d_lse, d_p, drop, C);             \
   } while (0)
@@ -512,12 +510,8 @@ extern "C" int rbx_attn_dropout_bwd(const float* d_q, const float* d_k, const fl
   hipStream_t s = as_stream(stream);
 #define CALL(HD)                                                                                                   \
   do {                                                                                                             \
-    if (lds_a > 64 * 1024)                                                                                         \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dq_kernel<HD>),                                  \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_a));                    \
-    if (lds_b > 64 * 1024)                                                                                         \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkv_kernel<HD>),                                 \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_b));                    \
+    if ((rc = allow_lds("attn_bwd_dq_kernel", &attn_bwd_dq_kernel<HD>, lds_a)) != RBX_OK) return rc;              \
+    if ((rc = allow_lds("attn_bwd_dkv_kernel", &attn_bwd_dkv_kernel<HD>, lds_b)) != RBX_OK) return rc;            \
     hipLaunchKernelGGL((attn_bwd_dq_kernel<HD>), dim3(static_cast<unsigned>(bh), qb), dim3(kAttnThreads), lds_a, s, \
                        d_q, d_k, d_v, d_mask, d_o, d_do, d_lse, lq, lk, scale, causal, mask_fill, d_dq,            \
                        d_scratch, drop, Ca);                                                                       \

@@ -121,9 +121,8 @@ __device__ __forceinline__ void stage_two(const float* __restrict__ ga, const lo
 // loops over sequences: one workgroup per CU means nothing else hides these loads -- the forward at L = 200 spent about as
 // long waiting for K and V as multiplying them).  Issued as inline assembly so that the compiler cannot sink the loads to
 // their use at the top of the next iteration; rows beyond `rows` are clamped here and zeroed when they are written to LDS.
-typedef float attn_f4 __attribute__((ext_vector_type(4)));
 template <int HD, int N>
-__device__ __forceinline__ void prefetch_rows(const float* g, const long long ld, int rows, attn_f4 (&v)[N]) {
+__device__ __forceinline__ void prefetch_rows(const float* g, const long long ld, int rows, f32x4 (&v)[N]) {
   constexpr int Q4 = HD / 4;
 #pragma unroll
   for (int u = 0; u < N; ++u) {
@@ -137,7 +136,7 @@ __device__ __forceinline__ void prefetch_rows(const float* g, const long long ld
 }
 template <int HD, int N>
 __device__ __forceinline__ void commit_rows(float* __restrict__ lds, int rows, int rows_pad, float scale,
-                                            const attn_f4 (&v)[N]) {
+                                            const f32x4 (&v)[N]) {
   constexpr int Q4 = HD / 4;
   const int total = rows_pad * Q4;
 #pragma unroll
@@ -495,7 +494,7 @@ __global__ __launch_bounds__(kAttnThreads) void attn_mfma_fwd_kernel(const float
   unsigned dk0 = 0, dk1 = 0;
   if (DROP) drop_seed(drop, &dk0, &dk1);
   constexpr bool PF = NPF > 0;
-  attn_f4 kpf[PF ? NPF : 1], vpf[PF ? NPF : 1];
+  f32x4 kpf[PF ? NPF : 1], vpf[PF ? NPF : 1];
   for (long long bh = blockIdx.x; bh < BH; bh += gridDim.x) {
     const float* Q = Q0 + attn_base(bh, ld.heads, L, ld.q, HD);
     const float* K = K0 + attn_base(bh, ld.heads, L, ld.k, HD);
@@ -927,16 +926,16 @@ static int run_fwd(const float* q, const float* k, const float* v, long long bh,
       // seven tiles (192 < L <= 224: BASELINE cfg 5's L = 200): K / V as three bf16 planes split once per tile by the loader
       // (rbx_attn_planes.h): 339 vs 373 us at L = 200, 4096 sequences, the same 1e-7 error against float64
       // (profiles/r04/attn_planes.txt); the default since round 5
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_planes_fwd_kernel<DROP>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kPlanesLds));
+      const int lrc = allow_lds("attn_planes_fwd_kernel", &attn_planes_fwd_kernel<DROP>, kPlanesLds);
+      if (lrc != RBX_OK) return lrc;
       const long long pairs = (bh + 1) / 2;
       hipLaunchKernelGGL((attn_planes_fwd_kernel<DROP>), dim3(static_cast<unsigned>(pairs < kCUs ? pairs : kCUs)), dim3(512),
                          kPlanesLds, s, q, k, v, L, scale, o, lse, drop, ld, bh);
       return check_launch("attn_planes_fwd_kernel");
     }
     if (causal != 0 && nT >= 3 && nT <= 7) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_stream_fwd_kernel<DROP>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kStreamLds));
+      const int lrc = allow_lds("attn_stream_fwd_kernel", &attn_stream_fwd_kernel<DROP>, kStreamLds);
+      if (lrc != RBX_OK) return lrc;
       hipLaunchKernelGGL((attn_stream_fwd_kernel<DROP>), dim3(static_cast<unsigned>((bh + 1) / 2)), dim3((nT + 1) * 64),
                          kStreamLds, s, q, k, v, L, scale, o, lse, drop, ld, bh);
       return check_launch("attn_stream_fwd_kernel");
@@ -953,8 +952,8 @@ static int run_fwd(const float* q, const float* k, const float* v, long long bh,
       const int split = split_on ? 1 : 0;
       const size_t lds_pf = split ? lds_split : lds;
 #define RBX_ATTN_PF(N)                                                                                                  \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_mfma_fwd_kernel<HD, DROP, N>),                        \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_pf));                   \
+      const int lrc = allow_lds("attn_mfma_fwd_kernel", &attn_mfma_fwd_kernel<HD, DROP, N>, lds_pf);                       \
+      if (lrc != RBX_OK) return lrc;                                                                                     \
       hipLaunchKernelGGL((attn_mfma_fwd_kernel<HD, DROP, N>), dim3(kCUs), dim3(kAttnThreads), lds_pf, s, q, k, v, L, scale, \
                          causal, o, lse, drop, ld, bh, split)
       if (npf == 6) { RBX_ATTN_PF(6); } else if (npf == 7) { RBX_ATTN_PF(7); } else { RBX_ATTN_PF(8); }
@@ -962,8 +961,8 @@ static int run_fwd(const float* q, const float* k, const float* v, long long bh,
       return check_launch("attn_mfma_fwd_kernel");
     }
   }
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_mfma_fwd_kernel<HD, DROP, 0>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+  const int lrc = allow_lds("attn_mfma_fwd_kernel", &attn_mfma_fwd_kernel<HD, DROP, 0>, lds);
+  if (lrc != RBX_OK) return lrc;
   hipLaunchKernelGGL((attn_mfma_fwd_kernel<HD, DROP, 0>), dim3(static_cast<unsigned>(bh)), dim3(kAttnThreads), lds, s, q, k, v,
                      L, scale, causal, o, lse, drop, ld, bh, split_on ? 2 : 0);
   return check_launch("attn_mfma_fwd_kernel");
@@ -974,10 +973,9 @@ static int run_bwd(const float* q, const float* k, const float* v, const float* 
                    long long bh, int L, float scale, int causal, float* dq, float* dk, float* dv, float* scratch,
                    const DropArgs& drop, const AttnLd& ld, hipStream_t s) {
   const size_t la = lds_bytes<HD>(L, false), lb = lds_bytes<HD>(L, true);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_mfma_bwd_q_kernel<HD, DROP>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(la));
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_mfma_bwd_kv_kernel<HD, DROP>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lb));
+  int lrc = allow_lds("attn_mfma_bwd_q_kernel", &attn_mfma_bwd_q_kernel<HD, DROP>, la);
+  if (lrc == RBX_OK) lrc = allow_lds("attn_mfma_bwd_kv_kernel", &attn_mfma_bwd_kv_kernel<HD, DROP>, lb);
+  if (lrc != RBX_OK) return lrc;
   const int split = attn_split(L, causal) ? 1 : 0;
   hipLaunchKernelGGL((attn_mfma_bwd_q_kernel<HD, DROP>), dim3(static_cast<unsigned>(bh)), dim3(kAttnThreads), la, s, q, k, v, o,
                      go, lse, L, scale, causal, dq, scratch, drop, ld, split);

@@ -94,10 +94,10 @@ __device__ __forceinline__ void tile_accumulate_pl(const char* __restrict__ Vt, 
 // Every load inside the persistent loop is an asm statement and the ONE wait of an iteration (`pl_arrived`, after the tile
 // step, in front of the plane writes) names all their registers: with loads the compiler counts, its wait for the next
 // tile's Q rows sat at the loop header as vmcnt(0) and drained the tile prefetch issued just before the barrier.
-__device__ __forceinline__ void pl_load(attn_f4& v, const float* src) {
+__device__ __forceinline__ void pl_load(f32x4& v, const float* src) {
   asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(src));
 }
-__device__ __forceinline__ void pl_arrived(attn_f4 (&pf)[4], attn_f4 (&qv)[8]) {
+__device__ __forceinline__ void pl_arrived(f32x4 (&pf)[4], f32x4 (&qv)[8]) {
   asm volatile("s_waitcnt vmcnt(0)"
                : "+v"(pf[0]), "+v"(pf[1]), "+v"(pf[2]), "+v"(pf[3]), "+v"(qv[0]), "+v"(qv[1]), "+v"(qv[2]), "+v"(qv[3]),
                  "+v"(qv[4]), "+v"(qv[5]), "+v"(qv[6]), "+v"(qv[7])
@@ -106,7 +106,7 @@ __device__ __forceinline__ void pl_arrived(attn_f4 (&pf)[4], attn_f4 (&qv)[8]) {
 }
 // the wavefront's own tile, unscaled: qv[q] = g[row0 + li][half * 32 + 4 q .. + 3] (rows beyond `rows`: row rows - 1).  Issued
 // under a (wave-uniform) condition: the destinations are read-write operands, so the registers are the same on both paths.
-__device__ __forceinline__ void pl_load_q(const float* __restrict__ g, const long long ld, int row0, int rows, attn_f4 (&qv)[8]) {
+__device__ __forceinline__ void pl_load_q(const float* __restrict__ g, const long long ld, int row0, int rows, f32x4 (&qv)[8]) {
   const int lane = threadIdx.x & 63;
   int row = row0 + (lane & 31);
   row = row < rows ? row : rows - 1;
@@ -116,7 +116,7 @@ __device__ __forceinline__ void pl_load_q(const float* __restrict__ g, const lon
 }
 
 // four floats of row r, columns c4 .. c4 + 3 -> the three planes of `tile`
-__device__ __forceinline__ void planes_store(char* tile, const int r, const int c4, const attn_f4 v) {
+__device__ __forceinline__ void planes_store(char* tile, const int r, const int c4, const f32x4 v) {
   unsigned h0, m0, l0, h1, m1, l1;
   attn_split2(af32x2_t{v[0], v[1]}, h0, m0, l0);
   attn_split2(af32x2_t{v[2], v[3]}, h1, m1, l1);
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(512) void attn_planes_fwd_kernel(const float* __res
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6), li = lane & 31, half = lane >> 5;
   const long long pairs = (BH + 1) / 2;
   const int pr = tid >> 4, pc4 = (tid & 15) * 4;             // this thread's float4 of every tile: row, first column
-  attn_f4 pf[4];
+  f32x4 pf[4];
   // the four tiles of iteration `it` of pair `p` -> registers (rows beyond L: row L - 1)
   // (UNCONDITIONAL: an asm load inside a branch makes the join copy its destination registers while the data is still in
   //  flight -- the landing load then overwrites whatever the allocator put there next, e.g. an address.  Slots without a
@@ -168,9 +168,9 @@ __global__ __launch_bounds__(512) void attn_planes_fwd_kernel(const float* __res
   unsigned dk0 = 0, dk1 = 0;
   if (DROP) drop_seed(drop, &dk0, &dk1);
   TileOp<HD, true> qop;
-  attn_f4 qv[8];
+  f32x4 qv[8];
 #pragma unroll
-  for (int q = 0; q < 8; ++q) qv[q] = attn_f4{0.f, 0.f, 0.f, 0.f};
+  for (int q = 0; q < 8; ++q) qv[q] = f32x4{0.f, 0.f, 0.f, 0.f};
   bool fresh = false;
   f32x16 oacc[2];
 #pragma unroll

@@ -27,8 +27,6 @@
 
 namespace rbx {
 
-typedef float bl_f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kBlMinF = 2, kBlMaxF = 64;
 constexpr int kBlTile = 16;                  // samples per tile = rows of the MFMA
 constexpr int kBlBlock = 256;
@@ -37,9 +35,10 @@ constexpr int kGateMaxR = 32;
 constexpr int kGateBlock = 256;
 constexpr int kGateFwdGrid = 1024, kGateBwdGrid = 256;
 
-static bool bl_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static bool bl_dim_ok(int d) { return d == 4 || d == 8 || d == 16 || d == 32; }
 
+// Not group_sum<16>: the offsets ascend here, which pairs the lanes in another order and rounds differently; the weight
+// gradients keep their bits only with this order.
 __device__ __forceinline__ float bl_sum16(float v) {
   v += __shfl_xor(v, 1, 64);
   v += __shfl_xor(v, 2, 64);
@@ -222,7 +221,7 @@ static int gate_check(const char* what, const float* x, int64_t xsb, int64_t xsf
                 fields, kBlMinF, kBlMaxF, dim, reduced, kGateMaxR);
   if (batch == 0) return RBX_OK;
   if (!x) return fail(RBX_ERR_INVALID, "%s: x is NULL", what);
-  if (!bl_aligned(x) || (xsb & 3) != 0 || (xsf & 3) != 0 || xsb < 0 || xsf < dim)
+  if (!aligned16(x) || (xsb & 3) != 0 || (xsf & 3) != 0 || xsb < 0 || xsf < dim)
     return fail(RBX_ERR_UNSUPPORTED, "%s: x must be 16-byte aligned with strides that are multiples of 4 floats", what);
   return RBX_OK;
 }
@@ -304,7 +303,7 @@ __global__ __launch_bounds__(kBlBlock) void bl_fwd_kernel(const BlArgs a) {
   bl_decode(w_lo, F, &i, &j);
   int last_m = -1, last_i = -1;
   float wf[NCB][KS];
-  bl_f32x4 L[NCB];
+  f32x4 L[NCB];
   for (int p = w_lo; p < w_hi; ++p) {
     const int m = bl_matrix(a.kind, i, p);
     const bool new_w = m != last_m;
@@ -312,7 +311,7 @@ __global__ __launch_bounds__(kBlBlock) void bl_fwd_kernel(const BlArgs a) {
     if (new_w || i != last_i) {
 #pragma unroll
       for (int cb = 0; cb < NCB; ++cb) {
-        bl_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s = 0; s < KS; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(xs[col * S + i * D + 4 * s + quad], wf[cb][s], acc, 0, 0, 0);
         L[cb] = acc;
@@ -367,9 +366,9 @@ __global__ __launch_bounds__(kBlBlock) void bl_dx_kernel(const BlArgs a) {
   int last_m = -1;
   float wl[NCB][KS], wt[NCB][KS];
   for (int i = 0; i + 1 < F; ++i) {
-    bl_f32x4 accI[NCB];
+    f32x4 accI[NCB];
 #pragma unroll
-    for (int cb = 0; cb < NCB; ++cb) accI[cb] = bl_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int cb = 0; cb < NCB; ++cb) accI[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
     float daI[4] = {0.f, 0.f, 0.f, 0.f}, ai[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) ai[r] = (has_a && b0 + 4 * quad + r < a.B) ? a.a[(b0 + 4 * quad + r) * F + i] : 0.f;
@@ -377,7 +376,7 @@ __global__ __launch_bounds__(kBlBlock) void bl_dx_kernel(const BlArgs a) {
     float xa[KS];
 #pragma unroll
     for (int s = 0; s < KS; ++s) xa[s] = oka ? a.x[ba * a.xsb + i * a.xsf + 4 * s + quad] : 0.f;
-    bl_f32x4 L[NCB];
+    f32x4 L[NCB];
     bool have_l = false;
     for (int j = i + 1 + wave; j < F; j += 4) {
       const int p = base + (j - i - 1);
@@ -392,7 +391,7 @@ __global__ __launch_bounds__(kBlBlock) void bl_dx_kernel(const BlArgs a) {
       if (!have_l) {
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb) {
-          bl_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+          f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
           for (int s = 0; s < KS; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[s], wl[cb][s], acc, 0, 0, 0);
           L[cb] = acc;
@@ -512,13 +511,13 @@ __global__ __launch_bounds__(kBlBlock) void bl_dw_kernel(const BlArgs a) {
       }
     }
   }
-  bl_f32x4 acc[NP][NCB][NCB];
+  f32x4 acc[NP][NCB][NCB];
 #pragma unroll
   for (int q = 0; q < NP; ++q)
 #pragma unroll
     for (int db = 0; db < NCB; ++db)
 #pragma unroll
-      for (int eb = 0; eb < NCB; ++eb) acc[q][db][eb] = bl_f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int eb = 0; eb < NCB; ++eb) acc[q][db][eb] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const long long t0 = static_cast<long long>(blockIdx.x) * a.tpc;
   for (int tt = 0; tt < a.tpc; ++tt) {
@@ -635,20 +634,10 @@ static int bl_check(const char* what, const float* x, int64_t xsb, int64_t xsf, 
                 kBlMaxF, dim);
   if (batch == 0) return RBX_OK;
   if (!x || !w) return fail(RBX_ERR_INVALID, "%s: NULL pointer", what);
-  if (!bl_aligned(x) || (xsb & 3) != 0 || (xsf & 3) != 0 || xsb < 0 || xsf < dim)
+  if (!aligned16(x) || (xsb & 3) != 0 || (xsf & 3) != 0 || xsb < 0 || xsf < dim)
     return fail(RBX_ERR_UNSUPPORTED, "%s: x must be 16-byte aligned with strides that are multiples of 4 floats", what);
   if ((batch + kBlTile - 1) / kBlTile > INT_MAX) return fail(RBX_ERR_UNSUPPORTED, "%s: batch=%lld is too large", what, static_cast<long long>(batch));
   return RBX_OK;
-}
-
-// above 64 KiB of dynamic LDS a kernel has to be opted in; a refusal is reported here, not by the launch that would follow
-template <typename K>
-static int bl_allow_lds(const char* what, K kernel, size_t lds) {
-  if (lds <= 64 * 1024) return RBX_OK;
-  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-  if (e == hipSuccess) return RBX_OK;
-  (void)hipGetLastError();
-  return fail(RBX_ERR_LAUNCH, "%s: the opt-in to %zu bytes of dynamic LDS failed: %s", what, lds, hipGetErrorString(e));
 }
 
 }  // namespace rbx
@@ -689,7 +678,7 @@ extern "C" int rbx_senet_gate_bwd(const float* d_da, const float* d_x, int64_t x
   if (rc != RBX_OK || batch == 0) return rc;
   if (!d_da || !d_w1 || !d_w2 || !d_a || !d_h || !d_dx || !d_dw1 || !d_dw2 || !d_workspace)
     return fail(RBX_ERR_INVALID, "senet_gate_bwd: NULL pointer");
-  if (!bl_aligned(d_dx)) return fail(RBX_ERR_UNSUPPORTED, "senet_gate_bwd: dx must be 16-byte aligned");
+  if (!aligned16(d_dx)) return fail(RBX_ERR_UNSUPPORTED, "senet_gate_bwd: dx must be 16-byte aligned");
   if (workspace_bytes < rbx_senet_gate_bwd_workspace_size(batch, fields, reduced))
     return fail(RBX_ERR_WORKSPACE, "senet_gate_bwd: workspace of %zu bytes is too small", workspace_bytes);
   GateArgs g{};
@@ -735,7 +724,7 @@ extern "C" int rbx_bilinear_pairs_fwd(const float* d_x, int64_t x_stride_b, int6
   hipStream_t s = as_stream(stream);
   int rc_lds = RBX_OK;
 #define RBX_BL_FWD(DD)                                                                      \
-  if ((rc_lds = bl_allow_lds("bilinear_pairs_fwd", bl_fwd_kernel<DD>, lds)) == RBX_OK)      \
+  if ((rc_lds = allow_lds("bilinear_pairs_fwd", bl_fwd_kernel<DD>, lds)) == RBX_OK)      \
   hipLaunchKernelGGL(bl_fwd_kernel<DD>, grid, block, lds, s, a)
   switch (dim) {
     case 4: RBX_BL_FWD(4); break;
@@ -765,7 +754,7 @@ extern "C" int rbx_bilinear_pairs_bwd(const float* d_dout, int64_t dout_stride_b
   if (rc != RBX_OK || batch == 0) return rc;
   const int P = bl_pairs(fields);
   if (!d_dout || !d_dx || !d_dw || !d_workspace) return fail(RBX_ERR_INVALID, "bilinear_pairs_bwd: NULL pointer");
-  if (!bl_aligned(d_dx)) return fail(RBX_ERR_UNSUPPORTED, "bilinear_pairs_bwd: dx must be 16-byte aligned");
+  if (!aligned16(d_dx)) return fail(RBX_ERR_UNSUPPORTED, "bilinear_pairs_bwd: dx must be 16-byte aligned");
   if (dout_stride_b < static_cast<int64_t>(d_a ? 2 : 1) * P * dim)
     return fail(RBX_ERR_INVALID, "bilinear_pairs_bwd: dout_stride_b=%lld is shorter than a row block", static_cast<long long>(dout_stride_b));
   if (workspace_bytes < rbx_bilinear_pairs_bwd_workspace_size(batch, fields, dim))
@@ -783,7 +772,7 @@ extern "C" int rbx_bilinear_pairs_bwd(const float* d_dout, int64_t dout_stride_b
   hipStream_t s = as_stream(stream);
   int rc_lds = RBX_OK;
 #define RBX_BL_BWD(DD)                                                                          \
-  if ((rc_lds = bl_allow_lds("bilinear_pairs_bwd", bl_dx_kernel<DD>, lds)) == RBX_OK) {         \
+  if ((rc_lds = allow_lds("bilinear_pairs_bwd", bl_dx_kernel<DD>, lds)) == RBX_OK) {         \
     hipLaunchKernelGGL(bl_dx_kernel<DD>, grid_dx, block, lds, s, a);                            \
     hipLaunchKernelGGL(bl_dw_kernel<DD>, grid_dw, block, 0, s, a);                              \
   }

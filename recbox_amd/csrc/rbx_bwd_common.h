@@ -195,13 +195,12 @@ struct Frag {
     }
   }
   __device__ __forceinline__ void load_from_nt(const float* row, int dim, int lane_g) {
-    typedef float v4f __attribute__((ext_vector_type(4)));
 #pragma unroll
     for (int u = 0; u < NV; ++u) {
       int e = (lane_g + u * G) * W;
       e = e < dim ? e : dim - W;
       if constexpr (VEC) {
-        const v4f t = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(row + e));
+        const f32x4 t = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(row + e));
         a[u * 4 + 0] = t.x; a[u * 4 + 1] = t.y; a[u * 4 + 2] = t.z; a[u * 4 + 3] = t.w;
       } else {
         a[u] = __builtin_nontemporal_load(row + e);
@@ -215,13 +214,12 @@ struct Frag {
   // streaming variants: rows that are touched once per call should not evict the L2-resident
   // gather operands (S, g), so they use the non-temporal cache policy
   __device__ __forceinline__ void add_from_nt(const float* row, int dim, int lane_g) {
-    typedef float v4f __attribute__((ext_vector_type(4)));
 #pragma unroll
     for (int u = 0; u < NV; ++u) {
       const int e = (lane_g + u * G) * W;
       if (e < dim) {
         if constexpr (VEC) {
-          const v4f t = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(row + e));
+          const f32x4 t = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(row + e));
           a[u * 4 + 0] += t.x; a[u * 4 + 1] += t.y; a[u * 4 + 2] += t.z; a[u * 4 + 3] += t.w;
         } else {
           a[u] += __builtin_nontemporal_load(row + e);
@@ -230,15 +228,14 @@ struct Frag {
     }
   }
   __device__ __forceinline__ void store_nt(float* row, int dim, int lane_g) const {
-    typedef float v4f __attribute__((ext_vector_type(4)));
 #pragma unroll
     for (int u = 0; u < NV; ++u) {
       const int e = (lane_g + u * G) * W;
       if (e < dim) {
         if constexpr (VEC) {
-          v4f t;
+          f32x4 t;
           t.x = a[u * 4]; t.y = a[u * 4 + 1]; t.z = a[u * 4 + 2]; t.w = a[u * 4 + 3];
-          __builtin_nontemporal_store(t, reinterpret_cast<v4f*>(row + e));
+          __builtin_nontemporal_store(t, reinterpret_cast<f32x4*>(row + e));
         } else {
           __builtin_nontemporal_store(a[u], row + e);
         }

@@ -98,12 +98,6 @@ __global__ __launch_bounds__(256) void capsule_hat_kernel(const float* __restric
 }
 
 // ---- routing ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float cap_wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 __device__ __forceinline__ bool cap_mask_on(const void* p, long long idx, int dt) {
   switch (dt) {
     case RBX_I32: return static_cast<const int*>(p)[idx] != 0;
@@ -155,7 +149,7 @@ __global__ void capsule_route_kernel(const float* __restrict__ hat, const long l
     // c = softmax over all L positions, then 0 at the masked ones
     float mx = -INFINITY;
     for (int l = lane; l < L; l += 64) mx = fmaxf(mx, lg[l]);
-    mx = cap_wave_max(mx);
+    mx = group_max<kWave>(mx);
     float sum = 0.f;
     for (int l = lane; l < L; l += 64) {
       const float e = expf(lg[l] - mx);
@@ -419,8 +413,6 @@ __global__ __launch_bounds__(256) void capsule_reduce_kernel(const float* __rest
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------
-static bool cap_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 static int cap_splits(int64_t batch) { return static_cast<int>((batch + kCapDwSplit - 1) / kCapDwSplit); }
 
 static long long cap_slab(int L, int D) { return static_cast<long long>(L) * (D + 1) + 3LL * L + D; }
@@ -437,19 +429,11 @@ static int cap_check_shape(const char* what, int64_t batch, int32_t seq_len, int
   return RBX_OK;
 }
 
-template <typename Kn>
-static int cap_set_lds(Kn kernel, size_t lds, const char* what) {
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          static_cast<int>(lds)) != hipSuccess)
-    return fail(RBX_ERR_LAUNCH, "%s: %zu bytes of LDS refused", what, lds);
-  return RBX_OK;
-}
-
 template <int NT>
 static int cap_launch_dx(const float* W, const float* G, long long gs_b, long long gs_l, const float* C, int B, int L, int D,
                          int K, float* dX, hipStream_t s) {
   const size_t lds = (static_cast<size_t>(kCapKC) * kCapLd + kCapKC * D + K * kCapBM) * sizeof(float);
-  const int rc = cap_set_lds(&capsule_dx_kernel<NT>, lds, "capsule_bilinear_dx");
+  const int rc = allow_lds("capsule_bilinear_dx", &capsule_dx_kernel<NT>, lds);
   if (rc != RBX_OK) return rc;
   hipLaunchKernelGGL((capsule_dx_kernel<NT>), dim3((B + kCapBM - 1) / kCapBM, L), dim3(256), lds, s, W, G, gs_b, gs_l, C, B, L,
                      D, K, dX);
@@ -460,7 +444,7 @@ template <int NT>
 static int cap_launch_dw(const float* X, long long xs_b, long long xs_l, const float* G, long long gs_b, long long gs_l,
                          const float* C, int B, int L, int D, int K, float* out, hipStream_t s) {
   const size_t lds = (static_cast<size_t>(kCapKC) * kCapBM + kCapKC * D + kCapKC * K) * sizeof(float);
-  const int rc = cap_set_lds(&capsule_dw_kernel<NT>, lds, "capsule_bilinear_dw");
+  const int rc = allow_lds("capsule_bilinear_dw", &capsule_dw_kernel<NT>, lds);
   if (rc != RBX_OK) return rc;
   hipLaunchKernelGGL((capsule_dw_kernel<NT>), dim3(cap_splits(B), L, (K * D + kCapBM - 1) / kCapBM), dim3(256), lds, s, X, xs_b,
                      xs_l, G, gs_b, gs_l, C, B, L, D, K, out);
@@ -483,11 +467,11 @@ extern "C" int rbx_capsule_hat(const float* d_x, int64_t x_stride_b, int64_t x_s
   if (rc != RBX_OK) return rc;
   if (batch == 0) return RBX_OK;
   if (!d_x || !d_w || !d_hat) return fail(RBX_ERR_INVALID, "capsule_hat: NULL tensor");
-  if (!cap_aligned(d_x) || !cap_aligned(d_w) || (x_stride_b & 3) != 0 || (x_stride_l & 3) != 0)
+  if (!aligned16(d_x) || !aligned16(d_w) || (x_stride_b & 3) != 0 || (x_stride_l & 3) != 0)
     return fail(RBX_ERR_UNSUPPORTED, "capsule_hat: bases must be 16-byte aligned and strides multiples of 4 floats");
   const int B = static_cast<int>(batch), N = interests * dim;
   const size_t lds = (static_cast<size_t>(dim) * kCapLd + dim * (kCapNC + 2)) * sizeof(float);
-  rc = cap_set_lds(&capsule_hat_kernel, lds, "capsule_hat");
+  rc = allow_lds("capsule_hat", &capsule_hat_kernel, lds);
   if (rc != RBX_OK) return rc;
   hipLaunchKernelGGL(capsule_hat_kernel, dim3((B + kCapBM - 1) / kCapBM, seq_len), dim3(256), lds, as_stream(stream), d_x,
                      x_stride_b, x_stride_l, d_w, B, seq_len, dim, N, d_hat);
@@ -509,7 +493,7 @@ extern "C" int rbx_capsule_route_fwd(const float* d_hat, int64_t hat_stride_b, i
     return fail(RBX_ERR_UNSUPPORTED, "capsule_route_fwd: mask_dtype=%d", mask_dtype);
   if (batch == 0) return RBX_OK;
   if (!d_hat || !d_mask || !d_v || !d_c || !d_s) return fail(RBX_ERR_INVALID, "capsule_route_fwd: NULL tensor");
-  if (!cap_aligned(d_hat) || (hat_stride_b & 3) != 0 || (hat_stride_k & 3) != 0 || (hat_stride_l & 3) != 0)
+  if (!aligned16(d_hat) || (hat_stride_b & 3) != 0 || (hat_stride_k & 3) != 0 || (hat_stride_l & 3) != 0)
     return fail(RBX_ERR_UNSUPPORTED, "capsule_route_fwd: hat must be 16-byte aligned with strides that are multiples of 4");
   const int slab = static_cast<int>(cap_slab(seq_len, dim));
   int per = kCapWgFloats / slab;
@@ -532,7 +516,7 @@ extern "C" int rbx_capsule_route_bwd(const float* d_dv, const float* d_s, const 
   if (batch == 0) return RBX_OK;
   if (!d_dv || !d_s || (d_dhat != nullptr && !d_c) || (!d_ds && !d_dhat))
     return fail(RBX_ERR_INVALID, "capsule_route_bwd: NULL tensor");
-  if (d_dhat != nullptr && !cap_aligned(d_dhat)) return fail(RBX_ERR_UNSUPPORTED, "capsule_route_bwd: dhat must be 16-byte aligned");
+  if (d_dhat != nullptr && !aligned16(d_dhat)) return fail(RBX_ERR_UNSUPPORTED, "capsule_route_bwd: dhat must be 16-byte aligned");
   hipLaunchKernelGGL(capsule_ds_kernel, dim3(static_cast<unsigned>(batch)), dim3(256), lds, as_stream(stream), d_dv, d_s, d_c,
                      interests, seq_len, dim, shared, d_ds, d_dhat);
   return check_launch("capsule_route_bwd");
@@ -546,7 +530,7 @@ extern "C" int rbx_capsule_bilinear_dx(const float* d_w, const float* d_g, int64
   if (rc != RBX_OK) return rc;
   if (batch == 0) return RBX_OK;
   if (!d_w || !d_g || !d_dx) return fail(RBX_ERR_INVALID, "capsule_bilinear_dx: NULL tensor");
-  if (!cap_aligned(d_w) || !cap_aligned(d_g) || (g_stride_b & 3) != 0 || (g_stride_l & 3) != 0)
+  if (!aligned16(d_w) || !aligned16(d_g) || (g_stride_b & 3) != 0 || (g_stride_l & 3) != 0)
     return fail(RBX_ERR_UNSUPPORTED, "capsule_bilinear_dx: bases must be 16-byte aligned and strides multiples of 4 floats");
   const int B = static_cast<int>(batch);
   hipStream_t s = as_stream(stream);
@@ -584,7 +568,7 @@ extern "C" int rbx_capsule_bilinear_dw(const float* d_x, int64_t x_stride_b, int
     return RBX_OK;
   }
   if (!d_x || !d_g) return fail(RBX_ERR_INVALID, "capsule_bilinear_dw: NULL tensor");
-  if (!cap_aligned(d_x) || !cap_aligned(d_g) || (x_stride_b & 3) != 0 || (x_stride_l & 3) != 0 || (g_stride_b & 3) != 0 ||
+  if (!aligned16(d_x) || !aligned16(d_g) || (x_stride_b & 3) != 0 || (x_stride_l & 3) != 0 || (g_stride_b & 3) != 0 ||
       (g_stride_l & 3) != 0)
     return fail(RBX_ERR_UNSUPPORTED, "capsule_bilinear_dw: bases must be 16-byte aligned and strides multiples of 4 floats");
   const int splits = cap_splits(batch);

@@ -108,10 +108,8 @@ extern "C" int rbx_cin_outer_fwd(const float* d_x0, const float* d_xk, int64_t b
   if (batch == 0) return RBX_OK;
   if (d_z == nullptr) return fail(RBX_ERR_INVALID, "cin_outer_fwd: d_z is NULL");
   const size_t lds = cin_lds_bytes(n_fields, m, dim, false);
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(cin_outer_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          static_cast<int>(lds)) != hipSuccess)
-    return fail(RBX_ERR_LAUNCH, "cin_outer_fwd: cannot reserve %zu bytes of LDS", lds);
+  rc = allow_lds("cin_outer_fwd", cin_outer_fwd_kernel, lds);
+  if (rc != RBX_OK) return rc;
   hipLaunchKernelGGL(cin_outer_fwd_kernel, dim3(static_cast<unsigned>(batch)), dim3(256), lds, as_stream(stream), d_x0, d_xk,
                      n_fields, m, dim, d_z);
   return check_launch("cin_outer_fwd_kernel");
@@ -125,10 +123,8 @@ extern "C" int rbx_cin_outer_bwd(const float* d_x0, const float* d_xk, const flo
   if (batch == 0) return RBX_OK;
   if (d_dz == nullptr) return fail(RBX_ERR_INVALID, "cin_outer_bwd: d_dz is NULL");
   const size_t lds = cin_lds_bytes(n_fields, m, dim, true);
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(cin_outer_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          static_cast<int>(lds)) != hipSuccess)
-    return fail(RBX_ERR_LAUNCH, "cin_outer_bwd: cannot reserve %zu bytes of LDS", lds);
+  rc = allow_lds("cin_outer_bwd", cin_outer_bwd_kernel, lds);
+  if (rc != RBX_OK) return rc;
   hipLaunchKernelGGL(cin_outer_bwd_kernel, dim3(static_cast<unsigned>(batch)), dim3(256), lds, as_stream(stream), d_x0, d_xk,
                      d_dz, n_fields, m, dim, d_dx0, d_dxk);
   return check_launch("cin_outer_bwd_kernel");

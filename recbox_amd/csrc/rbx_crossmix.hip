@@ -24,8 +24,6 @@
 
 namespace rbx {
 
-typedef float cm_f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kCmTile = 16;                  // rows per workgroup = rows of the MFMA
 constexpr int kCmBlock = 256;
 constexpr int kCmMaxN = 640, kCmMaxE = 8, kCmMaxER = 256;
@@ -70,7 +68,7 @@ __device__ __forceinline__ void cm_gemm_in(const float* As, int S, const float* 
       base = G + (c - ER) * n;
       kst = 1;
     }
-    cm_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     for (int s = 0; s < ksteps; ++s) {
       const int k = 4 * s + quad;
       const float bv = (base != nullptr && k < n) ? base[k * kst] : 0.f;
@@ -91,7 +89,7 @@ __device__ __forceinline__ void cm_gemm_out(const float* As, int HS, const float
   for (int cb = wave; cb * 16 < n; cb += 4) {
     const int m = 16 * cb + col;
     const float* base = W + (m < n ? m : 0) * r;
-    cm_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     for (int s = 0; s < ksteps; ++s) {
       const int c = 4 * s + quad;
       const float bv = m < n ? base[(c >> rsh) * n * r + (c & (r - 1))] : 0.f;
@@ -277,9 +275,9 @@ __global__ __launch_bounds__(kCmBlock) void cm_xty_kernel(const XtyArgs x) {
   const long long c0 = x.rpc * blockIdx.x, c1 = c0 + x.rpc < x.B ? c0 + x.rpc : x.B;
   const float* A = x.A + z * x.az;
   const float* Bm = x.Bm != nullptr ? x.Bm + z * x.bz : nullptr;
-  cm_f32x4 acc[4];
+  f32x4 acc[4];
 #pragma unroll
-  for (int q = 0; q < 4; ++q) acc[q] = cm_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int q = 0; q < 4; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
   for (long long b = c0; b < c1; b += 4) {
     const long long row = b + quad;
     const bool ok = row < c1;
@@ -340,16 +338,6 @@ static size_t cm_part_floats(int n, int E, int r) {
   return m * kCmChunks;
 }
 
-// above 64 KiB of dynamic LDS a kernel has to be opted in; a refusal is reported here, not by the launch that would follow
-template <typename K>
-static int cm_allow_lds(const char* what, K kernel, size_t lds) {
-  if (lds <= 64 * 1024) return RBX_OK;
-  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-  if (e == hipSuccess) return RBX_OK;
-  (void)hipGetLastError();
-  return fail(RBX_ERR_LAUNCH, "%s: the opt-in to %zu bytes of dynamic LDS failed: %s", what, lds, hipGetErrorString(e));
-}
-
 static int cm_log2(int r) {
   int s = 0;
   while ((1 << s) < r) ++s;
@@ -397,7 +385,7 @@ extern "C" int rbx_crossmix_fwd(const float* d_x0, int64_t x0_stride, const floa
   a.x0 = d_x0; a.x0s = x0_stride; a.xl = d_xl; a.xls = xl_stride; a.U = d_u; a.V = d_v; a.C = d_c; a.G = d_g; a.b = d_b;
   a.out = d_out; a.os = out_stride; a.B = batch; a.n = n; a.E = experts; a.r = rank; a.rsh = cm_log2(rank);
   const size_t lds = cm_fwd_lds(n, experts * rank);
-  const int rc_lds = cm_allow_lds("crossmix_fwd", cm_fwd_kernel, lds);
+  const int rc_lds = allow_lds("crossmix_fwd", cm_fwd_kernel, lds);
   if (rc_lds != RBX_OK) return rc_lds;
   hipLaunchKernelGGL(cm_fwd_kernel, dim3(static_cast<unsigned>((batch + kCmTile - 1) / kCmTile)), dim3(kCmBlock), lds,
                      as_stream(stream), a);
@@ -438,7 +426,7 @@ extern "C" int rbx_crossmix_bwd(const float* d_dout, int64_t dout_stride, const 
   a.B = batch; a.n = n; a.E = E; a.r = r; a.rsh = cm_log2(r); a.acc = accumulate != 0;
   hipStream_t s = as_stream(stream);
   const size_t lds = cm_bwd_lds(n, ER);
-  const int rc_lds = cm_allow_lds("crossmix_bwd", cm_bwd_kernel, lds);
+  const int rc_lds = allow_lds("crossmix_bwd", cm_bwd_kernel, lds);
   if (rc_lds != RBX_OK) return rc_lds;
   hipLaunchKernelGGL(cm_bwd_kernel, dim3(static_cast<unsigned>((batch + kCmTile - 1) / kCmTile)), dim3(kCmBlock), lds, s, a);
   int rc2 = check_launch("crossmix_bwd");

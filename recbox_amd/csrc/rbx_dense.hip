@@ -188,11 +188,11 @@ static bool try_bxt_dw(const GemmCall& c, int* rc) {
   int kps = (K + sp - 1) / sp;
   kps = (kps + PBK - 1) / PBK * PBK;
   sp = (K + kps - 1) / kps;
-  static const bool attr_set = [] {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bxt_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               kBxPipeLds) == hipSuccess;
-  }();
-  (void)attr_set;
+  static bool attr_set = false;
+  if (!attr_set) {
+    if ((*rc = allow_lds("gemm_bxt_kernel", gemm_bxt_kernel, kBxPipeLds)) != RBX_OK) return true;
+    attr_set = true;
+  }
   hipLaunchKernelGGL(gemm_bxt_kernel, dim3(n_tiles * sp), dim3(PTHREADS), kBxPipeLds, c.s, c.A, c.lda, c.B, c.ldb, c.ws, M, N, K,
                      kps, c.tiles_n(), n_tiles);
   *rc = check_launch("gemm_bxt_kernel");
@@ -230,11 +230,11 @@ static bool try_planes(const GemmCall& c, int splits, int* rc) {
     hipLaunchKernelGGL(gemm_bx6_kernel, dim3(tn * tm), dim3(256), 0, c.s, c.A, c.lda, e.planes, kp, c.C, c.ldc, c.M, c.N, c.K,
                        c.bias, c.act, tm, tn, c.epi);
   } else {
-    static const bool attr_set = [] {
-      return hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bxp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 kBxPipeLds) == hipSuccess;
-    }();
-    (void)attr_set;
+    static bool attr_set = false;
+    if (!attr_set) {
+      if ((*rc = allow_lds("gemm_bxp_kernel", gemm_bxp_kernel, kBxPipeLds)) != RBX_OK) return true;
+      attr_set = true;
+    }
     const int tm2 = (c.M + PBM - 1) / PBM;
     hipLaunchKernelGGL(gemm_bxp_kernel, dim3(tn * tm2), dim3(PTHREADS), kBxPipeLds, c.s, c.A, c.lda, e.planes, kp, c.C, c.ldc,
                        c.M, c.N, c.K, c.bias, c.act, tm2, tn, c.epi);

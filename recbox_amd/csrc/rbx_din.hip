@@ -488,8 +488,6 @@ __global__ __launch_bounds__(256) void din_pool_bwd_kernel(const float* __restri
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------
-static bool din_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 static int din_splits(long long m) { return static_cast<int>((m + kDinDwRows - 1) / kDinDwRows); }
 
 // RBX_OK, or the refusal of a shape none of the kernels serves
@@ -506,18 +504,8 @@ static int din_check_shape(const char* what, int64_t batch, int32_t seq_len, int
 
 static int din_check_operands(const char* what, const float* hist, int64_t hist_stride, const float* target,
                               int64_t target_stride) {
-  if (!din_aligned(hist) || (hist_stride & 3) != 0 || (target != nullptr && (!din_aligned(target) || (target_stride & 3) != 0)))
+  if (!aligned16(hist) || (hist_stride & 3) != 0 || (target != nullptr && (!aligned16(target) || (target_stride & 3) != 0)))
     return fail(RBX_ERR_UNSUPPORTED, "%s: bases must be 16-byte aligned and sample strides multiples of 4 floats", what);
-  return RBX_OK;
-}
-
-// the kernels' dynamic LDS goes beyond the 64 KiB a launch may ask for unannounced: announced before every launch (the
-// attribute is per device, and the call is cheap), as rbx_attn_mfma.hip does
-template <typename K>
-static int din_set_lds(K kernel, size_t lds, const char* what) {
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          static_cast<int>(lds)) != hipSuccess)
-    return fail(RBX_ERR_LAUNCH, "%s: %zu bytes of LDS refused", what, lds);
   return RBX_OK;
 }
 
@@ -525,7 +513,7 @@ template <int NT>
 static int din_launch_fwd(const float* H, long long hs, const float* T, long long ts, int M, int L, int E, const float* W,
                           const float* bias, int n, int act, float* Y, hipStream_t s) {
   const size_t lds = (4 * kDinKC * kDinLdA + 2 * 4 * kDinKC * (32 * NT + 2)) * sizeof(float);
-  const int rc = din_set_lds(&din_pairs_fwd_kernel<NT>, lds, "din_pairs_fwd");
+  const int rc = allow_lds("din_pairs_fwd", &din_pairs_fwd_kernel<NT>, lds);
   if (rc != RBX_OK) return rc;
   hipLaunchKernelGGL((din_pairs_fwd_kernel<NT>), dim3((M + kDinBM - 1) / kDinBM), dim3(256), lds, s, H, hs, T, ts, M, L, E, W,
                      bias, n, act, Y);
@@ -546,7 +534,7 @@ extern "C" int rbx_din_pairs_fwd(const float* d_hist, int64_t hist_stride_b, con
   if (!d_hist || !d_target || !d_w || !d_y) return fail(RBX_ERR_INVALID, "din_pairs_fwd: NULL tensor");
   rc = din_check_operands("din_pairs_fwd", d_hist, hist_stride_b, d_target, target_stride_b);
   if (rc != RBX_OK) return rc;
-  if (!din_aligned(d_w)) return fail(RBX_ERR_UNSUPPORTED, "din_pairs_fwd: the weight must be 16-byte aligned");
+  if (!aligned16(d_w)) return fail(RBX_ERR_UNSUPPORTED, "din_pairs_fwd: the weight must be 16-byte aligned");
   const int M = static_cast<int>(batch * seq_len);
   hipStream_t s = as_stream(stream);
   rc = n > 32 ? din_launch_fwd<2>(d_hist, hist_stride_b, d_target, target_stride_b, M, seq_len, dim, d_w, d_bias, n, act, d_y, s)
@@ -576,7 +564,7 @@ extern "C" int rbx_din_pairs_bwd(const float* d_hist, int64_t hist_stride_b, con
   if (!d_hist || !d_target || !d_w || !d_dy || (act != 0 && !d_y)) return fail(RBX_ERR_INVALID, "din_pairs_bwd: NULL tensor");
   rc = din_check_operands("din_pairs_bwd", d_hist, hist_stride_b, d_target, target_stride_b);
   if (rc != RBX_OK) return rc;
-  if (!din_aligned(d_w) || (d_dhist != nullptr && !din_aligned(d_dhist)))
+  if (!aligned16(d_w) || (d_dhist != nullptr && !aligned16(d_dhist)))
     return fail(RBX_ERR_UNSUPPORTED, "din_pairs_bwd: the weight and dhist must be 16-byte aligned");
   const bool want_w = d_dw != nullptr || d_db != nullptr;
   if (want_w && (d_workspace == nullptr || workspace_bytes < rbx_din_pairs_bwd_workspace_size(batch, seq_len, dim, n)))
@@ -586,7 +574,7 @@ extern "C" int rbx_din_pairs_bwd(const float* d_hist, int64_t hist_stride_b, con
   if (d_dhist != nullptr || d_dtarget != nullptr) {
     const int S = seq_len >= kDinBM ? 1 : kDinBM / seq_len;
     const size_t lds = (kDinMaxN * kDinLdA + 4 * kDinMaxN * kDinEC) * sizeof(float);
-    rc = din_set_lds(&din_pairs_dx_kernel, lds, "din_pairs_bwd");
+    rc = allow_lds("din_pairs_bwd", &din_pairs_dx_kernel, lds);
     if (rc != RBX_OK) return rc;
     hipLaunchKernelGGL(din_pairs_dx_kernel, dim3((B + S - 1) / S), dim3(256), lds, s, d_hist, hist_stride_b, d_target,
                        target_stride_b, B, seq_len, dim, d_w, n, act, d_y, d_dy, d_dhist, d_dtarget, S);
@@ -634,7 +622,7 @@ extern "C" int rbx_din_pool_bwd(const float* d_dout, const float* d_weight, cons
   if (!d_dout || !d_weight || !d_hist) return fail(RBX_ERR_INVALID, "din_pool_bwd: NULL tensor");
   rc = din_check_operands("din_pool_bwd", d_hist, hist_stride_b, nullptr, 0);
   if (rc != RBX_OK) return rc;
-  if (d_dhist != nullptr && !din_aligned(d_dhist)) return fail(RBX_ERR_UNSUPPORTED, "din_pool_bwd: dhist must be 16-byte aligned");
+  if (d_dhist != nullptr && !aligned16(d_dhist)) return fail(RBX_ERR_UNSUPPORTED, "din_pool_bwd: dhist must be 16-byte aligned");
   hipLaunchKernelGGL(din_pool_bwd_kernel, dim3(static_cast<unsigned>(batch)), dim3(256), 0, as_stream(stream), d_dout, d_weight,
                      d_mask, d_hist, hist_stride_b, seq_len, dim, softmax, d_dscore, d_dhist);
   return check_launch("din_pool_bwd");

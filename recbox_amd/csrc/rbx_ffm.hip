@@ -36,7 +36,6 @@ template <int D4C, bool REDUCE>
 __global__ __launch_bounds__(256) void ffm_fwd_kernel(const FfmPack P, const int F, const int D, const long long B,
                                                       float* __restrict__ out, const long long out_stride_b,
                                                       int* __restrict__ status, const int spw, const unsigned n_tasks) {
-  typedef float v4f __attribute__((ext_vector_type(4)));
   __shared__ FfmField sf[RBX_MAX_FIELDS];
   __shared__ unsigned short s_pair[kFfmMaxPairs];
   {
@@ -102,12 +101,12 @@ __global__ __launch_bounds__(256) void ffm_fwd_kernel(const FfmPack P, const int
         } else {
           const float4 a = *reinterpret_cast<const float4*>(ra);
           const float4 b = *reinterpret_cast<const float4*>(rb);
-          v4f o;
+          f32x4 o;
           o.x = ok ? a.x * b.x : 0.f;
           o.y = ok ? a.y * b.y : 0.f;
           o.z = ok ? a.z * b.z : 0.f;
           o.w = ok ? a.w * b.w : 0.f;
-          if (live) __builtin_nontemporal_store(o, reinterpret_cast<v4f*>(orow + static_cast<size_t>(r) * 4));
+          if (live) __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(orow + static_cast<size_t>(r) * 4));
         }
       }
     }

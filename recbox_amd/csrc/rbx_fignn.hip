@@ -41,10 +41,9 @@
 // No atomics, every sum in a fixed order: two runs give the same bits.  No host read-back, nothing allocated, everything on the
 // caller's stream.  Every index is bounded by batch, n_fields and dim.
 #include "rbx_internal.h"
+#include "rbx_tile16.h"
 
 namespace rbx {
-
-typedef float fg_f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kFgMinF = 2, kFgMaxF = 48;    // the softmax walks a row in three chunks of 16 lanes
 constexpr int kFgMinA = 4, kFgMaxA = 32;    // dw_ih and dw_hh [3 A, A] are held in 24 NE^2 accumulator registers
@@ -75,7 +74,8 @@ struct FgArgs {
   int F, A, T, tshift;   // T = 1 << tshift: the samples of a tile, 16 or 8
 };
 
-static __host__ __device__ inline int fg_pad16(int n) { return (n + 15) & ~15; }
+// (its own name for pad16 of rbx_internal.h: tests/test_gpu_fignn_forms.py holds the layout lines below to their text)
+static __host__ __device__ inline int fg_pad16(int n) { return pad16(n); }
 static __host__ __device__ inline int fg_row1(int F, int A) { return 2 * F * A * A; }
 static __host__ __device__ inline int fg_row2(int A) { return 6 * A * A + 9 * A; }
 // a wavefront's scratch: the forward stages h_f and a_f [16][A + 4]; the backward adds da_f and dgi, dgh [16][3 A + 4]; both
@@ -104,65 +104,20 @@ static unsigned fg_grid(int64_t batch, int T) {
   return static_cast<unsigned>(need < kFgMaxGrid ? need : kFgMaxGrid);
 }
 
-__device__ __forceinline__ float fg_sum16(float v) {
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float fg_max16(float v) {
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
 // the sum over the four lanes that hold one column of an accumulator tile
 __device__ __forceinline__ float fg_sumq(float v) {
   v += __shfl_xor(v, 16, 64);
   v += __shfl_xor(v, 32, 64);
   return v;
 }
-__device__ __forceinline__ float fg_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
-__device__ __forceinline__ float fg_tanh(float x) { return 2.f / (1.f + expf(-2.f * x)) - 1.f; }
 
-// acc += A B over one 16 x 16 tile: rows m0 .. m0 + 15 of A, columns n0 .. n0 + 15 of B, k < K (a multiple of 4).  A[m][k] lies
-// at a[m lda + k] (AT: a[k lda + m]), B[k][n] at b[k ldb + n] (BT: b[n ldb + k]); rows of A from mlim, columns of B from nlim
-// and k from klim on count as zeros and are not read.  acc[r] is row m0 + 4 quad + r, column n0 + col.  Either operand may lie
-// in LDS or in global memory.
-template <bool AT, bool BT>
-__device__ __forceinline__ fg_f32x4 fg_mm(const float* a, const int lda, const int m0, const int mlim, const float* b, const int ldb,
-                                          const int n0, const int nlim, const int K, const int klim, fg_f32x4 acc, const int col,
-                                          const int quad) {
-  // The three bounds act as per-lane AND masks on the loaded bits, from clamped (always valid) row and column addresses, not
-  // as selects: a select keeps its condition in a scalar register pair for the whole loop.  Only LDS operands are called with
-  // klim < K, and a k from klim on still reads: up to 3 field rows past a sample's plane or slab (K = pad4(F), klim = F), or, on
-  // 8-sample tiles, the 8 rows behind a field's slab (K = 16, klim = 8), which for the last field are the start of Y, or of
-  // s, d and the scratch.  Those addresses lie inside the workgroup's LDS: 8-sample tiles occur only from 30 fields on, where
-  // the 4 F T floats of s, d, ds, dd alone exceed 8 rows of A + 4; and 3 T rows past Y (K = pad4(F)) are fewer floats than
-  // s .. dd plus the wavefronts' scratch (four times at least 16 x 2 (A + 4) at the small F where s .. dd are short).  What is
-  // read there is masked to +0.
-  const int mi = m0 + col < mlim ? m0 + col : mlim - 1, ni = n0 + col < nlim ? n0 + col : nlim - 1;
-  int amask = m0 + col < mlim ? -1 : 0, bmask = n0 + col < nlim ? -1 : 0;
-  asm volatile("" : "+v"(amask), "+v"(bmask));
-  const float* ap = AT ? a + quad * lda + mi : a + mi * lda + quad;
-  const float* bp = BT ? b + ni * ldb + quad : b + quad * ldb + ni;
-  const int as = AT ? 4 * lda : 4, bs = BT ? 4 : 4 * ldb;
-  for (int k = quad; k < K; k += 4) {
-    const int km = k < klim ? -1 : 0;
-    const float av = __int_as_float(__float_as_int(*ap) & amask & km), bv = __int_as_float(__float_as_int(*bp) & bmask & km);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
-    ap += as;
-    bp += bs;
-  }
-  return acc;
-}
-
-__device__ __forceinline__ void fg_store(float* c, const int ldc, const int m0, const int mlim, const int n0, const int nlim,
-                                         const fg_f32x4 acc, const int col, const int quad) {
-  if (n0 + col < nlim) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      if (m0 + 4 * quad + r < mlim) c[(m0 + 4 * quad + r) * ldc + n0 + col] = acc[r];
-  }
-}
+// The products are mm16 / store16 of rbx_tile16.h, whose klim < K reads past the operand and asks the caller to show that those
+// addresses are LDS of the workgroup.  Here only LDS operands are called with klim < K, and a k from klim on reads up to 3 field
+// rows past a sample's plane or slab (K = pad4(F), klim = F), or, on 8-sample tiles, the 8 rows behind a field's slab (K = 16,
+// klim = 8), which for the last field are the start of Y, or of s, d and the scratch.  Those addresses lie inside the
+// workgroup's LDS: 8-sample tiles occur only from 30 fields on, where the 4 F T floats of s, d, ds, dd alone exceed 8 rows of
+// A + 4; and 3 T rows past Y (K = pad4(F)) are fewer floats than s .. dd plus the wavefronts' scratch (four times at least
+// 16 x 2 (A + 4) at the small F where s .. dd are short).
 
 // the tile's rows of field f, src[(b0 + s) F + f][..], s < 16, into dst [16][A + 4]; zeros for samples from nb on
 __device__ __forceinline__ void fg_stage(const float* src, const long long b0, const int nb, const int f, const int F, const int A,
@@ -216,14 +171,14 @@ __device__ __forceinline__ void fg_plane(const float* sv, const float* dv, const
       e[c] = al;
       m = fmaxf(m, al);
     }
-    m = fg_max16(m);
+    m = group_max<16, kWave>(m);
     float sum = 0.f;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       e[c] = e[c] > -INFINITY ? expf(e[c] - m) : 0.f;
       sum += e[c];
     }
-    sum = fg_sum16(sum);
+    sum = group_sum<16, kWave>(sum);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const int j = col + 16 * c;
@@ -265,8 +220,8 @@ __device__ __forceinline__ void fg_hout(const FgArgs& g, const long long b0, con
     __syncthreads();
     if (ok)
       for (int nt = 0; 16 * nt < A; ++nt)
-        fg_store(X + f * g.T * ld, ld, 0, g.T, 16 * nt, A,
-                 fg_mm<false, true>(th, ld, 0, kFgTile, g.wout + f * A * A, A, 16 * nt, A, A, A, fg_f32x4{0.f, 0.f, 0.f, 0.f}, col, quad),
+        store16(X + f * g.T * ld, ld, 0, g.T, 16 * nt, A,
+                 mm16<false, true>(th, ld, 0, kFgTile, g.wout + f * A * A, A, 16 * nt, A, A, A, f32x4{0.f, 0.f, 0.f, 0.f}, col, quad),
                  col, quad);
     __syncthreads();
   }
@@ -283,8 +238,8 @@ __device__ __forceinline__ void fg_aggr(const FgArgs& g, const long long b0, con
     __syncthreads();
     for (int mt = 0; 16 * mt < F; ++mt)
       for (int nt = 0; 16 * nt < A; ++nt)
-        fg_store(Y + s * ld, g.T * ld, 16 * mt, F, 16 * nt, A,
-                 fg_mm<false, false>(pl, ldp, 16 * mt, F, X + s * ld, g.T * ld, 16 * nt, A, K, F, fg_f32x4{0.f, 0.f, 0.f, 0.f}, col,
+        store16(Y + s * ld, g.T * ld, 16 * mt, F, 16 * nt, A,
+                 mm16<false, false>(pl, ldp, 16 * mt, F, X + s * ld, g.T * ld, 16 * nt, A, K, F, f32x4{0.f, 0.f, 0.f, 0.f}, col,
                                      quad),
                  col, quad);
     __syncthreads();
@@ -344,12 +299,12 @@ __global__ __launch_bounds__(256) void fignn_step_fwd_kernel(const FgArgs ga) {
         for (int nt = 0; nt < NE; ++nt) {
           if (16 * nt < A) {
             const int n = 16 * nt + col;
-            fg_f32x4 acc = fg_mm<false, true>(Y + f * g.T * ld, ld, 0, g.T, g.win + f * A * A, A, 16 * nt, A, A, A,
-                                              fg_f32x4{0.f, 0.f, 0.f, 0.f}, col, quad);
+            f32x4 acc = mm16<false, true>(Y + f * g.T * ld, ld, 0, g.T, g.win + f * A * A, A, 16 * nt, A, A, A,
+                                              f32x4{0.f, 0.f, 0.f, 0.f}, col, quad);
             const float bp = n < A ? g.biasp[n] : 0.f;
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[r] += bp;
-            fg_store(ta, ld, 0, kFgTile, 16 * nt, A, acc, col, quad);
+            store16(ta, ld, 0, kFgTile, 16 * nt, A, acc, col, quad);
           }
         }
       }
@@ -359,11 +314,11 @@ __global__ __launch_bounds__(256) void fignn_step_fwd_kernel(const FgArgs ga) {
         for (int nt = 0; nt < NE; ++nt) {
           if (16 * nt < A) {
             const int n = 16 * nt + col;
-            fg_f32x4 gi[3], gh[3];
+            f32x4 gi[3], gh[3];
 #pragma unroll
             for (int q = 0; q < 3; ++q) {
-              gi[q] = fg_mm<false, true>(ta, ld, 0, kFgTile, g.wih + q * A * A, A, 16 * nt, A, A, A, fg_f32x4{0.f, 0.f, 0.f, 0.f}, col, quad);
-              gh[q] = fg_mm<false, true>(th, ld, 0, kFgTile, g.whh + q * A * A, A, 16 * nt, A, A, A, fg_f32x4{0.f, 0.f, 0.f, 0.f}, col, quad);
+              gi[q] = mm16<false, true>(ta, ld, 0, kFgTile, g.wih + q * A * A, A, 16 * nt, A, A, A, f32x4{0.f, 0.f, 0.f, 0.f}, col, quad);
+              gh[q] = mm16<false, true>(th, ld, 0, kFgTile, g.whh + q * A * A, A, 16 * nt, A, A, A, f32x4{0.f, 0.f, 0.f, 0.f}, col, quad);
             }
             if (n < A) {
               float bi[3], bh[3];
@@ -376,9 +331,9 @@ __global__ __launch_bounds__(256) void fignn_step_fwd_kernel(const FgArgs ga) {
               for (int r = 0; r < 4; ++r) {
                 const int s = 4 * quad + r;
                 if (s < nb) {
-                  const float rg = fg_sigmoid(gi[0][r] + bi[0] + gh[0][r] + bh[0]);
-                  const float zg = fg_sigmoid(gi[1][r] + bi[1] + gh[1][r] + bh[1]);
-                  const float ng = fg_tanh(gi[2][r] + bi[2] + rg * (gh[2][r] + bh[2]));
+                  const float rg = sigmoidf_fast(gi[0][r] + bi[0] + gh[0][r] + bh[0]);
+                  const float zg = sigmoidf_fast(gi[1][r] + bi[1] + gh[1][r] + bh[1]);
+                  const float ng = tanhf_fast(gi[2][r] + bi[2] + rg * (gh[2][r] + bh[2]));
                   const long long at = ((b0 + s) * F + f) * A + n;
                   g.y[at] = (1.f - zg) * ng + zg * th[s * ld + n] + g.h0[at];
                 }
@@ -398,9 +353,9 @@ __global__ __launch_bounds__(256) void fignn_step_bwd_kernel(const FgArgs ga) {
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), col = lane & 15, quad = lane >> 4, nw = blockDim.x >> 6;
   const bool want_w = ga.part1 != nullptr;
   const long long tiles = (ga.B + ga.T - 1) >> ga.tshift;
-  const fg_f32x4 zero = fg_f32x4{0.f, 0.f, 0.f, 0.f};
+  const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  fg_f32x4 dwih[3 * NE][NE], dwhh[3 * NE][NE];     // [16 m + 4 quad + r][16 n + col] over this wavefront's fields and tiles
+  f32x4 dwih[3 * NE][NE], dwhh[3 * NE][NE];     // [16 m + 4 quad + r][16 n + col] over this wavefront's fields and tiles
   float dbi[3][NE], dbn[NE], dbp[NE], dws[NE], dwd[NE];   // column 16 n + col: db_ih, the n gate of db_hh, dbias_p, dw_attn
 #pragma unroll
   for (int n = 0; n < NE; ++n) {
@@ -433,27 +388,27 @@ __global__ __launch_bounds__(256) void fignn_step_bwd_kernel(const FgArgs ga) {
         for (int nt = 0; nt < NE; ++nt) {
           if (16 * nt < A) {
             const int n = 16 * nt + col;
-            fg_f32x4 acc = fg_mm<false, true>(Yf, ld, 0, g.T, g.win + f * A * A, A, 16 * nt, A, A, A, zero, col, quad);
+            f32x4 acc = mm16<false, true>(Yf, ld, 0, g.T, g.win + f * A * A, A, 16 * nt, A, A, A, zero, col, quad);
             const float bp = n < A ? g.biasp[n] : 0.f;
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[r] += bp;
-            fg_store(ta, ld, 0, kFgTile, 16 * nt, A, acc, col, quad);
+            store16(ta, ld, 0, kFgTile, 16 * nt, A, acc, col, quad);
           }
         }
       }
       __syncthreads();
-      fg_f32x4 dhp[NE];                      // dy z: the part of dh that does not pass the cell's matrices
+      f32x4 dhp[NE];                      // dy z: the part of dh that does not pass the cell's matrices
       if (ok) {
 #pragma unroll
         for (int nt = 0; nt < NE; ++nt) {
           dhp[nt] = zero;
           if (16 * nt < A) {
             const int n = 16 * nt + col;
-            fg_f32x4 gi[3], gh[3];
+            f32x4 gi[3], gh[3];
 #pragma unroll
             for (int q = 0; q < 3; ++q) {
-              gi[q] = fg_mm<false, true>(ta, ld, 0, kFgTile, g.wih + q * A * A, A, 16 * nt, A, A, A, zero, col, quad);
-              gh[q] = fg_mm<false, true>(th, ld, 0, kFgTile, g.whh + q * A * A, A, 16 * nt, A, A, A, zero, col, quad);
+              gi[q] = mm16<false, true>(ta, ld, 0, kFgTile, g.wih + q * A * A, A, 16 * nt, A, A, A, zero, col, quad);
+              gh[q] = mm16<false, true>(th, ld, 0, kFgTile, g.whh + q * A * A, A, 16 * nt, A, A, A, zero, col, quad);
             }
             if (n < A) {
               float bi[3], bh[3];
@@ -467,9 +422,9 @@ __global__ __launch_bounds__(256) void fignn_step_bwd_kernel(const FgArgs ga) {
                 const int s = 4 * quad + r;
                 const float dyv = s < nb ? g.dy[((b0 + s) * F + f) * A + n] : 0.f;
                 const float ghn = gh[2][r] + bh[2];
-                const float rg = fg_sigmoid(gi[0][r] + bi[0] + gh[0][r] + bh[0]);
-                const float zg = fg_sigmoid(gi[1][r] + bi[1] + gh[1][r] + bh[1]);
-                const float ng = fg_tanh(gi[2][r] + bi[2] + rg * ghn);
+                const float rg = sigmoidf_fast(gi[0][r] + bi[0] + gh[0][r] + bh[0]);
+                const float zg = sigmoidf_fast(gi[1][r] + bi[1] + gh[1][r] + bh[1]);
+                const float ng = tanhf_fast(gi[2][r] + bi[2] + rg * ghn);
                 const float dnp = dyv * (1.f - zg) * (1.f - ng * ng);
                 const float dzp = dyv * (th[s * ld + n] - ng) * zg * (1.f - zg);
                 const float drp = dnp * ghn * rg * (1.f - rg);
@@ -495,11 +450,11 @@ __global__ __launch_bounds__(256) void fignn_step_bwd_kernel(const FgArgs ga) {
         for (int nt = 0; nt < NE; ++nt) {
           if (16 * nt < A) {
             const int n = 16 * nt + col;
-            const fg_f32x4 da = fg_mm<false, false>(dgi, ld3, 0, kFgTile, g.wih, A, 16 * nt, A, A3, A3, zero, col, quad);
-            fg_store(tda, ld, 0, kFgTile, 16 * nt, A, da, col, quad);
+            const f32x4 da = mm16<false, false>(dgi, ld3, 0, kFgTile, g.wih, A, 16 * nt, A, A3, A3, zero, col, quad);
+            store16(tda, ld, 0, kFgTile, 16 * nt, A, da, col, quad);
             dbp[nt] += (da[0] + da[1]) + (da[2] + da[3]);
             if (g.dh != nullptr) {
-              const fg_f32x4 d = fg_mm<false, false>(dgh, ld3, 0, kFgTile, g.whh, A, 16 * nt, A, A3, A3, dhp[nt], col, quad);
+              const f32x4 d = mm16<false, false>(dgh, ld3, 0, kFgTile, g.whh, A, 16 * nt, A, A3, A3, dhp[nt], col, quad);
 #pragma unroll
               for (int r = 0; r < 4; ++r) {
                 const int s = 4 * quad + r;
@@ -510,15 +465,15 @@ __global__ __launch_bounds__(256) void fignn_step_bwd_kernel(const FgArgs ga) {
 #pragma unroll
               for (int m = 0; m < 3 * NE; ++m)
                 if (16 * m < A3) {
-                  dwih[m][nt] = fg_mm<true, false>(dgi, ld3, 16 * m, A3, ta, ld, 16 * nt, A, kFgTile, kFgTile, dwih[m][nt], col, quad);
-                  dwhh[m][nt] = fg_mm<true, false>(dgh, ld3, 16 * m, A3, th, ld, 16 * nt, A, kFgTile, kFgTile, dwhh[m][nt], col, quad);
+                  dwih[m][nt] = mm16<true, false>(dgi, ld3, 16 * m, A3, ta, ld, 16 * nt, A, kFgTile, kFgTile, dwih[m][nt], col, quad);
+                  dwhh[m][nt] = mm16<true, false>(dgh, ld3, 16 * m, A3, th, ld, 16 * nt, A, kFgTile, kFgTile, dwhh[m][nt], col, quad);
                 }
             }
           }
         }
       }
       __syncthreads();                       // da_f
-      fg_f32x4 dag[NE];
+      f32x4 dag[NE];
       if (ok) {
 #pragma unroll
         for (int nt = 0; nt < NE; ++nt) {
@@ -529,7 +484,7 @@ __global__ __launch_bounds__(256) void fignn_step_bwd_kernel(const FgArgs ga) {
 #pragma unroll
               for (int mt = 0; mt < NE; ++mt)
                 if (16 * mt < A) {
-                  const fg_f32x4 w = fg_mm<true, false>(tda, ld, 16 * mt, A, Yf, ld, 16 * nt, A, kFgTile, g.T, zero, col, quad);
+                  const f32x4 w = mm16<true, false>(tda, ld, 16 * mt, A, Yf, ld, 16 * nt, A, kFgTile, g.T, zero, col, quad);
 #pragma unroll
                   for (int r = 0; r < 4; ++r) {
                     const int m = 16 * mt + 4 * quad + r, n = 16 * nt + col;
@@ -537,7 +492,7 @@ __global__ __launch_bounds__(256) void fignn_step_bwd_kernel(const FgArgs ga) {
                   }
                 }
             }
-            dag[nt] = fg_mm<false, false>(tda, ld, 0, kFgTile, g.win + f * A * A, A, 16 * nt, A, A, A, zero, col, quad);
+            dag[nt] = mm16<false, false>(tda, ld, 0, kFgTile, g.win + f * A * A, A, 16 * nt, A, A, A, zero, col, quad);
           }
         }
       }
@@ -545,7 +500,7 @@ __global__ __launch_bounds__(256) void fignn_step_bwd_kernel(const FgArgs ga) {
       if (ok) {
 #pragma unroll
         for (int nt = 0; nt < NE; ++nt)
-          if (16 * nt < A) fg_store(Yf, ld, 0, g.T, 16 * nt, A, dag[nt], col, quad);
+          if (16 * nt < A) store16(Yf, ld, 0, g.T, 16 * nt, A, dag[nt], col, quad);
       }
       __syncthreads();                       // the scratch is written again; after the last field: Y = daggr
     }
@@ -560,12 +515,12 @@ __global__ __launch_bounds__(256) void fignn_step_bwd_kernel(const FgArgs ga) {
       __syncthreads();
       float cd[3] = {0.f, 0.f, 0.f};         // dd of the columns col + 16 c
       for (int mt = 0; 16 * mt < F; ++mt) {
-        fg_f32x4 dg[3];
+        f32x4 dg[3];
         float p[3][4], rs[4] = {0.f, 0.f, 0.f, 0.f}, dsr[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
           dg[c] = zero;
-          if (16 * c < F) dg[c] = fg_mm<false, true>(Ys, g.T * ld, 16 * mt, F, Xs, g.T * ld, 16 * c, F, A, A, zero, col, quad);
+          if (16 * c < F) dg[c] = mm16<false, true>(Ys, g.T * ld, 16 * mt, F, Xs, g.T * ld, 16 * c, F, A, A, zero, col, quad);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int i = 16 * mt + 4 * quad + r, j = 16 * c + col;
@@ -574,7 +529,7 @@ __global__ __launch_bounds__(256) void fignn_step_bwd_kernel(const FgArgs ga) {
           }
         }
 #pragma unroll
-        for (int r = 0; r < 4; ++r) rs[r] = fg_sum16(rs[r]);
+        for (int r = 0; r < 4; ++r) rs[r] = group_sum<16, kWave>(rs[r]);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
 #pragma unroll
@@ -589,7 +544,7 @@ __global__ __launch_bounds__(256) void fignn_step_bwd_kernel(const FgArgs ga) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int i = 16 * mt + 4 * quad + r;
-          const float t = fg_sum16(dsr[r]);
+          const float t = group_sum<16, kWave>(dsr[r]);
           if (col == 0 && i < F) dsv[i * g.T + s] = t;
         }
       }
@@ -601,8 +556,8 @@ __global__ __launch_bounds__(256) void fignn_step_bwd_kernel(const FgArgs ga) {
       __syncthreads();                       // hout of the sample is read
       for (int mt = 0; 16 * mt < F; ++mt)
         for (int nt = 0; 16 * nt < A; ++nt)
-          fg_store(Xs, g.T * ld, 16 * mt, F, 16 * nt, A,
-                   fg_mm<true, false>(scr, ldp, 16 * mt, F, Ys, g.T * ld, 16 * nt, A, KF, F, zero, col, quad), col, quad);
+          store16(Xs, g.T * ld, 16 * mt, F, 16 * nt, A,
+                   mm16<true, false>(scr, ldp, 16 * mt, F, Ys, g.T * ld, 16 * nt, A, KF, F, zero, col, quad), col, quad);
       __syncthreads();                       // the plane is written again; after the last sample: X = dhout, ds, dd
     }
 
@@ -624,7 +579,7 @@ __global__ __launch_bounds__(256) void fignn_step_bwd_kernel(const FgArgs ga) {
 #pragma unroll
               for (int mt = 0; mt < NE; ++mt)
                 if (16 * mt < A) {
-                  const fg_f32x4 w = fg_mm<true, false>(Xf, ld, 16 * mt, A, th, ld, 16 * nt, A, kFgTile, g.T, zero, col, quad);
+                  const f32x4 w = mm16<true, false>(Xf, ld, 16 * mt, A, th, ld, 16 * nt, A, kFgTile, g.T, zero, col, quad);
 #pragma unroll
                   for (int r = 0; r < 4; ++r) {
                     const int m = 16 * mt + 4 * quad + r;
@@ -632,8 +587,8 @@ __global__ __launch_bounds__(256) void fignn_step_bwd_kernel(const FgArgs ga) {
                   }
                 }
             }
-            fg_f32x4 d = zero;
-            if (g.dh != nullptr) d = fg_mm<false, false>(Xf, ld, 0, g.T, g.wout + f * A * A, A, 16 * nt, A, A, A, zero, col, quad);
+            f32x4 d = zero;
+            if (g.dh != nullptr) d = mm16<false, false>(Xf, ld, 0, g.T, g.wout + f * A * A, A, 16 * nt, A, A, A, zero, col, quad);
             if (n < A) {
               const float ws = g.wattn[n], wd = g.wattn[A + n];
 #pragma unroll
@@ -744,8 +699,6 @@ __global__ __launch_bounds__(256) void fignn_tail_kernel(const FgTail t) {
   }
 }
 
-static bool fg_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 static int fg_check(const char* what, int64_t batch, int32_t n_fields, int32_t dim, int32_t dtype) {
   if (batch < 0) return fail(RBX_ERR_INVALID, "%s: batch=%lld", what, static_cast<long long>(batch));
   if (!rbx_fignn_step_supported(n_fields, dim))
@@ -757,9 +710,8 @@ static int fg_check(const char* what, int64_t batch, int32_t n_fields, int32_t d
 
 template <typename K>
 static int fg_launch(const char* what, K kernel, unsigned grid, int nw, size_t lds, hipStream_t s, const FgArgs& args) {
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess)
-    return fail(RBX_ERR_UNSUPPORTED, "%s: %zu bytes of dynamic LDS refused", what, lds);
+  const int rc = allow_lds(what, kernel, lds);
+  if (rc != RBX_OK) return rc;
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * nw), lds, s, args);
   return RBX_OK;
 }
@@ -782,7 +734,7 @@ extern "C" int rbx_fignn_step_fwd(const float* d_h, const float* d_h0, const flo
   if (batch == 0) return RBX_OK;
   if (!d_h || !d_h0 || !d_w_attn || !d_w_out || !d_w_in || !d_bias_p || !d_w_ih || !d_w_hh || !d_b_ih || !d_b_hh || !d_y)
     return fail(RBX_ERR_INVALID, "fignn_step_fwd: NULL tensor");
-  if (!fg_aligned(d_h) || !fg_aligned(d_h0) || !fg_aligned(d_w_attn))
+  if (!aligned16(d_h) || !aligned16(d_h0) || !aligned16(d_w_attn))
     return fail(RBX_ERR_UNSUPPORTED, "fignn_step_fwd: h, h0 and w_attn must be 16-byte aligned");
   FgArgs args = {};
   args.h = d_h; args.h0 = d_h0; args.wattn = d_w_attn; args.wout = d_w_out; args.win = d_w_in; args.biasp = d_bias_p;
@@ -817,7 +769,7 @@ extern "C" int rbx_fignn_step_bwd(const float* d_dy, const float* d_h, const flo
   if (batch == 0) return RBX_OK;
   if (!d_dy || !d_h || !d_h0 || !d_w_attn || !d_w_out || !d_w_in || !d_bias_p || !d_w_ih || !d_w_hh || !d_b_ih || !d_b_hh)
     return fail(RBX_ERR_INVALID, "fignn_step_bwd: NULL tensor");
-  if (!fg_aligned(d_h) || !fg_aligned(d_h0) || !fg_aligned(d_w_attn))
+  if (!aligned16(d_h) || !aligned16(d_h0) || !aligned16(d_w_attn))
     return fail(RBX_ERR_UNSUPPORTED, "fignn_step_bwd: h, h0 and w_attn must be 16-byte aligned");
   const bool want_w = d_dw_attn || d_dw_out || d_dw_in || d_dbias_p || d_dw_ih || d_dw_hh || d_db_ih || d_db_hh;
   if (want_w && (d_workspace == nullptr || workspace_bytes < rbx_fignn_step_bwd_workspace_size(batch, n_fields, dim)))

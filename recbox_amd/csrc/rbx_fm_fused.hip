@@ -1141,8 +1141,7 @@ extern "C" int rbx_fm_bwd(const rbx_field_t* emb, const rbx_field_t* lr, int32_t
         const size_t lds = ta_num_lds_bytes(n_num, D);
         static bool attr_set = false;
         if (!attr_set) {
-          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fm_numeric_blocks_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+          if ((rc = allow_lds("fm_numeric_blocks_kernel", fm_numeric_blocks_kernel, 160 * 1024)) != RBX_OK) return rc;
           attr_set = true;
         }
         hipLaunchKernelGGL(fm_numeric_blocks_kernel, dim3(nblk), dim3(512), lds, s, np, static_cast<long long>(batch), D,

@@ -47,17 +47,12 @@
 
 namespace rbx {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 enum GruCell : int { kAgru = 0, kAugru = 1, kGru = 2 };    // the first two are the C ABI's cell codes of rbx_attgru_*
 
 constexpr int kGruTile = 16;               // samples per workgroup = rows of the MFMA
 constexpr int kGruMinH = 4, kGruMaxH = 128;
 constexpr int kGruSaved = 5;               // r, z, n, gh_n, h_prev
 constexpr int kGruMaxWaves = kGruMaxH / 16;
-
-__device__ __forceinline__ float gru_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
-__device__ __forceinline__ float gru_tanh(float x) { return 2.f / (1.f + expf(-2.f * x)) - 1.f; }
 
 // lengths of the lane's 4 samples, clamped to [0, L]; 0 for rows beyond the batch
 __device__ __forceinline__ void gru_lengths(const void* lengths, int len_dt, long long b_first, long long B, int L,
@@ -132,9 +127,9 @@ __global__ __launch_bounds__(16 * KSMAX) void gru_fwd_kernel(
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const float rg = gru_sigmoid(x[0][r] + acc[0][r]);
-      const float zg = kZ ? gru_sigmoid(x[1][r] + acc[1][r]) : 0.f;
-      const float ng = gru_tanh(x[2][r] + rg * acc[2][r]);
+      const float rg = sigmoidf_fast(x[0][r] + acc[0][r]);
+      const float zg = kZ ? sigmoidf_fast(x[1][r] + acc[1][r]) : 0.f;
+      const float ng = tanhf_fast(x[2][r] + rg * acc[2][r]);
       float hnew;
       if constexpr (kAtt) {
         const float c = kZ ? a[r] * zg : a[r];
@@ -269,8 +264,6 @@ __global__ __launch_bounds__(16 * KSMAX) void gru_bwd_kernel(
   }
 }
 
-static bool gru_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // cell: NULL for the plain GRU's entry points, else the C ABI's cell code (0 / 1) as the caller gave it
 static int gru_check(const char* what, int64_t batch, int32_t seq_len, int32_t hidden, const int32_t* cell, int32_t dtype,
                      const void* lengths, int32_t lengths_dtype) {
@@ -310,7 +303,7 @@ static int gru_fwd(const char* what, const int32_t* cell, const float* d_gi, int
   if (rc != RBX_OK) return rc;
   if (batch == 0) return RBX_OK;
   if (!d_gi || (cell && !d_att) || !d_w_hh || !d_out || !d_saved || !d_hn) return fail(RBX_ERR_INVALID, "%s: NULL tensor", what);
-  if (!gru_aligned(d_gi) || (gi_stride_b & 3) != 0 || (gi_stride_t & 3) != 0 || gi_stride_t < 3 * hidden)
+  if (!aligned16(d_gi) || (gi_stride_b & 3) != 0 || (gi_stride_t & 3) != 0 || gi_stride_t < 3 * hidden)
     return fail(RBX_ERR_UNSUPPORTED, "%s: gi must be 16-byte aligned with strides that are multiples of 4 floats", what);
   const dim3 grid(static_cast<unsigned>((batch + kGruTile - 1) / kGruTile)), block(64 * ((hidden + 15) / 16));
   gru_instantiation(hidden, cell, [&](auto ks, auto c) {
@@ -330,7 +323,7 @@ static int gru_bwd(const char* what, const int32_t* cell, const float* d_saved, 
   if (batch == 0) return RBX_OK;
   if (!d_saved || (cell && (!d_att || !d_datt)) || !d_w_hh || !d_dgi || !d_dghn || !d_dh0)
     return fail(RBX_ERR_INVALID, "%s: NULL tensor", what);
-  if (d_dout != nullptr && (!gru_aligned(d_dout) || (dout_stride_b & 3) != 0 || (dout_stride_t & 3) != 0 || dout_stride_t < hidden))
+  if (d_dout != nullptr && (!aligned16(d_dout) || (dout_stride_b & 3) != 0 || (dout_stride_t & 3) != 0 || dout_stride_t < hidden))
     return fail(RBX_ERR_UNSUPPORTED, "%s: d_out must be 16-byte aligned with strides that are multiples of 4 floats", what);
   const dim3 grid(static_cast<unsigned>((batch + kGruTile - 1) / kGruTile)), block(64 * ((hidden + 15) / 16));
   gru_instantiation(hidden, cell, [&](auto ks, auto c) {

@@ -192,11 +192,6 @@ __global__ __launch_bounds__(kIbBlock) void ib_bwd_kernel(const IbArgs a) {
   }
 }
 
-template <typename K>
-static void ib_allow_lds(K kernel, size_t lds) {
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-}
-
 static bool ib_rows_ok(const void* p, int64_t stride, int D) {
   return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && stride >= D && (stride & 3) == 0;
 }
@@ -244,7 +239,8 @@ extern "C" int rbx_inbatch_band_fwd(const float* d_u, int64_t u_stride, const fl
   a.u = d_u; a.v = d_v; a.w = d_w; a.us = u_stride; a.vs = v_stride; a.scores = d_scores; a.ss = scores_stride;
   a.ru = d_ru; a.rv = d_rv; a.B = batch; a.D = dim; a.n = n_neg; a.eps = eps; a.inv_t = inv_temperature;
   const size_t lds = ib_fwd_lds(dim, n_neg);
-  ib_allow_lds(ib_fwd_kernel, lds);
+  const int rc_lds = allow_lds("inbatch_band_fwd", ib_fwd_kernel, lds);
+  if (rc_lds != RBX_OK) return rc_lds;
   hipLaunchKernelGGL(ib_fwd_kernel, dim3(static_cast<unsigned>((batch + kIbTile - 1) / kIbTile)), dim3(kIbBlock), lds,
                      as_stream(stream), a);
   return check_launch("inbatch_band_fwd");
@@ -269,7 +265,8 @@ extern "C" int rbx_inbatch_band_bwd(const float* d_g, int64_t g_stride, const fl
   a.g = d_g; a.gs = g_stride; a.du = d_du; a.dv = d_dv; a.dw = d_dw; a.dus = du_stride; a.dvs = dv_stride;
   a.B = batch; a.D = dim; a.n = n_neg; a.eps = eps; a.inv_t = inv_temperature;
   const size_t lds = ib_bwd_lds(dim, n_neg);
-  ib_allow_lds(ib_bwd_kernel, lds);
+  const int rc_lds = allow_lds("inbatch_band_bwd", ib_bwd_kernel, lds);
+  if (rc_lds != RBX_OK) return rc_lds;
   hipLaunchKernelGGL(ib_bwd_kernel, dim3(static_cast<unsigned>((batch + kIbTile - 1) / kIbTile)), dim3(kIbBlock), lds,
                      as_stream(stream), a);
   return check_launch("inbatch_band_bwd");

@@ -100,11 +100,43 @@ __device__ __forceinline__ float add_rn(float a, float b) {
 }
 __device__ __forceinline__ float fma_rn(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 
-template <int W>
+// Sum and maximum over the aligned groups of W lanes (W a power of two, at most 64), offsets descending; every lane of a group
+// gets the result.  SW is the width handed to __shfl_xor.  lane ^ o with o < W never leaves the lane's group, so every SW >= W
+// names the same partner and gives the same bits, but not the same instructions: below the wavefront's width __shfl_xor adds a
+// bounds compare and select per step that the compiler does not fold away.  The kernels written on group_sum<W> were tuned and
+// measured with those (SW = W, the default); the 16-lane groups of the MFMA tile kernels shuffle at the wavefront's width
+// (group_sum<16, kWave>).  One of the two can go once the other's kernels are measured with it.
+template <int W, int SW = W>
 __device__ __forceinline__ float group_sum(float v) {
 #pragma unroll
-  for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, W);
+  for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, SW);
   return v;
+}
+template <int W, int SW = W>
+__device__ __forceinline__ float group_max(float v) {
+#pragma unroll
+  for (int o = W / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, SW));
+  return v;
+}
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));   // an MFMA 16 x 16 accumulator; a 16-byte aligned dwordx4
+
+__device__ __forceinline__ float sigmoidf_fast(float x) { return 1.f / (1.f + expf(-x)); }
+__device__ __forceinline__ float tanhf_fast(float x) { return 2.f / (1.f + expf(-2.f * x)) - 1.f; }
+
+__host__ __device__ inline int pad16(int n) { return (n + 15) & ~15; }
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// Opt a kernel in to `lds` bytes of dynamic LDS where that is more than the 64 KiB every kernel may have; to be called before
+// the launch, which it refuses with a message of its own.
+template <typename K>
+int allow_lds(const char* what, K kernel, size_t lds) {
+  if (lds <= 64 * 1024) return RBX_OK;
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           static_cast<int>(lds));
+  if (e == hipSuccess) return RBX_OK;
+  (void)hipGetLastError();
+  return fail(RBX_ERR_LAUNCH, "%s: the opt-in to %zu bytes of dynamic LDS failed: %s", what, lds, hipGetErrorString(e));
 }
 
 // Philox4x32-10 (Salmon et al., SC'11): counter-based, so a parallel kernel and its replay in a backward pass draw the

@@ -209,8 +209,6 @@ __global__ __launch_bounds__(kMixBlock) void mix_bwd_kernel(const MixArgs a) {
   }
 }
 
-static bool mix_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // Validates the shape and the selections and fills everything of MixArgs that does not depend on the pass.
 static int mix_pack(const char* what, const float* const* x, const int64_t* x_stride, const float* const* z, const int32_t* sel,
                     const int32_t* sel_off, int64_t batch, int32_t hidden, int32_t experts, int32_t gates, int32_t softmax,
@@ -225,7 +223,7 @@ static int mix_pack(const char* what, const float* const* x, const int64_t* x_st
   *a = MixArgs{};
   for (int e = 0; e < experts; ++e) {
     if (!x[e]) return fail(RBX_ERR_INVALID, "%s: expert %d is NULL", what, e);
-    if (!mix_aligned(x[e]) || (x_stride[e] & 3) != 0 || x_stride[e] < 0)
+    if (!aligned16(x[e]) || (x_stride[e] & 3) != 0 || x_stride[e] < 0)
       return fail(RBX_ERR_UNSUPPORTED, "%s: expert %d must be 16-byte aligned with a row stride that is a multiple of 4 floats",
                   what, e);
     a->x[e] = x[e];
@@ -287,7 +285,7 @@ extern "C" int rbx_expert_mix_fwd(const float* const* x, const int64_t* x_stride
   const int rc = mix_pack("expert_mix_fwd", x, x_stride, z, sel, sel_off, batch, hidden, experts, gates, softmax, dtype, &a);
   if (rc != RBX_OK || batch == 0) return rc;
   if (!d_out || (softmax && !d_p)) return fail(RBX_ERR_INVALID, "expert_mix_fwd: NULL output");
-  if (!mix_aligned(d_out)) return fail(RBX_ERR_UNSUPPORTED, "expert_mix_fwd: out must be 16-byte aligned");
+  if (!aligned16(d_out)) return fail(RBX_ERR_UNSUPPORTED, "expert_mix_fwd: out must be 16-byte aligned");
   a.out = d_out;
   a.p = d_p;
   const dim3 grid = mix_grid(a), block(kMixBlock);
@@ -311,14 +309,14 @@ extern "C" int rbx_expert_mix_bwd(const float* const* x, const int64_t* x_stride
   if (rc != RBX_OK || batch == 0) return rc;
   if (!dout || (softmax && !d_p)) return fail(RBX_ERR_INVALID, "expert_mix_bwd: NULL pointer array");
   for (int t = 0; t < gates; ++t) {
-    if (dout[t] != nullptr && !mix_aligned(dout[t]))
+    if (dout[t] != nullptr && !aligned16(dout[t]))
       return fail(RBX_ERR_UNSUPPORTED, "expert_mix_bwd: dout %d must be 16-byte aligned", t);
     a.g[t] = dout[t];
     a.dz[t] = dz ? dz[t] : nullptr;
   }
   for (int e = 0; e < experts; ++e) {
     a.dx[e] = dx ? dx[e] : nullptr;
-    if (a.dx[e] != nullptr && !mix_aligned(a.dx[e]))
+    if (a.dx[e] != nullptr && !aligned16(a.dx[e]))
       return fail(RBX_ERR_UNSUPPORTED, "expert_mix_bwd: dx %d must be 16-byte aligned", e);
   }
   a.p = const_cast<float*>(d_p);

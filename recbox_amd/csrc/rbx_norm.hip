@@ -719,8 +719,7 @@ struct LnRow {
         // this part (profiles/r03: a 420 MB read-only pass 4.2 -> 5.3 TB/s)
         // (NT = false: a gradient the previous kernel has just written -- measured slower with the hint)
         if constexpr (VEC && NT) {
-          typedef float v4f __attribute__((ext_vector_type(4)));
-          const v4f t = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(row + e));
+          const f32x4 t = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(row + e));
           a[u * 4] = t[0]; a[u * 4 + 1] = t[1]; a[u * 4 + 2] = t[2]; a[u * 4 + 3] = t[3];
         } else if constexpr (VEC) {
           const float4 t = *reinterpret_cast<const float4*>(row + e);

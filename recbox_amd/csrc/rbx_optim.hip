@@ -76,7 +76,6 @@ struct UpdPack { UpdField f[kUpdFields]; };
 // re-zero launch of its own.  Non-temporal: nothing reads those zeros before the next backward overwrites them.
 template <bool VEC, bool CLEAR = false>
 __device__ __forceinline__ void update_row(const OptArgs& o, const UpdField& fd, size_t row, int lane_g, int G) {
-  typedef float v4f __attribute__((ext_vector_type(4)));
   constexpr int W = VEC ? 4 : 1;
   if (fd.w != nullptr && fd.g != nullptr) {
     float* wrow = fd.w + row * fd.w_stride;
@@ -87,8 +86,8 @@ __device__ __forceinline__ void update_row(const OptArgs& o, const UpdField& fd,
       if constexpr (VEC) {
         const float4 g = *reinterpret_cast<const float4*>(grow + e);
         if constexpr (CLEAR) {
-          const v4f z = {0.f, 0.f, 0.f, 0.f};
-          __builtin_nontemporal_store(z, reinterpret_cast<v4f*>(const_cast<float*>(grow) + e));
+          const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+          __builtin_nontemporal_store(z, reinterpret_cast<f32x4*>(const_cast<float*>(grow) + e));
         }
         float4 w = *reinterpret_cast<const float4*>(wrow + e);
         float4 a = s1row ? *reinterpret_cast<const float4*>(s1row + e) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -199,8 +198,6 @@ extern "C" int rbx_opt_advance(int32_t kind, float lr, float beta1, float beta2,
   opt_advance_kernel<<<1, 1, 0, as_stream(stream)>>>(kind, lr, beta1, beta2, lr_decay, d_t, d_step_size);
   return check_launch("opt_advance_kernel");
 }
-
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 static bool upd_vec_ok(const UpdField& u) {
   if (u.dim % 4 != 0 || u.w_stride % 4 != 0) return false;

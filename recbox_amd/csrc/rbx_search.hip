@@ -269,9 +269,8 @@ static int search_launch(const float* U, long long user_stride, long long rows, 
   const long long total = static_cast<long long>(tiles_u) * ranges;
   if (total >= INT_MAX) return fail(RBX_ERR_UNSUPPORTED, "search_ip: too many rows");
   const bool vec = (reinterpret_cast<uintptr_t>(I) & 15) == 0 && (item_ld & 3) == 0;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&search_ip_kernel<FILTER>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          static_cast<int>(lds)) != hipSuccess)
-    return fail(RBX_ERR_LAUNCH, "search_ip: %zu bytes of LDS refused", lds);
+  const int lrc = allow_lds("search_ip", &search_ip_kernel<FILTER>, lds);
+  if (lrc != RBX_OK) return lrc;
   hipLaunchKernelGGL((search_ip_kernel<FILTER>), dim3(static_cast<unsigned>(total)), dim3(256), lds, s, U, user_stride, rows,
                      I, item_ld, n, dim, p.dimp, ranges, tpr, n_tiles, static_cast<int>(total), vec, out, ldo, thr, cnt,
                      failed, cval, cpos, FILTER ? p.stage_cap : 0);

@@ -543,7 +543,6 @@ template <bool VEC>
 __device__ __forceinline__ void rezero_rows_block(const RedField* sf, const unsigned block, const unsigned* __restrict__ keys,
                                                   const unsigned* __restrict__ vals, const unsigned n,
                                                   const unsigned sentinel, const int lanes) {
-  typedef float v4f __attribute__((ext_vector_type(4)));
   constexpr int W = VEC ? 4 : 1;
   // Phase 1, a thread per sorted pair: three independent coalesced loads decide whether the pair starts a run and
   // where its row lives.  Phase 2, a lane group per pair: the wave walks its 64 pairs `64 / lanes` at a time and a
@@ -574,8 +573,8 @@ __device__ __forceinline__ void rezero_rows_block(const RedField* sf, const unsi
     const int d = __shfl(dim, src, 64);
     for (int e = lane_g * W; e < d; e += lanes * W) {
       if constexpr (VEC) {
-        const v4f z = {0.f, 0.f, 0.f, 0.f};
-        __builtin_nontemporal_store(z, reinterpret_cast<v4f*>(dst + e));
+        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        __builtin_nontemporal_store(z, reinterpret_cast<f32x4*>(dst + e));
       } else {
         dst[e] = 0.f;
       }

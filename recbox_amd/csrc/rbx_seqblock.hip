@@ -30,7 +30,6 @@
 
 namespace rbx {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kSbWaves = 8;                 // wavefronts per workgroup (independent of each other after the staging)
@@ -1202,8 +1201,6 @@ static int sb_bwd_grid(long long m) {
   return static_cast<int>(wgs < 1 ? 1 : wgs);
 }
 
-static bool sb_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 static int sb_grid(long long m) {
   const long long slabs = (m + 31) / 32;
   long long wgs = (slabs + kSbWaves - 1) / kSbWaves;
@@ -1222,15 +1219,14 @@ extern "C" int rbx_seqblock_qkv_fwd(const float* d_x, int64_t m, const float* d_
   if (m == 0) return RBX_OK;
   if (!d_x || !d_in_w || !d_mean || !d_rstd || !d_Q || !d_KV)
     return fail(RBX_ERR_INVALID, "rbx_seqblock_qkv_fwd: NULL operand");
-  if (!sb_aligned(d_x) || !sb_aligned(d_q) || !sb_aligned(d_Q) || !sb_aligned(d_KV))
+  if (!aligned16(d_x) || !aligned16(d_q) || !aligned16(d_Q) || !aligned16(d_KV))
     return fail(RBX_ERR_UNSUPPORTED, "rbx_seqblock_qkv_fwd: activations must be 16-byte aligned");
   SbQkvArgs a{d_x, d_ln_w, d_ln_b, d_in_w, d_in_b, eps, d_mean, d_rstd, d_q, d_Q, d_KV, static_cast<int>(m)};
   const size_t lds = sizeof(float) * (3 * kSbW + 5 * 64 + kSbWaves * kSbSlab);
   static bool once = false;
   if (!once) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(sb_qkv_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(lds)) != hipSuccess)
-      return fail(RBX_ERR_LAUNCH, "rbx_seqblock_qkv_fwd: %zu bytes of LDS refused", lds);
+    const int lrc = allow_lds("rbx_seqblock_qkv_fwd", sb_qkv_fwd_kernel, lds);
+    if (lrc != RBX_OK) return lrc;
     once = true;
   }
   hipLaunchKernelGGL(sb_qkv_fwd_kernel, dim3(sb_grid(m)), dim3(64 * kSbWaves), lds, as_stream(stream), a);
@@ -1251,8 +1247,8 @@ extern "C" int rbx_seqblock_ffn_fwd(const float* d_attn, const float* d_res, con
     return fail(RBX_ERR_INVALID, "rbx_seqblock_ffn_fwd: NULL operand");
   const bool pro = d_attn != nullptr;
   if (pro && (!d_res || !d_wo)) return fail(RBX_ERR_INVALID, "rbx_seqblock_ffn_fwd: the prologue needs d_res and d_wo");
-  if (!sb_aligned(d_x) || !sb_aligned(d_h) || !sb_aligned(d_out) || !sb_aligned(d_n) || !sb_aligned(d_attn) ||
-      !sb_aligned(d_res))
+  if (!aligned16(d_x) || !aligned16(d_h) || !aligned16(d_out) || !aligned16(d_n) || !aligned16(d_attn) ||
+      !aligned16(d_res))
     return fail(RBX_ERR_UNSUPPORTED, "rbx_seqblock_ffn_fwd: activations must be 16-byte aligned");
   SbFfnArgs a{d_attn, d_res, d_wo, d_bo, d_x, d_ln_w, d_ln_b, d_w1, d_b1, d_w2, d_b2, d_keep, eps,
               d_mean, d_rstd, d_n, d_h, d_out, static_cast<int>(m), d_res_mean, d_res_rstd, d_res_ln_w, d_res_ln_b};
@@ -1260,8 +1256,8 @@ extern "C" int rbx_seqblock_ffn_fwd(const float* d_attn, const float* d_res, con
   static bool once[2] = {false, false};
   const void* fn = pro ? reinterpret_cast<const void*>(sb_ffn_fwd_kernel<true>) : reinterpret_cast<const void*>(sb_ffn_fwd_kernel<false>);
   if (!once[pro]) {
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess)
-      return fail(RBX_ERR_LAUNCH, "rbx_seqblock_ffn_fwd: %zu bytes of LDS refused", lds);
+    const int lrc = allow_lds("rbx_seqblock_ffn_fwd", fn, lds);
+    if (lrc != RBX_OK) return lrc;
     once[pro] = true;
   }
   if (pro) hipLaunchKernelGGL(sb_ffn_fwd_kernel<true>, dim3(sb_grid(m)), dim3(64 * kSbWaves), lds, as_stream(stream), a);
@@ -1282,7 +1278,7 @@ extern "C" int rbx_seqblock_ffn_bwd(const float* d_dout, const float* d_keep, co
   if (m == 0) return RBX_OK;
   if (!d_dout || !d_h || !d_x || !d_mean || !d_rstd || !d_w1 || !d_w2 || !d_dx)
     return fail(RBX_ERR_INVALID, "rbx_seqblock_ffn_bwd: NULL operand");
-  if (!sb_aligned(d_dout) || !sb_aligned(d_h) || !sb_aligned(d_x) || !sb_aligned(d_dx))
+  if (!aligned16(d_dout) || !aligned16(d_h) || !aligned16(d_x) || !aligned16(d_dx))
     return fail(RBX_ERR_UNSUPPORTED, "rbx_seqblock_ffn_bwd: activations must be 16-byte aligned");
   const size_t need = rbx_seqblock_ffn_bwd_workspace_size(m);
   if (d_workspace == nullptr || workspace_bytes < need)
@@ -1293,9 +1289,8 @@ extern "C" int rbx_seqblock_ffn_bwd(const float* d_dout, const float* d_keep, co
   const size_t lds = sizeof(float) * (2 * kSbW + 2 * 64 + 3 * kSbBwdWaves * kSbSlab);
   static bool attr = false;                 // (the other order of the four products measured 353 vs 339 us: profiles/r04/INDEX.md)
   if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(sb_ffn_bwd_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(lds)) != hipSuccess)
-      return fail(RBX_ERR_LAUNCH, "rbx_seqblock_ffn_bwd: %zu bytes of LDS refused", lds);
+    const int lrc = allow_lds("rbx_seqblock_ffn_bwd", sb_ffn_bwd_kernel<0>, lds);
+    if (lrc != RBX_OK) return lrc;
     attr = true;
   }
   hipLaunchKernelGGL(sb_ffn_bwd_kernel<0>, dim3(grid), dim3(64 * kSbBwdWaves), lds, as_stream(stream), a);
@@ -1327,7 +1322,7 @@ extern "C" int rbx_seqblock_attn_in_bwd(const float* d_dQ, const float* d_dKV, c
   if (m == 0) return RBX_OK;
   if (!d_dQ || !d_dKV || !d_g || !d_x || !d_mean || !d_rstd || !d_in_w || !d_de)
     return fail(RBX_ERR_INVALID, "rbx_seqblock_attn_in_bwd: NULL operand");
-  if (!sb_aligned(d_dQ) || !sb_aligned(d_dKV) || !sb_aligned(d_g) || !sb_aligned(d_x) || !sb_aligned(d_de))
+  if (!aligned16(d_dQ) || !aligned16(d_dKV) || !aligned16(d_g) || !aligned16(d_x) || !aligned16(d_de))
     return fail(RBX_ERR_UNSUPPORTED, "rbx_seqblock_attn_in_bwd: activations must be 16-byte aligned");
   const size_t need = rbx_seqblock_attn_in_bwd_workspace_size(m);
   if (d_workspace == nullptr || workspace_bytes < need)
@@ -1338,9 +1333,8 @@ extern "C" int rbx_seqblock_attn_in_bwd(const float* d_dQ, const float* d_dKV, c
   const size_t lds = sizeof(float) * (3 * kSbW + 64 + kSbWaves * kSbSlab);
   static bool once = false;
   if (!once) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(sb_attn_in_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(lds)) != hipSuccess)
-      return fail(RBX_ERR_LAUNCH, "rbx_seqblock_attn_in_bwd: %zu bytes of LDS refused", lds);
+    const int lrc = allow_lds("rbx_seqblock_attn_in_bwd", sb_attn_in_bwd_kernel, lds);
+    if (lrc != RBX_OK) return lrc;
     once = true;
   }
   hipLaunchKernelGGL(sb_attn_in_bwd_kernel, dim3(grid), dim3(64 * kSbWaves), lds, as_stream(stream), a);
@@ -1368,7 +1362,7 @@ extern "C" int rbx_seqblock_attn_out_bwd(const float* d_g, const float* d_O, int
   if (m < 0 || m > (1LL << 30)) return fail(RBX_ERR_INVALID, "rbx_seqblock_attn_out_bwd: m = %lld", static_cast<long long>(m));
   if (m == 0) return RBX_OK;
   if (!d_g || !d_O || !d_wo || !d_dO) return fail(RBX_ERR_INVALID, "rbx_seqblock_attn_out_bwd: NULL operand");
-  if (!sb_aligned(d_g) || !sb_aligned(d_O) || !sb_aligned(d_dO))
+  if (!aligned16(d_g) || !aligned16(d_O) || !aligned16(d_dO))
     return fail(RBX_ERR_UNSUPPORTED, "rbx_seqblock_attn_out_bwd: activations must be 16-byte aligned");
   const size_t need = rbx_seqblock_attn_out_bwd_workspace_size(m);
   if (d_workspace == nullptr || workspace_bytes < need)
@@ -1378,9 +1372,8 @@ extern "C" int rbx_seqblock_attn_out_bwd(const float* d_g, const float* d_O, int
   const size_t lds = sizeof(float) * (kSbW + 64 + kSbWaves * kSbSlab);
   static bool once = false;
   if (!once) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(sb_attn_out_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(lds)) != hipSuccess)
-      return fail(RBX_ERR_LAUNCH, "rbx_seqblock_attn_out_bwd: %zu bytes of LDS refused", lds);
+    const int lrc = allow_lds("rbx_seqblock_attn_out_bwd", sb_attn_out_bwd_kernel, lds);
+    if (lrc != RBX_OK) return lrc;
     once = true;
   }
   hipLaunchKernelGGL(sb_attn_out_bwd_kernel, dim3(grid), dim3(64 * kSbWaves), lds, as_stream(stream), a);
@@ -1408,7 +1401,7 @@ extern "C" int rbx_seqblock_inproj_dw(const float* d_dQ, const float* d_dKV, con
   if (m < 0 || m > (1LL << 30)) return fail(RBX_ERR_INVALID, "rbx_seqblock_inproj_dw: m = %lld", static_cast<long long>(m));
   if (m == 0) return RBX_OK;
   if (!d_dQ || !d_dKV || !d_x || !d_mean || !d_rstd) return fail(RBX_ERR_INVALID, "rbx_seqblock_inproj_dw: NULL operand");
-  if (!sb_aligned(d_dQ) || !sb_aligned(d_dKV) || !sb_aligned(d_x))
+  if (!aligned16(d_dQ) || !aligned16(d_dKV) || !aligned16(d_x))
     return fail(RBX_ERR_UNSUPPORTED, "rbx_seqblock_inproj_dw: activations must be 16-byte aligned");
   const size_t need = rbx_seqblock_inproj_dw_workspace_size(m);
   if (d_workspace == nullptr || workspace_bytes < need)
@@ -1418,9 +1411,8 @@ extern "C" int rbx_seqblock_inproj_dw(const float* d_dQ, const float* d_dKV, con
   const size_t lds = sizeof(float) * (kSbInPart + kSbBwdWaves * kSbSlab);
   static bool once = false;
   if (!once) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(sb_inproj_dw_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(lds)) != hipSuccess)
-      return fail(RBX_ERR_LAUNCH, "rbx_seqblock_inproj_dw: %zu bytes of LDS refused", lds);
+    const int lrc = allow_lds("rbx_seqblock_inproj_dw", sb_inproj_dw_kernel, lds);
+    if (lrc != RBX_OK) return lrc;
     once = true;
   }
   hipLaunchKernelGGL(sb_inproj_dw_kernel, dim3(grid), dim3(64 * kSbBwdWaves), lds, as_stream(stream), a);

@@ -819,8 +819,7 @@ static int ta_launch_bwd(const TaPlan& t, int64_t B, const float* g, const float
                           4 * kTaChunks) * 4;
       static bool attr_set[8] = {false, false, false, false, false, false, false, false};
       if (!attr_set[G]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ta_reduce_lds_kernel<G>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if ((rc = allow_lds("ta_reduce_lds_kernel", ta_reduce_lds_kernel<G>, 160 * 1024)) != RBX_OK) return rc;
         attr_set[G] = true;
       }
       TaNumPack none;

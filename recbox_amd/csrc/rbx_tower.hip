@@ -166,7 +166,6 @@ __global__ __launch_bounds__(256) void cosdot_bwd_kernel(const float* __restrict
 // a lane group takes one SAMPLE and issues the loads of all its candidate rows (CH at a time) before the first reduction.
 // The scalar kernels above keep one row per group with two dependent 4-byte loads per lane and, in the backward, walk a
 // sample's candidates one after the other: 1.7-1.8 TB/s at cfg 3 ([65 536, 5, 128]: 93 / 193 us).
-typedef float cos_f4 __attribute__((ext_vector_type(4)));
 template <int G, int NV>
 __global__ __launch_bounds__(256) void cosdot_fwd_vec_kernel(const float* __restrict__ u, const float* __restrict__ v,
                                                              const long long v_outer, const long long B, const int N,
@@ -176,17 +175,17 @@ __global__ __launch_bounds__(256) void cosdot_fwd_vec_kernel(const float* __rest
   const int lane_g = threadIdx.x % G;
   const long long ngroups = static_cast<long long>(gridDim.x) * (blockDim.x / G);
   for (long long b = static_cast<long long>(blockIdx.x) * (blockDim.x / G) + threadIdx.x / G; b < B; b += ngroups) {
-    cos_f4 uu[NV];
+    f32x4 uu[NV];
 #pragma unroll
-    for (int q = 0; q < NV; ++q) uu[q] = *reinterpret_cast<const cos_f4*>(u + b * D + (lane_g + q * G) * 4);
+    for (int q = 0; q < NV; ++q) uu[q] = *reinterpret_cast<const f32x4*>(u + b * D + (lane_g + q * G) * 4);
     for (int n0 = 0; n0 < N; n0 += CH) {
-      cos_f4 x[CH][NV];
+      f32x4 x[CH][NV];
 #pragma unroll
       for (int c = 0; c < CH; ++c) {
         const int n = n0 + c < N ? n0 + c : N - 1;
 #pragma unroll
         for (int q = 0; q < NV; ++q)
-          x[c][q] = *reinterpret_cast<const cos_f4*>(v + b * v_outer + static_cast<long long>(n) * D + (lane_g + q * G) * 4);
+          x[c][q] = *reinterpret_cast<const f32x4*>(v + b * v_outer + static_cast<long long>(n) * D + (lane_g + q * G) * 4);
       }
 #pragma unroll
       for (int c = 0; c < CH; ++c) {
@@ -219,14 +218,14 @@ __global__ __launch_bounds__(256) void cosdot_bwd_vec_kernel(const float* __rest
   const int lane_g = threadIdx.x % G;
   const long long ngroups = static_cast<long long>(gridDim.x) * (blockDim.x / G);
   for (long long b = static_cast<long long>(blockIdx.x) * (blockDim.x / G) + threadIdx.x / G; b < B; b += ngroups) {
-    cos_f4 uu[NV], acc[NV];
+    f32x4 uu[NV], acc[NV];
 #pragma unroll
     for (int q = 0; q < NV; ++q) {
-      uu[q] = *reinterpret_cast<const cos_f4*>(u + b * D + (lane_g + q * G) * 4);
-      acc[q] = cos_f4{0.f, 0.f, 0.f, 0.f};
+      uu[q] = *reinterpret_cast<const f32x4*>(u + b * D + (lane_g + q * G) * 4);
+      acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     for (int n0 = 0; n0 < N; n0 += CH) {
-      cos_f4 x[CH][NV];
+      f32x4 x[CH][NV];
       float si[CH], g[CH];
 #pragma unroll
       for (int c = 0; c < CH; ++c) {
@@ -235,7 +234,7 @@ __global__ __launch_bounds__(256) void cosdot_bwd_vec_kernel(const float* __rest
         g[c] = dout[b * N + n] * scale;
 #pragma unroll
         for (int q = 0; q < NV; ++q)
-          x[c][q] = *reinterpret_cast<const cos_f4*>(v + b * v_outer + static_cast<long long>(n) * D + (lane_g + q * G) * 4);
+          x[c][q] = *reinterpret_cast<const f32x4*>(v + b * v_outer + static_cast<long long>(n) * D + (lane_g + q * G) * 4);
       }
 #pragma unroll
       for (int c = 0; c < CH; ++c) {
@@ -251,7 +250,7 @@ __global__ __launch_bounds__(256) void cosdot_bwd_vec_kernel(const float* __rest
         const bool live = si[c] > 0.f;
 #pragma unroll
         for (int q = 0; q < NV; ++q) {
-          cos_f4 vh, d;
+          f32x4 vh, d;
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             vh[j] = x[c][q][j] * a;
@@ -259,13 +258,13 @@ __global__ __launch_bounds__(256) void cosdot_bwd_vec_kernel(const float* __rest
             acc[q][j] += g[c] * vh[j];
           }
           if (dv != nullptr)
-            *reinterpret_cast<cos_f4*>(dv + b * dv_outer + static_cast<long long>(n0 + c) * D + (lane_g + q * G) * 4) = d;
+            *reinterpret_cast<f32x4*>(dv + b * dv_outer + static_cast<long long>(n0 + c) * D + (lane_g + q * G) * 4) = d;
         }
       }
     }
     if (du != nullptr) {
 #pragma unroll
-      for (int q = 0; q < NV; ++q) *reinterpret_cast<cos_f4*>(du + b * D + (lane_g + q * G) * 4) = acc[q];
+      for (int q = 0; q < NV; ++q) *reinterpret_cast<f32x4*>(du + b * D + (lane_g + q * G) * 4) = acc[q];
     }
   }
 }
@@ -284,8 +283,6 @@ static void pick_vec(int D, int* G, int* NV) {
   if (q <= 64 && (q & (q - 1)) == 0) { *G = q; *NV = 1; }
   else if (q % 64 == 0 && q / 64 <= 4) { *G = 64; *NV = q / 64; }
 }
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 static unsigned grid_for(long long groups, int g) {
   const int gpb = 256 / g;
   long long blocks = (groups + gpb - 1) / gpb;
@@ -582,8 +579,7 @@ __global__ __launch_bounds__(256) void rowscale_kernel(const float* __restrict__
   for (long long i = (static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x) * 4; i < total; i += step) {
     if constexpr (VEC) {                                   // a float4 never straddles two rows
       const float sc = s[i / dim];
-      typedef float v4f __attribute__((ext_vector_type(4)));
-      const v4f vv = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(x + i));       // streamed once
+      const f32x4 vv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(x + i));       // streamed once
       const float4 v = make_float4(vv[0], vv[1], vv[2], vv[3]);
       float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
       if (add != nullptr) a = *reinterpret_cast<const float4*>(add + (add_period > 0 ? i % add_period : i));
@@ -655,8 +651,7 @@ __global__ __launch_bounds__(256) void seq_colsum_partial_kernel(const float* __
       const long long bb = b + u < b1 ? b + u : b1 - 1;
       sc[u] = b + u < b1 ? s[bb * L + l] : 0.f;
       if constexpr (W == 4) {
-        typedef float v4f __attribute__((ext_vector_type(4)));
-        const v4f t = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(g + bb * cols + c));
+        const f32x4 t = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g + bb * cols + c));
         v[u][0] = t[0]; v[u][1] = t[1]; v[u][2] = t[2]; v[u][3] = t[3];
       } else {
         v[u][0] = g[bb * cols + c];

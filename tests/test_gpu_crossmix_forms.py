@@ -7,7 +7,7 @@ tests/test_gpu_crossmix.py runs the ranks {4, 8, 32, 64}, n of 3 .. 416 and at m
 The host-side quantities, restated here from the .hip file (``forms``):
   rsh = log2 r (the kernels split a column c of [E r] as expert c >> rsh, rank c & (r - 1)); ksteps = ceil(n / 4) MFMA steps
   xs = n rounded up to 4, + 4; hs = E r + 4; LDS forward 4 (16 (xs + 2 hs) + 128), backward 4 (16 (2 xs + 4 hs) + 256) bytes;
-  above 64 KiB a kernel has to be opted in (cm_allow_lds), and rbx_crossmix_supported caps the backward at 160 KiB
+  above 64 KiB a kernel has to be opted in (allow_lds), and rbx_crossmix_supported caps the backward at 160 KiB
   rpc = ceil(B / 16) rounded up to 64 rows per chunk of the weight-gradient sums, chunks = ceil(B / rpc), clast = the rows of
   the last chunk
 The workspace the library asks for (4 (B (4 E r + E) + 16 max(n E r, E r r, E n)) bytes) must agree with the restatement.

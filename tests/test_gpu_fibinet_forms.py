@@ -7,7 +7,7 @@ cannot pass.  tests/test_gpu_fibinet.py stops at F = 26 and B = 257; the forms b
 The host-side quantities, restated here from the .hip file (``forms``; P = F (F - 1) / 2, tiles = ceil(B / 16)):
   forward   split = max(1, min(8, ceil(1024 / tiles), (P + 3) / 4)), ppb = ceil(P / split) pairs per blockIdx.y, ylast = the
             pairs of the last blockIdx.y; LDS = 4 (16 S + 16 (F + 1)) bytes, S = F D rounded up to 64, + 4
-  dx        LDS = the forward's + 4 (64 (D + 1) + 64); above 64 KiB a kernel has to be opted in (bl_allow_lds)
+  dx        LDS = the forward's + 4 (64 (D + 1) + 64); above 64 KiB a kernel has to be opted in (allow_lds)
   dW        NP = 4 (D = 32) or 8 pairs per wavefront, groups = ceil(P / 4 NP), want = clamp(512 / groups, 1, tiles),
             tpc = ceil(tiles / want) tiles per chunk, chunks = ceil(tiles / tpc), clast = the tiles of the last chunk
   gate      forward grid = min(ceil(B / 4), 1024) workgroups of 4 samples, ftrips = trips of workgroup 0; backward grid =
