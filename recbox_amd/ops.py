@@ -6005,3 +6005,53 @@ def fignn_step(h, h0, w_attn, W_out, W_in, bias_p, w_ih, w_hh, b_ih, b_hh, want_
     if not _fignn_fused_ok(h, h0, weights):
         return fignn_step_torch(h, h0, *weights, want_graph=want_graph)
     return _FignnStep.apply(h, h0, *weights, bool(want_graph))
+
+
+# ---- SR-GNN: the session graph and one gated GNN step, in ATen (no kernel yet: see DESIGN.md) -----------------------------------
+
+
+def session_graph_torch(item_seq):
+    """SR-GNN's ``_get_slice`` (srgnn.py:163-199) in vectorised ATen on whatever device ``item_seq`` [B, L] (integer) lives on:
+    ``(alias_inputs [B, L] int64, A [B, L, 2 L] float32, items [B, L] int64, mask [B, L] bool)``.  ``items[b]`` are the row's
+    distinct ids in ascending order, padded with 0 (0 is itself a node where it occurs); ``alias_inputs[b, t]`` is the rank of
+    ``item_seq[b, t]`` among them; an edge t -> t + 1 exists for every t up to the last one before the first 0 at a position
+    >= 1; per distinct edge u -> v, ``A[b, v, u] = 1 / max(indeg(v), 1)`` and ``A[b, u, L + v] = 1 / max(outdeg(u), 1)``;
+    ``mask = item_seq > 0``.  No numpy, no loop over the batch and no host copy."""
+    if item_seq.dim() != 2 or item_seq.is_floating_point() or item_seq.dtype == torch.bool:
+        raise RuntimeError("session_graph: item_seq must be an integer [B, L] tensor, got %s %s" % (item_seq.dtype, tuple(item_seq.shape)))
+    B, L = item_seq.shape
+    seq = item_seq.long()
+    dev = seq.device
+    srt, _ = torch.sort(seq, dim=1)
+    first = torch.ones_like(srt, dtype=torch.bool)
+    first[:, 1:] = srt[:, 1:] != srt[:, :-1]
+    items = torch.zeros_like(srt).scatter_(1, first.cumsum(1) - 1, srt)          # equal ids write the same value
+    alias = ((srt.unsqueeze(1) < seq.unsqueeze(2)) & first.unsqueeze(1)).sum(-1)  # [B, L]: distinct ids below item_seq[b, t]
+    flags = torch.zeros((B, L * L), dtype=torch.float32, device=dev)
+    if L > 1:
+        valid = (seq[:, 1:] != 0).cumprod(1).to(torch.float32)
+        flags.scatter_reduce_(1, alias[:, :-1] * L + alias[:, 1:], valid, "amax", include_self=True)
+    u_A = flags.view(B, L, L)                                                       # [u][v]
+    indeg = u_A.sum(1).clamp_min(1.0)                                               # [B, v]
+    outdeg = u_A.sum(2).clamp_min(1.0)                                              # [B, u]
+    A = torch.cat([(u_A / indeg.unsqueeze(1)).transpose(1, 2), u_A / outdeg.unsqueeze(2)], dim=2)
+    return alias, A, items, seq > 0
+
+
+def session_gnn_step_torch(A, hidden, w_edge_in, b_edge_in, w_edge_out, b_edge_out, b_iah, b_ioh, w_ih, w_hh, b_ih, b_hh):
+    """One ``GNN.GNNCell`` of SR-GNN (srgnn.py:68-89) in plain ATen on whatever device the tensors live on.  ``A`` [B, L, 2 L]
+    (``[A_in | A_out]``), ``hidden`` [B, L, H], ``w_edge_in``, ``w_edge_out`` [H, H], ``b_edge_in``, ``b_edge_out``, ``b_iah``,
+    ``b_ioh`` [H], ``w_ih`` [3 H, 2 H], ``w_hh`` [3 H, H], ``b_ih``, ``b_hh`` [3 H] -> ``hy`` [B, L, H]."""
+    L = A.shape[1]
+    lin = torch.nn.functional.linear
+    input_in = torch.matmul(A[:, :, :L], lin(hidden, w_edge_in, b_edge_in)) + b_iah
+    input_out = torch.matmul(A[:, :, L:2 * L], lin(hidden, w_edge_out, b_edge_out)) + b_ioh
+    inputs = torch.cat([input_in, input_out], 2)
+    gi = lin(inputs, w_ih, b_ih)
+    gh = lin(hidden, w_hh, b_hh)
+    i_r, i_i, i_n = gi.chunk(3, 2)
+    h_r, h_i, h_n = gh.chunk(3, 2)
+    reset_gate = torch.sigmoid(i_r + h_r)
+    input_gate = torch.sigmoid(i_i + h_i)
+    new_gate = torch.tanh(i_n + reset_gate * h_n)
+    return (1 - input_gate) * hidden + input_gate * new_gate

@@ -3,8 +3,10 @@
 that of AutoInt (``AutoIntInteraction``, also exported here) over ``ops.field_attn`` and that of FiGNN (``GraphLayer``,
 ``FiGNNInteraction``, also exported here) over ``ops.field_attn`` and ``ops.fignn_step``; in ``sequential`` the layers of DIEN
 (``AGRUCell``, ``AUGRUCell``, ``DynamicRNN``, ``InterestExtractorNetwork``, ``InterestEvolvingLayer``) over ``ops.att_gru`` /
-``ops.gru``.  RecBole's ``(config, dataset)`` constructors, its recommender base classes, ``ContextSeqEmbLayer``, trainer and
+``ops.gru``, and SR-GNN's ``GNN`` and ``SRGNNEncoder`` (also exported here) over ``ops.session_graph_torch`` and
+``ops.session_gnn_step_torch``.  RecBole's ``(config, dataset)`` constructors, its recommender base classes, ``ContextSeqEmbLayer``, trainer and
 ``calculate_loss`` are not mirrored, and ``compat.install()`` registers nothing under ``recbole.*``: the trainable models
-(``AFM``, ``AutoInt``, ``FiGNN``, ``DIEN``) are registered with the rechub ranking zoo."""
+(``AFM``, ``AutoInt``, ``FiGNN``, ``DIEN``) are registered with the rechub ranking zoo; ``rechub.models.matching.SRGNN`` is the trainable SR-GNN."""
 from . import context_aware, layers, sequential  # noqa: F401
 from .context_aware import AutoIntInteraction, FiGNNInteraction, GraphLayer  # noqa: F401
+from .sequential import GNN, SRGNNEncoder  # noqa: F401

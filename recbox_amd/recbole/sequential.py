@@ -4,6 +4,8 @@ and ``state_dict`` keys.  For GPU tensors the attention-gated recurrence is ``op
 csrc/rbx_gru.hip), the plain GRUs are ``ops.gru`` with the lengths read on the device, and nothing is packed or copied to
 the host; for CPU tensors the same arithmetic runs in plain ATen.  RecBole's ``DIEN(config, dataset)`` model,
 ``ContextSeqEmbLayer`` and ``calculate_loss`` are not mirrored (``rechub.models.ranking.DIEN`` is the trainable model)."""
+import math
+
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -187,3 +189,96 @@ class InterestEvolvingLayer(nn.Module):
             att_outputs = self.attention_layer(queries, keys, keys_length).squeeze(1)          # [B, T]
             _, outputs = self.dynamic_rnn.forward_padded(keys, att_outputs, keys_length)
         return outputs
+
+
+def _linear(m, x):
+    return ops.linear(x, m.weight, m.bias) if x.is_cuda else m(x)
+
+
+def _lookup(table, ids):
+    """table(ids) for an [B, L] id block: the gather kernel on the GPU, nn.Embedding elsewhere."""
+    if not ids.is_cuda:
+        return table(ids)
+    from ..rechub.models.matching import ops_position
+    return ops_position(table, ids)
+
+
+class GNN(nn.Module):
+    """``recbole.model.sequential_recommender.srgnn.GNN`` (srgnn.py:29-95; GCSAN carries the same class): same constructor,
+    attribute names and ``state_dict`` keys (``w_ih``, ``w_hh``, ``b_ih``, ``b_hh``, ``b_iah``, ``b_ioh``,
+    ``linear_edge_in.*``, ``linear_edge_out.*``).  ``forward(A, hidden)`` is ``step`` calls of
+    ``ops.session_gnn_step_torch`` (the cell in ATen; it has no fused kernel yet).  The reference leaves the bare parameters
+    uninitialised until its model draws them; here they start from the model's own rule, uniform in +- 1 / sqrt(size)."""
+
+    def __init__(self, embedding_size, step=1):
+        super(GNN, self).__init__()
+        self.step = step
+        self.embedding_size = embedding_size
+        self.input_size = embedding_size * 2
+        self.gate_size = embedding_size * 3
+        self.w_ih = nn.Parameter(torch.empty(self.gate_size, self.input_size))
+        self.w_hh = nn.Parameter(torch.empty(self.gate_size, self.embedding_size))
+        self.b_ih = nn.Parameter(torch.empty(self.gate_size))
+        self.b_hh = nn.Parameter(torch.empty(self.gate_size))
+        self.b_iah = nn.Parameter(torch.empty(self.embedding_size))
+        self.b_ioh = nn.Parameter(torch.empty(self.embedding_size))
+        self.linear_edge_in = nn.Linear(self.embedding_size, self.embedding_size, bias=True)
+        self.linear_edge_out = nn.Linear(self.embedding_size, self.embedding_size, bias=True)
+        stdv = 1.0 / math.sqrt(self.embedding_size)
+        for p in (self.w_ih, self.w_hh, self.b_ih, self.b_hh, self.b_iah, self.b_ioh):
+            p.data.uniform_(-stdv, stdv)
+
+    def GNNCell(self, A, hidden):
+        return ops.session_gnn_step_torch(A, hidden, self.linear_edge_in.weight, self.linear_edge_in.bias, self.linear_edge_out.weight,
+                                          self.linear_edge_out.bias, self.b_iah, self.b_ioh, self.w_ih, self.w_hh, self.b_ih, self.b_hh)
+
+    def forward(self, A, hidden):
+        for _ in range(self.step):
+            hidden = self.GNNCell(A, hidden)
+        return hidden
+
+
+class SRGNNEncoder(nn.Module):
+    """The network of ``recbole.model.sequential_recommender.srgnn.SRGNN`` (srgnn.py:126-217) without RecBole's
+    ``(config, dataset)`` plumbing: the reference model's ``state_dict`` keys (``item_embedding``, ``gnn``, ``linear_one``,
+    ``linear_two``, ``linear_three``, ``linear_transform``) and its ``_reset_parameters``.  ``forward(item_seq, item_seq_len)``
+    is srgnn.py:201-217: the session graphs are built on the device (``ops.session_graph_torch``: vectorised ATen, no host copy), the node
+    embeddings go through ``GNN``, and the readout -- alpha has no softmax -- runs in ATen.  The last click is looked up at
+    ``(item_seq_len - 1).clamp_min(0)``, so an empty session does not fault (the reference's index is -1 there)."""
+
+    def __init__(self, n_items, embedding_size, step=1):
+        super(SRGNNEncoder, self).__init__()
+        self.n_items = n_items
+        self.embedding_size = embedding_size
+        self.step = step
+        self.item_embedding = nn.Embedding(n_items, embedding_size, padding_idx=0)
+        self.gnn = GNN(embedding_size, step)
+        self.linear_one = nn.Linear(embedding_size, embedding_size, bias=True)
+        self.linear_two = nn.Linear(embedding_size, embedding_size, bias=True)
+        self.linear_three = nn.Linear(embedding_size, 1, bias=False)
+        self.linear_transform = nn.Linear(embedding_size * 2, embedding_size, bias=True)
+        self._reset_parameters()
+
+    def _reset_parameters(self):
+        stdv = 1.0 / math.sqrt(self.embedding_size)
+        for weight in self.parameters():
+            weight.data.uniform_(-stdv, stdv)
+
+    def forward(self, item_seq, item_seq_len):
+        alias_inputs, A, items, mask = ops.session_graph_torch(item_seq)
+        hidden = self.gnn(A, _lookup(self.item_embedding, items))
+        H = self.embedding_size
+        seq_hidden = torch.gather(hidden, 1, alias_inputs.unsqueeze(-1).expand(-1, -1, H))
+        last = (item_seq_len.long() - 1).clamp_min(0).view(-1, 1, 1).expand(-1, -1, H)
+        ht = seq_hidden.gather(1, last).squeeze(1)
+        q1 = _linear(self.linear_one, ht).view(ht.size(0), 1, ht.size(1))
+        q2 = _linear(self.linear_two, seq_hidden)
+        alpha = self.linear_three(torch.sigmoid(q1 + q2))
+        a = torch.sum(alpha * seq_hidden * mask.view(mask.size(0), -1, 1).float(), 1)
+        return _linear(self.linear_transform, torch.cat([a, ht], dim=1))
+
+    def full_sort_scores(self, item_seq, item_seq_len):
+        """[B, n_items]: ``seq_output`` against the whole table (srgnn.py:247-255)."""
+        seq_output = self.forward(item_seq, item_seq_len)
+        w = self.item_embedding.weight
+        return ops.linear(seq_output, w.view_as(w)) if seq_output.is_cuda else torch.matmul(seq_output, w.t())

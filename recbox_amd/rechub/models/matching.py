@@ -653,6 +653,26 @@ class STAMP(torch.nn.Module):
         return ops.linear(h_s * h_t, self.item_emb.weight.view_as(self.item_emb.weight))
 
 
+class SRGNN(torch.nn.Module):
+    """SR-GNN (Wu et al., AAAI 2019) as a rechub-style trainable session model beside ``STAMP``: ``SRGNN(item_history_feature,
+    step=1)`` over ``recbole.SRGNNEncoder`` (RecBole's network, srgnn.py:126-217, with its ``state_dict`` keys under
+    ``encoder.`` and its uniform +- 1 / sqrt(dim) initialisation).  ``forward(input_dict)`` returns the [B, V] catalogue
+    scores.  The session lengths (non-zero ids per row; sessions are left-aligned) are counted on the device, the session
+    graphs are built there (``ops.session_graph_torch``), so a training step copies nothing to the host; the propagation
+    steps are ``ops.session_gnn_step_torch``."""
+
+    def __init__(self, item_history_feature, step=1):
+        super(SRGNN, self).__init__()
+        from ...recbole.sequential import SRGNNEncoder
+        self.item_history_feature = item_history_feature
+        self.encoder = SRGNNEncoder(item_history_feature.vocab_size, item_history_feature.embed_dim, step)
+
+    def forward(self, input_dict):
+        ids = input_dict[self.item_history_feature.name]
+        lengths = (ids != 0).sum(dim=1)                                                      # stays on the device
+        return self.encoder.full_sort_scores(ids, lengths)
+
+
 class YoutubeSBC(torch.nn.Module):
     """Sampling-bias-corrected in-batch softmax (drop-in for ``torch_rechub.models.matching.youtube_sbc.YoutubeSBC``): same
     constructor, ``mode`` switch, ``index0`` / ``index1`` and parameter names.  The towers are the shared lookup and MLP; the
