@@ -122,7 +122,7 @@ _RECHUB = {
 # entries); ``install()`` binds these as well.
 _RECHUB_ALSO = {"models.matching.comirec": ["ComirecSA"], "models.ranking": ["FiBiNet", "DCN", "DCNv2", "EDCN", "WideDeep", "AFM",
                                                                                   "DIEN", "AutoInt", "FiGNN"],
-                "models.matching": ["YoutubeSBC", "FaceBookDSSM"]}
+                "models.matching": ["YoutubeSBC", "FaceBookDSSM", "LightGCN"]}
 
 
 def alias_also():

@@ -184,6 +184,9 @@ class config(object):
     # runs the composition.  The kernels themselves take up to 48 fields x 32; the tests raise these two attributes.
     fignn_fields = 48
     fignn_dim = 16
+    # Edges per task of a PropGraph (a longer row is cut into segments of this many edges): the ragged bags' RBX_CSR_SEGMENT.
+    # The task list is what a propagation kernel would walk; there is none in the tree (limits).
+    graph_segment = 256
 
 
 def _require_cuda(t, what):
@@ -6055,3 +6058,194 @@ def session_gnn_step_torch(A, hidden, w_edge_in, b_edge_in, w_edge_out, b_edge_o
     input_gate = torch.sigmoid(i_i + h_i)
     new_gate = torch.tanh(i_n + reset_gate * h_n)
     return (1 - input_gate) * hidden + input_gate * new_gate
+
+
+# ---- graph propagation over a static sparse matrix: LightGCN / NGCF, in ATen (no kernel yet: see DESIGN.md) ---------------------
+
+
+class _GraphSide(object):
+    """One side (A or A^T) of a PropGraph: its CSR arrays and its task list, all device arrays computed once."""
+
+    def __init__(self, row_ptr, col, val, n_in, segment):
+        dev = row_ptr.device
+        self.row_ptr, self.col, self.val = row_ptr, col, val
+        self.n_out, self.n_in = row_ptr.numel() - 1, int(n_in)
+        deg = row_ptr[1:] - row_ptr[:-1]
+        n_seg = ((deg + (segment - 1)) // segment).clamp_min(1)                     # an empty row is one task of no edges
+        first = torch.cumsum(n_seg, 0) - n_seg
+        rows = torch.arange(self.n_out, dtype=torch.int64, device=dev)
+        task_row = torch.repeat_interleave(rows, n_seg)
+        k = torch.arange(task_row.numel(), dtype=torch.int64, device=dev) - first[task_row]
+        is_part = n_seg[task_row] > 1
+        slot = torch.cumsum(is_part.to(torch.int64), 0) - 1                         # a long row's partial rows are consecutive
+        self.task_start = (row_ptr[task_row] + k * segment).contiguous()
+        self.task_len = (deg[task_row] - k * segment).clamp(0, segment).to(torch.int32)
+        self.task_dst = torch.where(is_part, -(slot + 1), task_row).to(torch.int32)
+        long_rows = n_seg > 1
+        self.fin_row = rows[long_rows].to(torch.int32)
+        self.fin_ptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev),
+                                  torch.cumsum(n_seg[long_rows], 0)]).to(torch.int32)
+        self.n_tasks = int(task_row.numel())
+        self.n_fin = int(self.fin_row.numel())
+        self.n_partials = int(is_part.sum()) if self.n_fin else 0
+        if self.n_partials >= 2 ** 31:
+            raise ValueError("PropGraph: %d partial rows; raise the segment length" % self.n_partials)
+
+
+class PropGraph(object):
+    """A static sparse matrix A [N_out, N_in] prepared once for ``graph_prop``: the CSR of A (``row_ptr`` int64, ``col``
+    int32 ascending within a row, ``val`` float32), the CSR of A^T (``t_row_ptr``, ``t_col``, ``t_val``) with ``t_perm`` (int32:
+    the position of each edge of A^T in A's edge order, so that a per-edge scale given in A's order is read from either
+    side), and per side a task list: rows cut into segments of at most ``segment`` edges (``task_start`` int64, ``task_len``,
+    ``task_dst`` int32; ``task_dst`` < 0 names a partial row; ``fin_row`` / ``fin_ptr`` are the finish records of the rows
+    longer than a segment).  Built by ``from_coo``; nothing here runs per step.  The composition reads ``to_sparse_coo()``;
+    the transposed side and the task lists are what a propagation kernel walks (none is in the tree: DESIGN.md, limits)."""
+
+    def __init__(self, side, tside, t_perm, perm, segment):
+        self._side, self._tside, self.t_perm, self._perm, self.segment = side, tside, t_perm, perm, segment
+        self.shape = (side.n_out, side.n_in)
+        self._coo = None
+
+    row_ptr = property(lambda self: self._side.row_ptr)
+    col = property(lambda self: self._side.col)
+    val = property(lambda self: self._side.val)
+    t_row_ptr = property(lambda self: self._tside.row_ptr)
+    t_col = property(lambda self: self._tside.col)
+    t_val = property(lambda self: self._tside.val)
+    nnz = property(lambda self: int(self._side.col.numel()))
+    device = property(lambda self: self._side.col.device)
+
+    @classmethod
+    def from_coo(cls, rows, cols, values, shape, segment=None):
+        """``rows``, ``cols`` (integer) and ``values`` [nnz] of A ``shape`` = (N_out, N_in) on any device.  Duplicates are
+        summed as ``torch.sparse_coo_tensor(...).coalesce()`` sums them.  Dimensions of 2^31 and above, indices outside the
+        shape and a ``segment`` below 1 raise ``ValueError``."""
+        n_out, n_in = int(shape[0]), int(shape[1])
+        segment = int(config.graph_segment if segment is None else segment)
+        if n_out < 0 or n_in < 0 or n_out >= 2 ** 31 or n_in >= 2 ** 31:
+            raise ValueError("PropGraph: both dimensions must be below 2^31 (col is int32), got %s" % ((n_out, n_in),))
+        if segment < 1:
+            raise ValueError("PropGraph: segment must be at least 1, got %d" % segment)
+        rows, cols = rows.reshape(-1).long(), cols.reshape(-1).long()
+        values = values.reshape(-1).to(device=rows.device, dtype=torch.float32)
+        if not (rows.numel() == cols.numel() == values.numel()):
+            raise ValueError("PropGraph: rows, cols and values differ in length")
+        if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= n_out or int(cols.min()) < 0 or int(cols.max()) >= n_in):
+            raise ValueError("PropGraph: an index lies outside the shape %s" % ((n_out, n_in),))
+        coo = torch.sparse_coo_tensor(torch.stack([rows, cols]), values, (n_out, n_in)).coalesce()
+        r, c = coo.indices()[0], coo.indices()[1]
+        v = coo.values().contiguous()
+        dev = r.device
+
+        def ptr(index, n):
+            out = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            out[1:] = torch.cumsum(torch.bincount(index, minlength=n), 0)
+            return out
+        perm = torch.argsort(c * max(n_out, 1) + r)                      # A^T's edge order: by column, then by row
+        side = _GraphSide(ptr(r, n_out), c.to(torch.int32).contiguous(), v, n_in, segment)
+        tside = _GraphSide(ptr(c, n_in), r[perm].to(torch.int32).contiguous(), v[perm].contiguous(), n_out, segment)
+        inv = torch.empty_like(perm)
+        inv[perm] = torch.arange(perm.numel(), dtype=torch.int64, device=dev)
+        return cls(side, tside, perm.to(torch.int32), inv.to(torch.int32), segment)
+
+    def t(self):
+        """The transposed graph, a view: the two sides swapped, nothing copied."""
+        return PropGraph(self._tside, self._side, self._perm, self.t_perm, self.segment)
+
+    def to(self, device):
+        """A copy on ``device`` (the graph is rebuilt there from its coalesced edges)."""
+        coo = self.to_sparse_coo()
+        i = coo.indices().to(device)
+        return PropGraph.from_coo(i[0], i[1], coo.values().to(device), self.shape, self.segment)
+
+    def edge_rows(self):
+        """The row of every edge of A, int64 [nnz]."""
+        s = self._side
+        return torch.repeat_interleave(torch.arange(s.n_out, dtype=torch.int64, device=s.col.device), s.row_ptr[1:] - s.row_ptr[:-1])
+
+    def to_sparse_coo(self):
+        """A as a coalesced ``torch.sparse_coo_tensor`` (float32), the operand of the composition and of the tests."""
+        if self._coo is None:
+            idx = torch.stack([self.edge_rows(), self.col.long()])
+            self._coo = torch.sparse_coo_tensor(idx, self.val, self.shape, is_coalesced=True)
+        return self._coo
+
+
+def _blocks(x, what):
+    """A tensor or a pair of tensors as a tuple of one or two [n, D] row blocks."""
+    if torch.is_tensor(x):
+        x = (x,)
+    x = tuple(x)
+    if not 1 <= len(x) <= 2 or any(t.dim() != 2 for t in x) or any(t.shape[1] != x[0].shape[1] for t in x):
+        raise RuntimeError("graph_prop: %s must be a [n, D] tensor or a pair of them" % what)
+    return x
+
+
+def _cat(blocks):
+    return blocks[0] if len(blocks) == 1 else torch.cat(blocks, 0)
+
+
+def graph_prop_torch(G, x, add=None, alpha=1.0, beta=1.0, edge_scale=None):
+    """``alpha * (A scaled per edge) @ x + beta * add`` as the ``torch.sparse.mm`` composition on whatever device and in
+    whatever floating dtype the tensors are.  A pair is concatenated first, as the reference does."""
+    X = _cat(_blocks(x, "x"))
+    A = G.to_sparse_coo()
+    if A.device != X.device:
+        raise RuntimeError("graph_prop: the graph is on %s, x on %s" % (A.device, X.device))
+    if edge_scale is not None or X.dtype != torch.float32:
+        v = A.values() if edge_scale is None else A.values() * edge_scale.to(torch.float32)
+        A = torch.sparse_coo_tensor(A.indices(), v.to(X.dtype), A.shape, is_coalesced=True)
+    y = torch.sparse.mm(A, X)
+    if alpha != 1.0:
+        y = y * alpha
+    if add is not None:
+        R = _cat(_blocks(add, "add"))
+        y = y + (R if beta == 1.0 else R * beta)
+    return y
+
+
+def graph_prop_mean_torch(G, x, n_layers):
+    """``mean_k A^k x`` as the reference forms it (lightgcn.py:138-151): cat, K sparse products, stack, mean."""
+    X = _cat(_blocks(x, "x"))
+    layers = [X]
+    for _ in range(int(n_layers)):
+        layers.append(graph_prop_torch(G, layers[-1]))
+    return torch.mean(torch.stack(layers, dim=1), dim=1)
+
+
+def graph_prop(G, x, add=None, alpha=1.0, beta=1.0, edge_scale=None):
+    """``y [N_out, D] = alpha * sum_e val[e] edge_scale[e] x[col[e]] + beta * add`` over the PropGraph ``G``.  ``x`` (and
+    ``add``) may be a tensor or a pair of tensors that stand for the rows [0, n0) and [n0, N) -- the user and item tables.
+    ``edge_scale`` [nnz] is given in the edge order of ``G`` (``G.col`` / ``G.val``) and, like the graph's values, carries no
+    gradient: one that requires grad raises.  Runs ``graph_prop_torch`` on every device (no kernel: DESIGN.md, limits)."""
+    xb = _blocks(x, "x")
+    ab = _blocks(add, "add") if add is not None else ()
+    D = xb[0].shape[1]
+    if sum(t.shape[0] for t in xb) != G.shape[1] or (ab and (sum(t.shape[0] for t in ab) != G.shape[0] or ab[0].shape[1] != D)):
+        raise RuntimeError("graph_prop: x / add do not fit the graph %s" % (G.shape,))
+    if edge_scale is not None:
+        if edge_scale.requires_grad:
+            raise RuntimeError("graph_prop: edge_scale carries no gradient (trainable edge values are not supported)")
+        if edge_scale.numel() != G.nnz:
+            raise RuntimeError("graph_prop: edge_scale has %d entries, the graph %d edges" % (edge_scale.numel(), G.nnz))
+    return graph_prop_torch(G, x, add, alpha, beta, edge_scale)
+
+
+def graph_prop_mean(G, x, n_layers, layers=False):
+    """LightGCN's whole propagation, ``mean_{k <= K} A^k x`` (lightgcn.py:138-151), through ``graph_prop_mean_torch``.  ``G``
+    must be square.  ``x`` a tensor -> a tensor; a pair (n0 and n1 rows) -> the pair of results, two views of one tensor.
+    ``n_layers = 0`` returns ``x`` (a pair concatenated).  ``layers=True`` returns instead the list ``[x, A x, .., A^K x]``
+    through K ``graph_prop`` calls (NCL, SGL and NGCF need the layers)."""
+    xb = _blocks(x, "x")
+    K = int(n_layers)
+    if G.shape[0] != G.shape[1] or sum(t.shape[0] for t in xb) != G.shape[1] or K < 0:
+        raise RuntimeError("graph_prop_mean: a square graph, x with as many rows and n_layers >= 0 (graph %s)" % (G.shape,))
+    if layers:
+        out = [_cat(xb)]
+        for k in range(K):
+            out.append(graph_prop(G, xb if k == 0 else out[-1]))
+        return out
+    if K == 0:
+        return _cat(xb)
+    y = graph_prop_mean_torch(G, xb, K)
+    return tuple(torch.split(y, [t.shape[0] for t in xb], 0)) if len(xb) == 2 else y

@@ -673,6 +673,36 @@ class SRGNN(torch.nn.Module):
         return self.encoder.full_sort_scores(ids, lengths)
 
 
+class LightGCN(torch.nn.Module):
+    """LightGCN (He et al., SIGIR 2020) as a rechub-style trainable matching model: ``LightGCN(user_feature, item_feature,
+    graph, n_layers=3)`` over ``recbole.LightGCNEncoder`` (RecBole's network, lightgcn.py:60-151, with its ``state_dict`` keys
+    under ``encoder.``).  ``user_feature`` / ``item_feature`` are ``SparseFeature``s (``vocab_size`` users / items of
+    ``embed_dim``), ``graph`` the ``recbole.norm_adj`` of the training interactions.  ``forward(x)``: ``x[user_feature.name]``
+    [B] and ``x[item_feature.name]`` [B, 1 + n_neg] (the positive first) -> [B, 1 + n_neg] inner-product scores of the
+    propagated rows (``ops.pair_dot``); ``mode = "user"`` / ``"item"`` returns the propagated rows of the ids given.  The
+    propagation is ``ops.graph_prop_mean``."""
+
+    def __init__(self, user_feature, item_feature, graph, n_layers=3):
+        super(LightGCN, self).__init__()
+        from ...recbole.general import LightGCNEncoder
+        if user_feature.embed_dim != item_feature.embed_dim:
+            raise ValueError("LightGCN: users and items share one width")
+        self.user_feature, self.item_feature = user_feature, item_feature
+        self.encoder = LightGCNEncoder(user_feature.vocab_size, item_feature.vocab_size, user_feature.embed_dim, n_layers, graph)
+        self.mode = None
+
+    def forward(self, x):
+        user_all, item_all = self.encoder()
+        if self.mode == "user":
+            return user_all[x[self.user_feature.name].long().reshape(-1)]
+        if self.mode == "item":
+            return item_all[x[self.item_feature.name].long().reshape(-1)]
+        users = x[self.user_feature.name].long().reshape(-1)
+        items = x[self.item_feature.name].long().reshape(users.shape[0], -1)
+        u, v = user_all[users], item_all[items]                                              # [B, D], [B, 1 + n_neg, D]
+        return ops.pair_dot(u, v) if u.is_cuda else (u.unsqueeze(1) * v).sum(-1)
+
+
 class YoutubeSBC(torch.nn.Module):
     """Sampling-bias-corrected in-batch softmax (drop-in for ``torch_rechub.models.matching.youtube_sbc.YoutubeSBC``): same
     constructor, ``mode`` switch, ``index0`` / ``index1`` and parameter names.  The towers are the shared lookup and MLP; the
