@@ -1519,6 +1519,39 @@ int rbx_inbatch_band_bwd(const float* d_g, int64_t g_stride, const float* d_u, i
                          int64_t v_stride, const float* d_w, const float* d_ru, const float* d_rv, int64_t batch, int32_t dim,
                          int32_t n_neg, float eps, float inv_temperature, int32_t dtype, float* d_du, int64_t du_stride,
                          float* d_dv, int64_t dv_stride, float* d_dw, void* stream);
+
+/* ---- Caser: horizontal and vertical convolutions over a session block (csrc/rbx_caser.hip; additions only, the version stays) --
+ * Replaces, under third_party/recbole/model/sequential_recommender/caser.py:121-137, a Conv2d, a ReLU and a max_pool1d per height
+ * h = 1 .. L, the torch.cat of the L pieces, the vertical Conv2d and the second cat.  B = batch, d_x is read at
+ * x[b x_stride_b + l x_stride_l + d], d < D (16-byte aligned base, strides multiples of 4).  w_h and b_h are HOST arrays of L device
+ * pointers: w_h[h - 1] [n_h, h, D] and b_h[h - 1] [n_h], contiguous; they may be NULL when n_h = 0.  d_w_v [n_v, L], d_b_v [n_v]
+ * contiguous, NULL when n_v = 0.  d_out [B, n_v D + n_h L] contiguous:
+ *   out[b, v D + d]                 = b_v[v] + sum_l w_v[v, l] x[b, l, d]
+ *   out[b, n_v D + (h - 1) n_h + f] = max_{t <= L - h} relu(b_h[h - 1][f] + sum_{i < h, d} w_h[h - 1][f, i, d] x[b, t + i, d])
+ *   rbx_caser_fwd  one launch.  A workgroup stages the [L, D] blocks of 16 samples in LDS once (8 where 16 do not fit in 160 KiB,
+ *                  L D + pad4(L) > 2552); every (h, t) window is a [16, h D] x [h D, n_h] product on v_mfma_f32_16x16x4_f32 (exact fp32)
+ *                  with the filters read through L2, eight windows per pass; the running maximum and its t stay in registers; the
+ *                  vertical rows come from the same LDS image.  Writes d_out and, when not NULL, d_win [B, L n_h] (int8): the
+ *                  first maximal t of (h, f), or -1 where the ReLU is shut.
+ *   rbx_caser_bwd  d_dout [B, n_v D + n_h L] contiguous, d_win as the forward wrote it.  Only the winning window of a (b, h, f)
+ *                  carries gradient.  d_dx [B, L, D] contiguous (NULL: skipped): one launch, a thread per element with every sum
+ *                  in ascending (h, f), then v.  The weight gradients -- d_dw_v [n_v, L], d_db_v [n_v] and the host arrays dw_h,
+ *                  db_h of L device pointers laid out as w_h, b_h (all four NULL: skipped) -- take two launches: a thread per
+ *                  gradient element and run of samples into the workspace (rbx_caser_bwd_workspace_size: [runs <= 32][n_h D L
+ *                  (L + 1) / 2 + n_h L + n_v L + n_v] floats), and a tail that adds the runs in ascending order.
+ * Supported (rbx_caser_supported): 1 <= L <= 50, D a multiple of 4 in [4, 64], 0 <= n_h <= 16, 0 <= n_v <= 16, n_h + n_v > 0.
+ * dtype (the RBX_* code of every float tensor) RBX_F32.  Anything else: RBX_ERR_UNSUPPORTED before any launch.  batch = 0 launches
+ * nothing.  No atomics, every sum in a fixed order: two runs give the same bits.  Every launch goes to `stream`; no call
+ * allocates, clears, copies or reads back: capturable. */
+int rbx_caser_supported(int32_t L, int32_t D, int32_t n_h, int32_t n_v);
+int rbx_caser_fwd(const float* d_x, int64_t x_stride_b, int64_t x_stride_l, const float* d_w_v, const float* d_b_v,
+                  const void* const* w_h, const void* const* b_h, int64_t batch, int32_t L, int32_t D, int32_t n_h, int32_t n_v,
+                  int32_t dtype, float* d_out, int8_t* d_win, void* stream);
+size_t rbx_caser_bwd_workspace_size(int64_t batch, int32_t L, int32_t D, int32_t n_h, int32_t n_v);
+int rbx_caser_bwd(const float* d_dout, const float* d_x, int64_t x_stride_b, int64_t x_stride_l, const float* d_w_v,
+                  const void* const* w_h, const int8_t* d_win, int64_t batch, int32_t L, int32_t D, int32_t n_h, int32_t n_v,
+                  int32_t dtype, float* d_dx, float* d_dw_v, float* d_db_v, void* const* dw_h, void* const* db_h,
+                  void* d_workspace, size_t workspace_bytes, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -331,6 +331,11 @@ SIGNATURES = {
     "rbx_inbatch_band_fwd": (ctypes.c_int, [_P, _i64, _P, _i64, _P, _i64, _i32, _i32, _f32, _f32, _i32, _P, _i64, _P, _P, _P]),
     "rbx_inbatch_band_bwd": (ctypes.c_int, [_P, _i64, _P, _i64, _P, _i64, _P, _P, _P, _i64, _i32, _i32, _f32, _f32, _i32, _P, _i64,
                                             _P, _i64, _P, _P]),
+    "rbx_caser_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32]),
+    "rbx_caser_fwd": (ctypes.c_int, [_P, _i64, _i64, _P, _P, _P, _P, _i64, _i32, _i32, _i32, _i32, _i32, _P, _P, _P]),
+    "rbx_caser_bwd_workspace_size": (_sz, [_i64, _i32, _i32, _i32, _i32]),
+    "rbx_caser_bwd": (ctypes.c_int, [_P, _P, _i64, _i64, _P, _P, _P, _i64, _i32, _i32, _i32, _i32, _i32, _P, _P, _P, _P, _P, _P,
+                                     _sz, _P]),
 }
 
 

@@ -122,7 +122,7 @@ _RECHUB = {
 # entries); ``install()`` binds these as well.
 _RECHUB_ALSO = {"models.matching.comirec": ["ComirecSA"], "models.ranking": ["FiBiNet", "DCN", "DCNv2", "EDCN", "WideDeep", "AFM",
                                                                                   "DIEN", "AutoInt", "FiGNN"],
-                "models.matching": ["YoutubeSBC", "FaceBookDSSM", "LightGCN"]}
+                "models.matching": ["YoutubeSBC", "FaceBookDSSM", "LightGCN", "Caser"]}
 
 
 def alias_also():

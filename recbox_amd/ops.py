@@ -184,6 +184,11 @@ class config(object):
     # runs the composition.  The kernels themselves take up to 48 fields x 32; the tests raise these two attributes.
     fignn_fields = 48
     fignn_dim = 16
+    # Caser: the L horizontal convolutions with their ReLU and max over time, the vertical convolution and both concatenations
+    # as one launch that stages a tile of sessions in LDS once and saves only the winning window of each (b, h, f)
+    # (caser_conv: csrc/rbx_caser.hip) instead of 3 L + 1 ATen launches and the [B, n_h, L - h + 1] activations autograd keeps
+    # per height.  Off, or for what caser_conv_supported refuses: the composition (caser_conv_torch).
+    caser_fused = os.environ.get("RECBOX_AMD_CASER_FUSED", "1") != "0"
     # Edges per task of a PropGraph (a longer row is cut into segments of this many edges): the ragged bags' RBX_CSR_SEGMENT.
     # The task list is what a propagation kernel would walk; there is none in the tree (limits).
     graph_segment = 256
@@ -6008,6 +6013,165 @@ def fignn_step(h, h0, w_attn, W_out, W_in, bias_p, w_ih, w_hh, b_ih, b_hh, want_
     if not _fignn_fused_ok(h, h0, weights):
         return fignn_step_torch(h, h0, *weights, want_graph=want_graph)
     return _FignnStep.apply(h, h0, *weights, bool(want_graph))
+
+
+# ---- Caser: horizontal and vertical convolutions over a session block (csrc/rbx_caser.hip) --------------------------------------
+CASER_MAX_LEN, CASER_MAX_DIM, CASER_MAX_NH, CASER_MAX_NV = 50, 64, 16, 16
+# What caser_conv sends to the kernels: the cells of profiles/caser/table.md at which both forms were measured, alternating, and
+# the fused one was ahead beyond the spread.  Sessions of up to CASER_FUSED_LONG_LEN positions in batches of up to
+# CASER_FUSED_MAX_BATCH (10 x 64 x 8 x 4 at B = 512 and 4096: forward 5.9 x, forward + backward 11 x and 33 x), longer ones up to
+# CASER_FUSED_MAX_LEN in batches of up to CASER_FUSED_LONG_MAX_BATCH (at B = 512, 20 x 64 x 16 x 4: 3.6 x and 31 x; 50 x 64 x 8 x 4 and
+# 50 x 64 x 16 x 8: forward 1.9 x and 1.8 x, forward + backward 45 x and 27 x).  The other cells have the fused op's time
+# only and run the composition; the kernels themselves take every shape of caser_conv_supported at any batch, and the tests
+# raise all four constants.
+CASER_FUSED_MAX_LEN, CASER_FUSED_MAX_BATCH = 50, 4096
+CASER_FUSED_LONG_LEN, CASER_FUSED_LONG_MAX_BATCH = 10, 512
+
+
+def _caser_routed(B, L):
+    """Whether a batch of B sessions of L positions lies in the measured range above."""
+    if L > CASER_FUSED_MAX_LEN or B > CASER_FUSED_MAX_BATCH:
+        return False
+    return L <= CASER_FUSED_LONG_LEN or B <= CASER_FUSED_LONG_MAX_BATCH
+
+
+def caser_conv_supported(L, D, n_h, n_v, dtype=torch.float32):
+    """Whether the fused op takes this shape (rbx_caser_supported): float32, 1 <= L <= 50, ``D`` a multiple of 4 in 4 .. 64,
+    0 <= n_h <= 16, 0 <= n_v <= 16 and n_h + n_v > 0 (tiles of 16 samples, 8 where L D + pad4(L) > 2552).  What it refuses runs
+    ``caser_conv_torch``."""
+    if dtype != torch.float32:
+        return False
+    return bool(lib.rbx_caser_supported(int(L), int(D), int(n_h), int(n_v)))
+
+
+def _caser_dims(x, w_v, b_v, w_h, b_h):
+    """(B, L, D, n_h, n_v) of a ``caser_conv`` call; raises where the arguments do not fit each other."""
+    if x.dim() != 3:
+        raise RuntimeError("caser_conv: x must be [B, L, D], got %s" % (tuple(x.shape),))
+    B, L, D = x.shape
+    w_h, b_h = tuple(w_h), tuple(b_h)
+    if (w_v is None) != (b_v is None) or len(w_h) != len(b_h) or len(w_h) not in (0, L):
+        raise RuntimeError("caser_conv: w_v and b_v go together, and w_h, b_h hold L = %d tensors each or none" % L)
+    n_v = 0 if w_v is None else w_v.shape[0]
+    n_h = w_h[0].shape[0] if w_h else 0
+    if n_v and (tuple(w_v.shape) != (n_v, 1, L, 1) or tuple(b_v.shape) != (n_v,)):
+        raise RuntimeError("caser_conv: w_v %s, b_v %s do not fit L = %d" % (tuple(w_v.shape), tuple(b_v.shape), L))
+    for i, (w, b) in enumerate(zip(w_h, b_h)):
+        if tuple(w.shape) != (n_h, 1, i + 1, D) or tuple(b.shape) != (n_h,):
+            raise RuntimeError("caser_conv: w_h[%d] %s, b_h[%d] %s, expected %s and %s"
+                               % (i, tuple(w.shape), i, tuple(b.shape), (n_h, 1, i + 1, D), (n_h,)))
+    if n_h + n_v == 0:
+        raise RuntimeError("caser_conv: no filters (n_h = n_v = 0)")
+    return B, L, D, n_h, n_v
+
+
+def caser_conv_torch(x, w_v, b_v, w_h, b_h):
+    """Caser's convolutional layers (caser.py:121-137) as the reference composes them, on whatever device and in whatever
+    floating dtype the tensors are: ``x`` [B, L, D], ``w_v`` [n_v, 1, L, 1] and ``b_v`` [n_v] (both None: no vertical part),
+    ``w_h[h - 1]`` [n_h, 1, h, D] and ``b_h[h - 1]`` [n_h] for h = 1 .. L (both empty: no horizontal part) ->
+    ``[B, n_v D + n_h L]``:
+
+        out[b, v D + d]                 = b_v[v] + sum_l w_v[v, 0, l, 0] x[b, l, d]
+        out[b, n_v D + (h - 1) n_h + f] = max_t relu(b_h[h - 1][f] + sum_{i < h, d} w_h[h - 1][f, 0, i, d] x[b, t + i, d])
+
+    A Conv2d, a ReLU and a max_pool1d per height, then the two cats.  No padding mask: padded positions are zero rows that are
+    convolved like the others.  Serves what the fused op refuses and is what it is measured against."""
+    B, L, D, n_h, n_v = _caser_dims(x, w_v, b_v, w_h, b_h)
+    x4 = x.unsqueeze(1)
+    pieces = []
+    if n_v:
+        pieces.append(torch.nn.functional.conv2d(x4, w_v, b_v).reshape(B, n_v * D))
+    if n_h:
+        out_hs = []
+        for w, b in zip(w_h, b_h):
+            conv_out = torch.relu(torch.nn.functional.conv2d(x4, w, b).squeeze(3))
+            out_hs.append(torch.nn.functional.max_pool1d(conv_out, conv_out.size(2)).squeeze(2))
+        pieces.append(torch.cat(out_hs, 1))
+    return pieces[0] if len(pieces) == 1 else torch.cat(pieces, 1)
+
+
+def _caser_fused_ok(x, tensors, L, D, n_h, n_v):
+    """The refusals of ``caser_conv`` that run the composition: the switch, an empty batch, a length or batch the routing excludes, CPU
+    or non-float32 tensors, a shape outside the kernels' range, an ``x`` the kernels cannot read in place."""
+    if not config.caser_fused or x.shape[0] == 0 or not _caser_routed(x.shape[0], L):
+        return False
+    if any((not t.is_cuda) or t.dtype != torch.float32 for t in (x,) + tuple(tensors)):
+        return False
+    if not caser_conv_supported(L, D, n_h, n_v):
+        return False
+    return _fields_in_place(x)
+
+
+class _CaserConv(torch.autograd.Function):
+    """out [B, n_v D + n_h L] as ONE launch (rbx_caser_fwd); backward = rbx_caser_bwd (one launch for dx; one per-element
+    launch plus the tail that adds the runs for the weight gradients).  Saved: x, the parameters and the winners [B, L n_h]
+    (int8: the first maximal t, -1 where the ReLU is shut)."""
+
+    @staticmethod
+    def forward(ctx, x, w_v, b_v, n_h, *wb):
+        B, L, D = x.shape
+        dev = x.device
+        k = len(wb) // 2
+        w_h = tuple(t.contiguous() for t in wb[:k])
+        b_h = tuple(t.contiguous() for t in wb[k:])
+        n_v = 0 if w_v is None else w_v.shape[0]
+        wv = w_v.contiguous() if n_v else None
+        bv = b_v.contiguous() if n_v else None
+        out = torch.empty((B, n_v * D + n_h * L), dtype=torch.float32, device=dev)
+        win = torch.empty((B, L * n_h), dtype=torch.int8, device=dev) if n_h else None
+        check(_timed(("caser_fwd", B, L, D, n_h, n_v),
+                     lambda: lib.rbx_caser_fwd(_ptr(x), x.stride(0), x.stride(1), _ptr(wv), _ptr(bv),
+                                               _ptr_array(w_h) if n_h else None, _ptr_array(b_h) if n_h else None, B, L, D, n_h,
+                                               n_v, _lib.RBX_F32, _ptr(out), _ptr(win), _stream())))
+        ctx.save_for_backward(x, wv, bv, win, *(w_h + b_h))
+        ctx.dims = (B, L, D, n_h, n_v)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, wv, bv, win = ctx.saved_tensors[:4]
+        B, L, D, n_h, n_v = ctx.dims
+        w_h = ctx.saved_tensors[4:4 + (L if n_h else 0)]
+        b_h = ctx.saved_tensors[4 + len(w_h):]
+        dev = x.device
+        need = ctx.needs_input_grad
+        dout = dout.float().contiguous()
+        want_w = any(need[1:3]) or any(need[4:])
+        dx = torch.empty((B, L, D), dtype=torch.float32, device=dev) if need[0] else None
+        dwv = dbv = None
+        dw_h, db_h = (), ()
+        ws_bytes, wsp = 0, None
+        if want_w:
+            if n_v:
+                dwv, dbv = torch.empty_like(wv), torch.empty_like(bv)
+            dw_h, db_h = tuple(torch.empty_like(t) for t in w_h), tuple(torch.empty_like(t) for t in b_h)
+            ws_bytes = lib.rbx_caser_bwd_workspace_size(B, L, D, n_h, n_v)
+            wsp = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        if dx is not None or want_w:
+            check(_timed(("caser_bwd", B, L, D, n_h, n_v),
+                         lambda: lib.rbx_caser_bwd(_ptr(dout), _ptr(x), x.stride(0), x.stride(1), _ptr(wv),
+                                                   _ptr_array(w_h) if n_h else None, _ptr(win), B, L, D, n_h, n_v, _lib.RBX_F32,
+                                                   _ptr(dx), _ptr(dwv), _ptr(dbv), _ptr_array(dw_h) if dw_h else None,
+                                                   _ptr_array(db_h) if db_h else None, _ptr(wsp), ws_bytes, _stream())))
+        grads = tuple(g if need[4 + i] else None for i, g in enumerate(dw_h + db_h)) if want_w else (None,) * (len(need) - 4)
+        return (dx, dwv if need[1] else None, dbv if need[2] else None, None) + grads
+
+
+def caser_conv(x, w_v, b_v, w_h, b_h):
+    """Caser's convolutional layers as one autograd node over rbx_caser_fwd / _bwd (see ``caser_conv_torch`` for the formulas
+    and the arguments, which are the reference model's parameters as they are).  ``x`` may be a strided view that the kernels
+    read in place (unit inner stride, 16-byte aligned, strides multiples of 4 floats).  The backward follows torch's: the
+    gradient of a (b, h, f) goes to the first maximal window and only where its pre-activation is positive.  Saved: x, the
+    parameters and the winners [B, L n_h] as int8; nothing per window exists in either direction.  CPU or non-float32
+    tensors, an empty batch, what ``caser_conv_supported`` refuses, a length and batch outside the measured range
+    (``CASER_FUSED_MAX_LEN``, ``CASER_FUSED_MAX_BATCH``, ``CASER_FUSED_LONG_LEN``, ``CASER_FUSED_LONG_MAX_BATCH``), an ``x`` that
+    cannot be read in place and ``config.caser_fused = False`` run ``caser_conv_torch``."""
+    B, L, D, n_h, n_v = _caser_dims(x, w_v, b_v, w_h, b_h)
+    w_h, b_h = tuple(w_h), tuple(b_h)
+    tensors = ((w_v, b_v) if n_v else ()) + w_h + b_h
+    if not _caser_fused_ok(x, tensors, L, D, n_h, n_v):
+        return caser_conv_torch(x, w_v, b_v, w_h, b_h)
+    return _CaserConv.apply(x, w_v if n_v else None, b_v if n_v else None, n_h, *(w_h + b_h))
 
 
 # ---- SR-GNN: the session graph and one gated GNN step, in ATen (no kernel yet: see DESIGN.md) -----------------------------------

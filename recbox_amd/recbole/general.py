@@ -1,7 +1,7 @@
 """Mirrors of RecBole's graph collaborative-filtering networks (third_party/recbole/model/general_recommender) over
 ``ops.graph_prop`` / ``ops.graph_prop_mean`` (the ``torch.sparse.mm`` composition; no kernel: DESIGN.md): ``norm_adj`` (``get_norm_adj_mat`` of lightgcn.py /
 ngcf.py on the device), ``LightGCNEncoder`` (lightgcn.py:60-151), ``BiGNNLayer`` (model/layers.py:208-233), ``NGCFEncoder``
-(ngcf.py:50-165) and the two losses they train with, ``BPRLoss`` and ``EmbLoss`` (model/loss.py).  RecBole's ``(config,
+(ngcf.py:50-165) and the losses of model/loss.py, ``BPRLoss``, ``RegLoss`` (Caser's) and ``EmbLoss``.  RecBole's ``(config,
 dataset)`` constructors, ``GeneralRecommender``, ``calculate_loss`` and the trainers are not mirrored: an encoder takes the
 sizes and the graph."""
 import torch
@@ -45,6 +45,16 @@ class BPRLoss(nn.Module):
             d = pos_score - neg_score
             return ops.pair_logsigmoid_loss(d, -d, None, 0.5 / d.numel())
         return -torch.log(self.gamma + torch.sigmoid(pos_score - neg_score)).mean()
+
+
+class RegLoss(nn.Module):
+    """L2 regularisation on model parameters (loss.py:50-63): the sum of the 2-norms of the tensors given; ``None`` for none."""
+
+    def forward(self, parameters):
+        reg_loss = None
+        for W in parameters:
+            reg_loss = W.norm(2) if reg_loss is None else reg_loss + W.norm(2)
+        return reg_loss
 
 
 class EmbLoss(nn.Module):

@@ -282,3 +282,73 @@ class SRGNNEncoder(nn.Module):
         seq_output = self.forward(item_seq, item_seq_len)
         w = self.item_embedding.weight
         return ops.linear(seq_output, w.view_as(w)) if seq_output.is_cuda else torch.matmul(seq_output, w.t())
+
+
+class CaserEncoder(nn.Module):
+    """The network of ``recbole.model.sequential_recommender.caser.Caser`` (caser.py:42-155) without RecBole's ``(config,
+    dataset)`` plumbing: the reference model's ``state_dict`` keys (``user_embedding``, ``item_embedding``, ``conv_v``,
+    ``conv_h.<h - 1>``, ``fc1``, ``fc2``) and its ``_init_weights``.  ``conv_v`` and ``conv_h`` are ``nn.Conv2d`` modules kept as
+    parameter holders: ``forward(user, item_seq)`` is caser.py:114-145 with both convolution branches, the ReLU, the max over
+    time and the two concatenations as one ``ops.caser_conv`` call, the dropout as ``ops.dropout`` and the two fully-connected
+    layers as ``ops.linear(..., act="relu")``.  As in the reference, ``max_seq_length`` fixes L and padded positions are zero
+    rows that are convolved like the others."""
+
+    def __init__(self, n_users, n_items, embedding_size, max_seq_length, n_h, n_v, dropout_prob=0.0, reg_weight=0.0):
+        super(CaserEncoder, self).__init__()
+        self.n_users, self.n_items = n_users, n_items
+        self.embedding_size = embedding_size
+        self.max_seq_length = max_seq_length
+        self.n_h, self.n_v = n_h, n_v
+        self.dropout_prob = dropout_prob
+        self.reg_weight = reg_weight
+        self.user_embedding = nn.Embedding(n_users, embedding_size, padding_idx=0)
+        self.item_embedding = nn.Embedding(n_items, embedding_size, padding_idx=0)
+        self.conv_v = nn.Conv2d(in_channels=1, out_channels=n_v, kernel_size=(max_seq_length, 1))
+        self.conv_h = nn.ModuleList([nn.Conv2d(in_channels=1, out_channels=n_h, kernel_size=(i + 1, embedding_size))
+                                     for i in range(max_seq_length)])
+        self.fc1_dim_v = n_v * embedding_size
+        self.fc1_dim_h = n_h * max_seq_length
+        self.fc1 = nn.Linear(self.fc1_dim_v + self.fc1_dim_h, embedding_size)
+        self.fc2 = nn.Linear(embedding_size + embedding_size, embedding_size)
+        self.apply(self._init_weights)
+
+    def _init_weights(self, module):
+        if isinstance(module, nn.Embedding):
+            nn.init.normal_(module.weight.data, 0, 1.0 / module.embedding_dim)
+        elif isinstance(module, nn.Linear):
+            nn.init.xavier_normal_(module.weight.data)
+            if module.bias is not None:
+                nn.init.constant_(module.bias.data, 0)
+
+    def conv(self, item_seq_emb):
+        """[B, n_v D + n_h L] of an embedded session [B, L, D]: caser.py:121-137."""
+        w_h = [c.weight for c in self.conv_h] if self.n_h else []
+        b_h = [c.bias for c in self.conv_h] if self.n_h else []
+        return ops.caser_conv(item_seq_emb, self.conv_v.weight if self.n_v else None, self.conv_v.bias if self.n_v else None,
+                              w_h, b_h)
+
+    def forward(self, user, item_seq):
+        item_seq_emb = _lookup(self.item_embedding, item_seq)                                # [B, L, D]
+        user_emb = _lookup(self.user_embedding, user.reshape(-1, 1)).squeeze(1)             # [B, D]
+        out = self.conv(item_seq_emb)
+        if out.is_cuda:
+            out = ops.dropout(out, self.dropout_prob, self.training)
+            z = ops.linear(out, self.fc1.weight, self.fc1.bias, act="relu")
+            return ops.linear(torch.cat([z, user_emb], 1), self.fc2.weight, self.fc2.bias, act="relu")
+        out = F.dropout(out, self.dropout_prob, self.training)
+        z = F.relu(self.fc1(out))
+        return F.relu(self.fc2(torch.cat([z, user_emb], 1)))
+
+    def reg_loss_conv_h(self):
+        """L2 loss on conv_h (caser.py:147-155): ``reg_weight`` times the sum of the filters' 2-norms."""
+        loss_conv_h = 0
+        for name, parm in self.conv_h.named_parameters():
+            if name.endswith("weight"):
+                loss_conv_h = loss_conv_h + parm.norm(2)
+        return self.reg_weight * loss_conv_h
+
+    def full_sort_scores(self, user, item_seq):
+        """[B, n_items]: ``seq_output`` against the whole table (caser.py:196-204)."""
+        seq_output = self.forward(user, item_seq)
+        w = self.item_embedding.weight
+        return ops.linear(seq_output, w.view_as(w)) if seq_output.is_cuda else torch.matmul(seq_output, w.t())

@@ -673,6 +673,27 @@ class SRGNN(torch.nn.Module):
         return self.encoder.full_sort_scores(ids, lengths)
 
 
+class Caser(torch.nn.Module):
+    """Caser (Tang and Wang, WSDM 2018) as a rechub-style trainable session model beside ``SRGNN``: ``Caser(user_feature,
+    item_history_feature, max_len, n_h=8, n_v=4, dropout_prob=0.4, reg_weight=1e-4)`` over ``recbole.CaserEncoder`` (RecBole's network,
+    caser.py:42-155, with its ``state_dict`` keys under ``encoder.`` and its initialisation).  ``user_feature`` is a
+    ``SparseFeature`` of the user ids, ``item_history_feature`` the ``SequenceFeature`` of the clicks and ``max_len`` the session
+    length L the filters are built for.  ``forward(input_dict)`` returns the [B, V] catalogue scores; both convolution branches are
+    one ``ops.caser_conv`` call."""
+
+    def __init__(self, user_feature, item_history_feature, max_len, n_h=8, n_v=4, dropout_prob=0.4, reg_weight=1e-4):
+        super(Caser, self).__init__()
+        from ...recbole.sequential import CaserEncoder
+        if user_feature.embed_dim != item_history_feature.embed_dim:
+            raise ValueError("Caser: users and items share one width")
+        self.user_feature, self.item_history_feature = user_feature, item_history_feature
+        self.encoder = CaserEncoder(user_feature.vocab_size, item_history_feature.vocab_size, item_history_feature.embed_dim,
+                                    int(max_len), n_h, n_v, dropout_prob, reg_weight)
+
+    def forward(self, input_dict):
+        return self.encoder.full_sort_scores(input_dict[self.user_feature.name], input_dict[self.item_history_feature.name])
+
+
 class LightGCN(torch.nn.Module):
     """LightGCN (He et al., SIGIR 2020) as a rechub-style trainable matching model: ``LightGCN(user_feature, item_feature,
     graph, n_layers=3)`` over ``recbole.LightGCNEncoder`` (RecBole's network, lightgcn.py:60-151, with its ``state_dict`` keys
